@@ -392,6 +392,8 @@ def bench_infer_mixing(args, rank, world, use_dist):
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"predict": out.cpu().numpy()})
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -434,6 +436,29 @@ def bench_infer_mixing(args, rank, world, use_dist):
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <dump_dir>/<name>.npy in float32 /
+    float64, so that two builds can be compared output for output (the inputs are seeded: the same arguments give the same
+    inputs).  Past `limit` bytes in all, an array keeps a fixed seeded sample of its rows (first axis), sorted, and the row
+    indices go beside it as <name>.rows.npy (float64)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32))
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.ndim > 0 and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = max(1, min(a.shape[0], int(limit * (a.nbytes / total)) // (row_bytes + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(dump_dir, name + ".rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+    log("outputs of the last timed step written to %s: %s" % (dump_dir, ", ".join(sorted(arrays))))
 
 
 CPU_THREADS = 16
@@ -916,7 +941,14 @@ def main():
                          "teacher-forced training step (fwd + BPTT + Adam, data-parallel all-reduce when N > 1); "
                          "train_mixing / infer_mixing: configs[2] (512 sequences per GPU); config1: configs[0] latency; "
                          "convlstm: configs[3]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="modes infer and infer_mixing: after the timed region, write what the timed call returned in its last "
+                         "step as DIR/<name>.npy (rank 0; float32, at most 64 MB in all - a seeded row sample past that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode not in ("infer", "infer_mixing"):
+        ap.error("--dump-outputs is implemented for --mode infer and infer_mixing only")
     t_default = 10 if args.mode in ("train_mixing", "infer_mixing") else 30
     args.t_in = t_default if args.t_in is None else args.t_in
     args.t_out = t_default if args.t_out is None else args.t_out
@@ -1026,6 +1058,8 @@ def main():
     ws.check()
     xmode = ws.exchange_mode()
     step_ms_events = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"seq2seq_decode": out.cpu().numpy()})
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -266,7 +266,7 @@ def test_epoch_loop_equals_the_scripts_loop_and_checkpoints_round_trip(kind, tmp
     assert [os.path.basename(p) for p in d3.saved] == ["LSTM_tepoch1.ckpt.npz"]      # epoch 1 is odd: only the final save
 
 
-def test_dropout_masks_training_and_total_batch():
+def test_dropout_masks_training_and_total_batch(tmp_path):
     """The driver at the script's settings (dropout 0.1 -> DropoutWrapper masks on what layer 1 hands up, drawn per step from
     a seeded generator): two runs with the same seed agree bit for bit, another seed differs; and
     total_batch_of counts lstm.py:570-580's steps."""
@@ -277,7 +277,7 @@ def test_dropout_masks_training_and_total_batch():
     outs = []
     for seed in (3, 3, 4):
         tr = _trainer(51, 400, "meanvar", lr=cfg.LEARNING_RATE)
-        drv = LSTMPyDriver(tr, cfg, model_path="/tmp/fov_lstm_drv_%d/LSTM_x.ckpt" % os.getpid(), dropout=0.1, seed=seed)
+        drv = LSTMPyDriver(tr, cfg, model_path=str(tmp_path / "LSTM_x.ckpt"), dropout=0.1, seed=seed)
         drv.fit(FakeDataLayer(61, fixed=True), 6, training_epochs=2, batch_size=10, starting_epoch=3)
         outs.append((tr.flat.clone(), list(drv.history)))
     assert torch.equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1]
