@@ -724,6 +724,27 @@ int fov_window_stacks(const float* x, float* enc, float* fut, float* fut_in, int
 int fov_fov_hit_rate(const float* pred_xyz, int64_t pred_row_stride, const float* gt_xyz, int64_t gt_row_stride,
                      float* out, int64_t rows, float span_deg, float gt_span_deg, fov_stream_t stream);
 
+/* One-hot FoV heat maps of the ConvLSTM heat-map model (cfg.use_one_hot), built from the trajectories they encode:
+ *   replaces: mycode/utility.py:522-544 (_save_theta_phi_index: frame centre xyz -> 10-degree (theta, phi) bin indices,
+ *             through xyz2thetaphi of mycode/dataIO.py:77-82), :557-571 (_create_one_hot) and the transpose to channels-last
+ *             of mycode/convlstm_seq2seq.py:356-374 (convlstm_heatmap.py:45-130).
+ * Input: xyz (N,T,30,3) fp32, each step's 30 frames contiguous, steps / sequences `xyz_step_stride` / `xyz_seq_stride` floats
+ * apart (the (N,T,1,30,3) form is a stride); OR theta_index, phi_index (N,T,30) int32 contiguous (the reference's cached
+ * pickles).  Pass xyz = NULL for the second form.  Bins are computed in fp64, in the reference's operation order:
+ *   theta = mod(atan2(y,x), 2pi) - pi, phi = mod(atan2(z, sqrt(x^2+y^2)) + pi/2, pi)  (mod with the divisor's sign),
+ *   ti = floor((theta+pi)/pi*180/10) (36 -> 35), pi = floor(phi/pi*180/10) (18 -> 17).
+ * Output: maps (N,T,36,18,C) fp32, C = 30 or 32: frame f sets channel f of pixel (ti, pi) to 1, every other element -
+ * channels 30, 31 included - is written 0 (no memset needed).  Slab (n, t) starts at maps + n*maps_seq_stride +
+ * t*maps_step_stride (floats, multiples of 4; base 16-byte aligned): batch-major or time-major from one launch.  maps may be
+ * NULL when theta_out / phi_out ((N,T,30) int32, both or neither) are given: indices only.
+ * status: a device int the caller zeroes once.  A NaN / infinite coordinate or an index outside [0,36) x [0,18) ORs a bit
+ * into it (that frame's channel stays all zero, its index outputs are -1); fov_onehot_status synchronises `stream`,
+ * returns FOV_ERR_INVALID if the word is set (and clears it), else FOV_OK. */
+int fov_onehot_maps(const float* xyz, int64_t xyz_seq_stride, int64_t xyz_step_stride, const int* theta_index,
+                    const int* phi_index, float* maps, int64_t maps_seq_stride, int64_t maps_step_stride, int channels,
+                    int* theta_out, int* phi_out, int* status, int N, int T, fov_stream_t stream);
+int fov_onehot_status(int* status, fov_stream_t stream);
+
 /* Zero-fills a freshly allocated workspace (asynchronously on `stream`): required once before its first use by
  * a persistent-kernel entry point, and again whenever the buffer is re-allocated. */
 int fov_workspace_init(void* workspace, size_t workspace_bytes, fov_stream_t stream);

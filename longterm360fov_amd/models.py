@@ -1377,7 +1377,8 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out), np.float32)
 
     def predict_device(self, xe, dec0, predict_step=None):
-        """predict on device-resident inputs: xe (B,T_in,H,W,C), dec0 (B,1,H,W,C) float32 tensors on self.device -> the
+        """predict on device-resident inputs: xe (B,T_in,H,W,C), dec0 (B,1,H,W,C) float32 tensors on self.device (C may already
+        carry the zero channels up to a multiple of 4, as ops.one_hot_maps(channels=32) writes them) -> the
         prediction as a device tensor (B,T_out,H,W,C_out) / (B,T_out,6); no host transfer (what bench.py times)."""
         import torch
         from . import ops
@@ -1399,7 +1400,12 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         inp = dec0[:, 0]
         B, T_in, H, W, C_in = xe.shape
         pad = (-C_in) % 4
-        if pad:       # channel-pad the input maps once: 30 -> 32 keeps every pixel 16-byte aligned
+        C_model = dw["enc0_K"].shape[2]
+        if C_in == C_model + (-C_model) % 4 and C_in != C_model:
+            # maps that arrive padded already (ops.one_hot_maps(channels=32)); the feedback below writes into inp
+            C_in, pad = C_model, C_in - C_model
+            inp = inp.clone()
+        elif pad:     # channel-pad the input maps once: 30 -> 32 keeps every pixel 16-byte aligned
             xe = torch.cat([xe, torch.zeros((B, T_in, H, W, pad), dtype=torch.float32, device=self.device)], -1)
             inp = torch.cat([inp, torch.zeros(inp.shape[:-1] + (pad,), dtype=torch.float32, device=self.device)], -1)
         # encoder: layer l runs over the whole sequence of layer l-1 (return_sequences=True)
@@ -1450,3 +1456,83 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         return out
 
     predict_on_batch = predict
+
+    # ---- trajectory entry points: the one-hot maps are built on the device from the frame centres ----
+    def _check_onehot_model(self):
+        if self.head != "conv2d" or self._w["enc0_K"].shape[2] != 30:
+            raise ValueError("trajectory inputs need the one-hot heat-map model (head 'conv2d', 30 input channels)")
+
+    def _xyz_on_device(self, a):
+        import torch
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=torch.float32)
+        return torch.from_numpy(_as_f32(a)).to(self.device)
+
+    def _trajectory_maps(self, enc_xyz, dec_xyz, target_xyz):
+        """(enc, dec0, target) maps for ConvLSTMTrainer.  30 channels: the trainer's first-layer kernels take the model's own
+        channel count.  enc and target are written time-major and handed over as (N, T, ...) views, so the trainer's
+        permute(1, 0).contiguous() / transpose(0, 1).contiguous() of them copies nothing."""
+        from . import ops
+        enc = ops.one_hot_maps(self._xyz_on_device(enc_xyz), time_major=True).transpose(0, 1)
+        dec = ops.one_hot_maps(self._xyz_on_device(dec_xyz))
+        tgt = ops.one_hot_maps(self._xyz_on_device(target_xyz), time_major=True).transpose(0, 1)
+        return enc, dec, tgt
+
+    def predict_trajectories(self, enc_xyz, dec_xyz, batch_size=None, predict_step=None):
+        """predict([one-hot encoder maps, one-hot decoder seed]) from frame centres (convlstm_seq2seq.py:356-374 feeds the
+        maps of utility._create_one_hot): enc_xyz (N, T_in, 30, 3) or (N, T_in, 1, 30, 3), dec_xyz (N, 1, 30, 3) - the second
+        whose map is one_hot_future_input[:, 0] - as NumPy arrays or device tensors.  Only xyz crosses PCIe; the 32-channel
+        maps predict_device runs on are written on the device.  -> NumPy (N, T_out, 36, 18, 30), what predict returns for the
+        host-built maps."""
+        from . import ops
+        self._check_onehot_model()
+        T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        enc, dec = self._xyz_on_device(enc_xyz), self._xyz_on_device(dec_xyz)
+        n = enc.shape[0]
+        bs = n if not batch_size else int(batch_size)
+        outs = []
+        for lo in range(0, n, max(bs, 1)):
+            xe = ops.one_hot_maps(enc[lo:lo + bs], channels=32)
+            d0 = ops.one_hot_maps(dec[lo:lo + bs], channels=32)
+            outs.append(self.predict_device(xe, d0, T_out).cpu().numpy())
+        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out), np.float32)
+
+    def train_on_trajectories(self, enc_xyz, dec_xyz, target_xyz):
+        """train_on_batch([enc maps, dec maps], target maps) with the three one-hot map sets built on the device from frame
+        centres ((N, T, 30, 3) each; dec_xyz one second).  Returns the loss as train_on_batch does."""
+        self._check_onehot_model()
+        tr = self._get_trainer()
+        loss = tr.train_step(*self._trajectory_maps(enc_xyz, dec_xyz, target_xyz))
+        value = float(loss.item())
+        tr.check()
+        self._w = tr.weights_numpy()
+        self._dw = None
+        return value
+
+    def fit_trajectories(self, enc_xyz, dec_xyz, target_xyz, batch_size=32, epochs=1, validation_split=0.0, shuffle=True,
+                         callbacks=None, initial_epoch=0, verbose=0, validation_data=None):
+        """fit on frame centres (the Keras fit semantics of _keras_fit): the training set stays on the device as xyz, 12
+        bytes a frame instead of 2,592 of map, and each batch's maps are built right before its step.  validation_data:
+        ([enc_xyz, dec_xyz], target_xyz)."""
+        if self.optimizer is None:
+            raise RuntimeError("call compile() before fit_trajectories()")
+        self._check_onehot_model()
+        return _keras_fit(self, _TrajectoryTrainer(self, self._get_trainer()), [enc_xyz, dec_xyz], target_xyz, batch_size,
+                          epochs, validation_split, shuffle, callbacks, initial_epoch, validation_data)
+
+
+
+class _TrajectoryTrainer:
+    """ConvLSTMSeq2Seq's trainer fed with frame centres: the fit loop hands it xyz batches, it builds their maps and steps."""
+
+    def __init__(self, model, trainer):
+        self._model, self._tr = model, trainer
+
+    def __getattr__(self, name):
+        return getattr(self._tr, name)
+
+    def train_step(self, enc_xyz, dec_xyz, target_xyz, n_global=None):
+        return self._tr.train_step(*self._model._trajectory_maps(enc_xyz, dec_xyz, target_xyz), n_global=n_global)
+
+    def eval_loss(self, enc_xyz, dec_xyz, target_xyz):
+        return self._tr.eval_loss(*self._model._trajectory_maps(enc_xyz, dec_xyz, target_xyz))

@@ -1269,3 +1269,84 @@ def window_stacks(x, T, stride, collapse_user=True):
     outs = [torch.empty(shape, dtype=torch.float32, device=x.device) for _ in range(3)]
     check(L.fov_window_stacks(_ptr(x), *[_ptr(o) for o in outs], U, S, feat, T, stride, 1 if collapse_user else 0, _stream()))
     return tuple(outs)
+
+
+ONEHOT_BIN_SIZE = 10    # the only bin size: it fixes the ConvLSTM model's 36 x 18 map geometry
+
+
+def _onehot_check_bin(bin_size):
+    if bin_size != ONEHOT_BIN_SIZE:
+        raise ValueError("bin_size must be %d (the 36 x 18 map geometry), got %r" % (ONEHOT_BIN_SIZE, bin_size))
+
+
+def _onehot_launch(src, maps, seq_stride, step_stride, channels, idx_out):
+    """One fov_onehot_maps launch plus the status check: a NaN / infinite coordinate or an out-of-range index raises
+    ValueError (the call synchronises the stream to read the status word)."""
+    status = torch.zeros(1, dtype=torch.int32, device=maps.device if maps is not None else idx_out[0].device)
+    L = _lib.lib()
+    if isinstance(src, torch.Tensor):
+        xyz = src
+        if xyz.dim() == 5:          # (N, T, 1, 30, 3): reshape2second_stacks' form of one user
+            if xyz.shape[2] != 1:
+                raise ValueError("xyz of shape %s: expected (N, T, 30, 3) or (N, T, 1, 30, 3)" % (tuple(xyz.shape),))
+            xyz = xyz[:, :, 0]
+        if not (xyz.is_cuda and xyz.dtype == torch.float32 and xyz.dim() == 4 and tuple(xyz.shape[2:]) == (30, 3)):
+            raise TypeError("xyz must be a float32 (N, T, 30, 3) or (N, T, 1, 30, 3) tensor on the GPU")
+        if xyz.stride(3) != 1 or xyz.stride(2) != 3:
+            raise TypeError("xyz: each second's 30 frames of x, y, z must be contiguous")
+        N, T = xyz.shape[:2]
+        args = (xyz.data_ptr(), xyz.stride(0), xyz.stride(1), None, None)
+    else:
+        ti, pi = src
+        for t, name in ((ti, "theta_index"), (pi, "phi_index")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and
+                    t.dim() == 3 and t.shape[2] == 30):
+                raise TypeError("%s must be a contiguous int32 (N, T, 30) tensor on the GPU" % name)
+        if ti.shape != pi.shape:
+            raise ValueError("theta_index and phi_index differ in shape")
+        N, T = ti.shape[:2]
+        args = (None, 0, 0, ti.data_ptr(), pi.data_ptr())
+    t_out, p_out = idx_out if idx_out is not None else (None, None)
+    check(L.fov_onehot_maps(*args, _ptr(maps), seq_stride, step_stride, channels, _ptr(t_out), _ptr(p_out), status.data_ptr(),
+                            N, T, _stream()))
+    code = L.fov_onehot_status(status.data_ptr(), _stream())
+    if code == _lib.ERR_INVALID:
+        raise ValueError(L.fov_last_error().decode("utf-8", "replace"))
+    check(code)
+    return N, T
+
+
+def theta_phi_index(xyz, bin_size=10):
+    """10-degree (theta, phi) bin indices of every frame centre (mycode/utility.py:522-544 through dataIO.xyz2thetaphi,
+    computed in fp64).  xyz: float32 (N, T, 30, 3) or (N, T, 1, 30, 3) on the GPU -> int32 (N, T, 30) pair.
+    ValueError on a NaN / infinite coordinate."""
+    _onehot_check_bin(bin_size)
+    shape = (xyz.shape[0], xyz.shape[1], 30)
+    out = (torch.empty(shape, dtype=torch.int32, device=xyz.device), torch.empty(shape, dtype=torch.int32, device=xyz.device))
+    _onehot_launch(xyz, None, 0, 0, 30, out)
+    return out
+
+
+def one_hot_maps(src, channels=30, out=None, time_major=False, bin_size=10):
+    """One-hot heat maps in the ConvLSTM model's channels-last layout (mycode/utility.py:557-571 transposed as
+    convlstm_seq2seq.py:356-374 does).  src: an xyz tensor (see theta_phi_index) or a (theta_index, phi_index) pair of
+    int32 (N, T, 30) tensors.  -> float32 (N, T, 36, 18, channels), or (T, N, 36, 18, channels) with time_major.
+    channels 32 appends two zero channels (16-byte pixels, what ConvLSTMSeq2Seq.predict_device runs on).  `out`: a
+    contiguous float32 tensor of that shape to write into.  ValueError on a NaN / infinite coordinate or an index outside
+    [0, 36) x [0, 18)."""
+    _onehot_check_bin(bin_size)
+    if channels not in (30, 32):
+        raise ValueError("channels must be 30 or 32")
+    lead = src.shape[:2] if isinstance(src, torch.Tensor) else src[0].shape[:2]
+    N, T = int(lead[0]), int(lead[1])
+    shape = ((T, N) if time_major else (N, T)) + (36, 18, channels)
+    dev = src.device if isinstance(src, torch.Tensor) else src[0].device
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape:
+        raise ValueError("out has shape %s, expected %s" % (tuple(out.shape), shape))
+    out = _dev(out, "out")
+    slab = 36 * 18 * channels
+    seq_stride, step_stride = (slab, N * slab) if time_major else (T * slab, slab)
+    _onehot_launch(src, out, seq_stride, step_stride, channels, None)
+    return out

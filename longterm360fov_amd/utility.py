@@ -10,6 +10,9 @@ reference's functions):
     slice_layer              mycode/utility.py:246-261
     reshape_others_data      mycode/given_others_gt_mean_var_seq2seq.py:318-323
     generator_train2         mycode/data_generator_including_saliency.py:114-182
+    theta_phi_index_for_onehot / create_one_hot
+                             mycode/utility.py:522-571 (the ConvLSTM heat-map inputs; pinned by tests/golden/onehot.npz;
+                             ops.theta_phi_index / ops.one_hot_maps build the same on the device)
 """
 import numpy as np
 
@@ -156,6 +159,43 @@ def reshape_others_data(video_db_oth):
     """(U-1, N, T, 90) -> (N, T, U-1, 30, 3), the layout of the model's `others` input."""
     a = video_db_oth.transpose((1, 2, 0, 3))
     return a.reshape(a.shape[0], a.shape[1], a.shape[2], cfg.fps, 3)
+
+
+def theta_phi_index_for_onehot(video_db, bin_size=10):
+    """(theta_index, phi_index) of every frame centre, float64 (N, T, 30), as _save_theta_phi_index
+    (mycode/utility.py:522-544) computes them without its pickle side effect.  video_db: (N, T, 30, 3) or (N, T, 1, 30, 3).
+    The conversion is dataIO.xyz2thetaphi (mycode/dataIO.py:77-82), evaluated in float64 whatever the input dtype (the
+    reference's windows are float64 already)."""
+    v = np.asarray(video_db)
+    v = v[:, :, 0] if v.ndim == 5 else v
+    x, y, z = (v[..., a].astype(np.float64) for a in range(3))
+    theta = np.mod(np.arctan2(y, x), 2 * np.pi) - np.pi
+    phi = np.mod(np.arctan2(z, np.sqrt(x ** 2 + y ** 2)) + np.pi / 2, np.pi)
+    theta_index = np.floor((theta + np.pi) / np.pi * 180 / bin_size)
+    theta_index[theta_index == 360 // bin_size] -= 1
+    phi_index = np.floor(phi / np.pi * 180 / bin_size)
+    phi_index[phi_index == 180 // bin_size] -= 1
+    return theta_index, phi_index
+
+
+def create_one_hot(theta_index, phi_index, bin_size=10, vector=False):
+    """_create_one_hot (mycode/utility.py:557-571) without its triple loop: (N, T, F) indices -> float64 zero/one maps
+    (N, T, F, 360/bin_size, 180/bin_size), indexed [theta, phi]; vector=True flattens each map.  Indices go through int()
+    as in the reference; a NaN / infinite index (the reference's int() raises) or one outside the map (which NumPy's negative
+    indexing would silently wrap) raises ValueError."""
+    ti, pi = np.asarray(theta_index), np.asarray(phi_index)
+    H, W = 360 // bin_size, 180 // bin_size
+    if not (np.isfinite(ti).all() and np.isfinite(pi).all()):
+        raise ValueError("create_one_hot: NaN or infinite index")
+    ti, pi = np.trunc(ti).astype(np.int64), np.trunc(pi).astype(np.int64)
+    if ((ti < 0) | (ti >= H) | (pi < 0) | (pi >= W)).any():
+        raise ValueError("create_one_hot: index outside [0, %d) x [0, %d)" % (H, W))
+    one_hot = np.zeros(ti.shape + (H, W))
+    n, t, f = np.indices(ti.shape)
+    one_hot[n, t, f, ti, pi] = 1
+    if vector:
+        one_hot = one_hot.reshape(ti.shape + (-1,))
+    return one_hot
 
 
 def get_shuffle_index(data_length, rng=None):
