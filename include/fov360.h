@@ -758,7 +758,7 @@ int fov_check_status(void* workspace, size_t workspace_bytes, fov_stream_t strea
  * (write-through) granule exchange even where its run-time handshake finds a whole group on one XCD.  Results are
  * bit-identical either way (tests/test_gpu_parity.py, tests/test_gpu_train.py); fov_exchange_mode tells which ran. */
 int fov_workspace_force_safe(void* workspace, size_t workspace_bytes, int on, fov_stream_t stream);
-/* The library reads its environment knobs (FOV_FORCE_SAFE_EXCHANGE, FOV_PAIR, FOV_TWO_LAUNCHES, FOV_DBG_RESIDENT_LIMIT)
+/* The library reads its environment knobs (FOV_FORCE_SAFE_EXCHANGE, FOV_TWO_LAUNCHES, FOV_DBG_RESIDENT_LIMIT)
  * once, at first use; call this after changing them.  No launch path calls getenv. */
 void fov_reload_env(void);
 /* Diagnostic: launches of the generic (VALU, any-shape) LSTM kernel so far in this process - lets a test assert that a

@@ -473,29 +473,21 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8n_bf16_kernel(Bwd8Params p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) dzp[g] = pack_bf16(dzv[g][0], dzv[g][1]);
             B8_STAMP_AFTER(2, "+v"(dzp[0]), "+v"(dzp[1]), "+v"(dzp[2]), "+v"(dzp[3]), "+v"(dc[0]), "+v"(dc[1]));
-#ifndef FOV_DBG_B8_NOPUB
             q_dz_publish2(rs, par, prow, unit0, dzp, epoch, sDZ, ticket.same_xcd);
-#endif
             // Everything that does not depend on the partners goes between the publish and the gather: an sc1 store
             // takes about a microsecond to become visible, a sweep issued earlier comes back stale and costs a second
             // round trip.  The tape of step t-1 is requested here, a whole step before its use.
             B8_STAMP(3);
-#ifndef FOV_DBG_B8_NOTAPE     // timing experiments (wrong results): tools/b8_variants.sh
             load_step(t - 1, pre);
-#endif
 #pragma unroll
             for (int g = 0; g < 4; ++g) dbacc[g] += dzv[g];
-#ifndef FOV_DBG_B8_NODZ
             if (live) {
                 float* zp = p.dz + ((size_t)row * T + t) * H4 + unit0;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) *(f32x2*)(zp + g * QH) = dzv[g];
             }
-#endif
             B8_STAMP(4);
-#ifndef FOV_DBG_B8_NOGATHER
             if (!q_dz_gather2(rs, par, slice, tid, epoch, sDZ, p.status)) sFlag[0] = 1;
-#endif
             B8_STAMP(5);
             __syncthreads();   // barrier A: the whole dz tile is in LDS
             B8_STAMP(6);

@@ -321,11 +321,8 @@ __device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* a
 }
 template <bool FIRST, bool LAST>
 __device__ __forceinline__ void input_proj_any(f32x4 (&acc)[4], const float* arow, const float* sKw, int nq, int lane) {
-#ifndef FOV_DBG_NO_XK_UNROLL
     if (nq == 6) input_proj_fixed<6, FIRST, LAST>(acc, arow, sKw, lane);   // F in (80, 96]: the reference's 90-wide input (FoV_seq2seq.py:24-26)
-    else
-#endif
-        input_proj<FIRST, LAST>(acc, arow, sKw, nq, lane);
+    else input_proj<FIRST, LAST>(acc, arow, sKw, nq, lane);
 }
 
 // DECODE: acc += y(16 x 8) . Kslice, y fragment and the two K blocks already in registers (y is VALU-written: the run

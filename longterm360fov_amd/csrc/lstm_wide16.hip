@@ -376,9 +376,6 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
             const unsigned want = ticket.base + 1u + (unsigned)s_;
             unsigned spins = 0;
             while (__any(zq[0].y != want || zq[0].w != want || zq[1].y != want || zq[1].w != want)) {
-#ifdef FOV_DBG_W16_NOZWAIT   // timing experiment (tools/w16_variants.sh): WRONG results
-                break;
-#endif
                 ++spins;
                 if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
                     if (lane == 0) {
@@ -556,13 +553,7 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
                 }
             }
             if (do_xch) gather_issue(par);
-#if defined(FOV_DBG_W16_NOL2GATHER)   // timing experiments (tools/w16_variants.sh): WRONG results
-            if (do_xch && ROLE != 4) gather_finish(par);
-#elif defined(FOV_DBG_W16_NOL1GATHER)
-            if (do_xch && ROLE != 1) gather_finish(par);
-#else
             if (do_xch) gather_finish(par);
-#endif
             __syncthreads();   // barrier 2: the whole h_t tile is in LDS
             if (sFlag[0]) { aborted = true; break; }
             if constexpr (ROLE == 2) {
@@ -659,9 +650,6 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
             }
         }
         unsigned spins = 0;
-#ifdef FOV_DBG_W16_NOPRODGATHER   // timing experiment: WRONG results
-        bad = 0;
-#endif
         while (__any(bad != 0)) {
             ++spins;
             if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
@@ -676,7 +664,7 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
             // ONE 16-byte probe per lane and sweep while layer 1 is not that far (its last piece: the pieces of a step appear
             // within a fraction of a microsecond of each other); the 16 loads of the full sweep only behind a current probe.
             // Sweeping all of them polled 64 KB per workgroup and iteration through the fabric the layers exchange over:
-            // 0.7 us per step of the whole launch (tools/w16_variants.sh, NOPRODGATHER).
+            // 0.7 us per step of the whole launch (profiles/r04_w16_variants.txt, NOPRODGATHER).
             {
                 const vu32x4 pv = __builtin_amdgcn_raw_buffer_load_b128(ringrs, vo + (NRG - 1) * 32 * 8, (unsigned)s_ * PARITY, 16);
                 if (!__any(pv.y == want && pv.w == want)) continue;
@@ -704,11 +692,9 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
         if (sFlag[0]) { aborted = true; break; }
         if (t + 1 < steps) ring_issue(t + 1);
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#ifndef FOV_DBG_W16_NOPRODMM   // timing experiment (tools/w16_variants.sh): WRONG results without
         vm_begin(acc);
         wide16_mm<NJX>(acc, sX + (t & 1) * VBT * WLD + n * WLD + 4 * g4, wk);
         vm_end(acc);
-#endif
         const f32x4 z = acc[0] + acc[1];
         const unsigned tag = ticket.base + 1u + (unsigned)t;
         const unsigned so = (unsigned)t * (unsigned)(W16_MAIL * 8u);
@@ -722,7 +708,7 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
 // member b / 8 of "XCD group" b % 8 (round-robin dispatch: one XCD, verified by the layers' hello handshakes): XCD groups
 // [0, tiles) are layer 1's tiles, [tiles, 2 tiles) the product role's, [2 tiles, 3 tiles) layer 2's - every 32-workgroup group
 // has an XCD (32 CUs) of its own and the layers exchange through its L2 (sc0 stores, xch_common.h), 4.2 us per step against
-// 5.7 with a group's members dealt over all XCDs (tools/w16_variants.sh); what crosses XCDs - layer 1's h_t to the product
+// 5.7 with a group's members dealt over all XCDs (HISTORY.md, round 4); what crosses XCDs - layer 1's h_t to the product
 // role (the mirror ring), z_t to layer 2 (the mailboxes) - is written with sc1 stores.  Spare blocks count as arrived and leave.
 template <int ACT, int WH>
 __global__ __launch_bounds__(256, 1) void lstm_wide16_trio_kernel(Wide16Pair pp) {

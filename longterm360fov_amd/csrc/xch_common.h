@@ -204,13 +204,8 @@ __device__ __forceinline__ XchTicket xch_ticket(const unsigned* lds2, unsigned a
     // epoch-derived scalar offset of a buffer load / store (the parity buffer) then becomes a waterfall loop around EVERY
     // granule access (v_readfirstlane + v_cmp + s_and_saveexec + branch, 16 of them per step of lstm_cluster)
     XchTicket t;
-#ifdef FOV_DBG_OLD_TICKET
-    t.base = lds2[0];
-    t.launch = lds2[1];
-#else
     t.base = (unsigned)__builtin_amdgcn_readfirstlane((int)lds2[0]);
     t.launch = (unsigned)__builtin_amdgcn_readfirstlane((int)lds2[1]);
-#endif
     t.arrival = arrival;
     t.same_xcd = __builtin_amdgcn_readfirstlane((int)lds2[2]) != 0 && __builtin_amdgcn_readfirstlane((int)lds2[3]) == 0;
     return t;
