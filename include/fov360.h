@@ -22,6 +22,9 @@
  *     serves one stream at a time; different entry points may share it.  The header's timeout word is
  *     sticky: once a bounded in-kernel wait has given up, every later call on that workspace returns
  *     without computing until fov_check_status has reported (and cleared) the failure.
+ *   - Weight gradients over an empty batch or sequence (B = 0, T = 0, no rows): accumulate = 0 writes zeros
+ *     (the gradient of an empty sum), accumulate != 0 leaves the output unchanged.  Every weight-gradient entry
+ *     point keeps this rule (a data-parallel rank with an empty shard contributes zero, not a stale gradient).
  *   - Every function returns FOV_OK (0) or a negative FOV_ERR_*; fov_last_error() gives the
  *     message of the calling thread's last failure.  No host synchronisation inside a call
  *     (except fov_check_status, which is the explicit "did the persistent kernel finish
@@ -594,7 +597,11 @@ int fov_rmsprop_step_guarded(float* params, const float* grads, float* accum, in
  * device memory, any size >= 256 bytes: what does not fit is reduced at once) and the flush sums all of them in ONE launch
  * instead of one per product; results are bit-identical.  In-stream order is kept for writes made through this library (a
  * later product over a pending range flushes first); a caller that reads or writes the gradient buffer by other means
- * between _begin and _end calls _flush before.
+ * between _begin and _end calls _flush before.  Writers covered: fov_lstm_seq_bwd(_bf16), fov_lstm_seq_wgrad,
+ * fov_lstm_seq_wgrad_pair, fov_lstm_stack2_bwd, fov_dense_bwd(_bf16), fov_wgrad_fused, fov_colsum, fov_mix_head_wgrad,
+ * fov_mse_dense_grad_db / _w (db), fov_dense_mse_head, fov_mlp_head_bwd, fov_tf_head_bwd, fov_conv2d_wgrad,
+ * fov_conv2d_dilated_wgrad, in every kernel form and in their empty-shape zeroing; readers covered (they
+ * flush over the gradients they read): fov_adam_step(_guarded), fov_rmsprop_step(_guarded), fov_rmsprop_tf_step(_guarded).
  * A region is KEYED BY ITS GRADIENT BUFFER: each caller (trainer, thread, stream, device) opens its own with _begin and names
  * it again by grad_base (any address inside the buffer) in _flush / _end; regions of different buffers share nothing - their
  * arenas and pending records are separate - so several may be open at once from different threads (at most 16 per process;

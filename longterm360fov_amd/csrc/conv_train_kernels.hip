@@ -312,10 +312,7 @@ int conv2d_wgrad(const float* x, long ldx, const float* dz, float* dw, int B, in
                  int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream, int dil) {
     const long P = (long)B * H * W;
     const size_t wn = (size_t)kh * kw * C * N;
-    if (P == 0) {
-        if (!accumulate) (void)hipMemsetAsync(dw, 0, sizeof(float) * wn, stream);
-        return FOV_OK;
-    }
+    if (P == 0) return accumulate ? FOV_OK : zero_grad(dw, wn, stream);
     if ((long)16 * ldx * 4 >= (1L << 30) || (long)16 * N * 4 >= (1L << 30)) { set_error("conv2d_wgrad: strides out of range"); return FOV_ERR_UNSUPPORTED; }
     // narrow layers: every tap in one workgroup, operands read once (conv_wgrad_lines.hip)
     if (conv_wgrad_lines_takes(H, W, C, N, kh, kw, dil < 1 ? 1 : dil))
@@ -354,6 +351,8 @@ int conv2d_wgrad(const float* x, long ldx, const float* dz, float* dw, int B, in
     const bool via_scratch = split > 1 || accumulate;
     if (via_scratch && (size_t)split * wn > scratch_floats) { set_error("conv2d_wgrad: scratch too small"); return FOV_ERR_WORKSPACE; }
     g.out = via_scratch ? scratch : dw;
+    if (!via_scratch)       // the direct form stores into dw: pending deferred reductions over it go first
+        if (int rc = defer_touch(dw, wn, stream)) return rc;
     g.split = split;
     g.tiles_per_split = tps;
     const bool avec = (C & 3) == 0 && (ldx & 3) == 0 && (((uintptr_t)x) & 15) == 0;

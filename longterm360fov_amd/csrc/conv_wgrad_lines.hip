@@ -258,6 +258,8 @@ int conv_wgrad_lines(const float* x, long ldx, const float* dz, float* dw, int B
     const bool via_scratch = split > 1 || accumulate;
     if (via_scratch && (size_t)split * wn > scratch_floats) { set_error("conv_wgrad_lines: scratch too small"); return FOV_ERR_WORKSPACE; }
     g.out = via_scratch ? scratch : dw;
+    if (!via_scratch)       // the direct form stores into dw: pending deferred reductions over it go first
+        if (int rc = defer_touch(dw, wn, stream)) return rc;
     // 16-byte staging loads: x when the pixel stride holds whole pieces, dz when N is a multiple of 4
     g.avec = (ldx & 3) == 0 && (((uintptr_t)x) & 15) == 0 && ((C + 3) & ~3) <= ldx;
     g.bvec = (N & 3) == 0 && (((uintptr_t)dz) & 15) == 0;

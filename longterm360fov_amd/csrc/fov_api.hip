@@ -728,7 +728,7 @@ int fov_lstm_seq_bwd(const float* x, const float* K, const float* R, const float
         set_error("fov_lstm_seq_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
-    if (B == 0) return FOV_OK;
+    if (B == 0) return accumulate ? FOV_OK : zero_lstm_wgrads(dK, dR, db, F, H, (hipStream_t)stream);
     int rc = check_ws(workspace, workspace_bytes, fov_lstm_seq_bwd_workspace_bytes(B, T, F, H));
     if (rc) return rc;
     return lstm_seq_bwd(x, K, R, h0, c0, hs, reserve, dhs, dhT, dcT, dz, dx, dK, dR, db, dh0, dc0, B, T, F, H, act,
@@ -746,7 +746,7 @@ int fov_lstm_seq_bwd_bf16(const float* x, const float* K, const float* R, const 
         set_error("fov_lstm_seq_bwd_bf16: invalid argument (H = 256 only)");
         return FOV_ERR_INVALID;
     }
-    if (B == 0) return FOV_OK;
+    if (B == 0) return accumulate ? FOV_OK : zero_lstm_wgrads(dK, dR, db, F, H, (hipStream_t)stream);
     int rc = check_ws(workspace, workspace_bytes, fov_lstm_seq_bwd_workspace_bytes(B, T, F, H));
     if (rc) return rc;
     return lstm_seq_bwd(x, K, R, h0, c0, hs, reserve, dhs, dhT, dcT, dz, dx, dK, dR, db, dh0, dc0, B, T, F, H, act,
@@ -772,7 +772,21 @@ int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const 
         set_error("fov_lstm_stack2_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
-    if (B == 0 || T == 0) return FOV_OK;
+    if (B == 0 || T == 0) {
+        hipStream_t s = (hipStream_t)stream;
+        int rc = accumulate ? FOV_OK : zero_lstm_wgrads(dK1, dR1, db1, F, H, s);
+        if (!rc && !accumulate) rc = zero_lstm_wgrads(dK2, dR2, db2, H, H, s);
+        // no steps: the state gradients pass through (as fov_lstm_seq_bwd at T = 0; the lower layer gets no dx from the upper one)
+        const size_t bh = sizeof(float) * (size_t)B * H;
+        const float* src[4] = {dhT2, dcT2, dhT1, dcT1};
+        float* dst[4] = {dh0_2, dc0_2, dh0_1, dc0_1};
+        for (int i = 0; i < 4 && !rc && bh; ++i) {
+            if (!dst[i]) continue;
+            hipError_t e = src[i] ? hipMemcpyAsync(dst[i], src[i], bh, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(dst[i], 0, bh, s);
+            if (e != hipSuccess) { set_error("fov_lstm_stack2_bwd: %s", hipGetErrorString(e)); rc = FOV_ERR_LAUNCH; }
+        }
+        return rc;
+    }
     if (!bwd16_pair_shape(B, T, H)) {
         set_error("fov_lstm_stack2_bwd: H = 512, at most 32 sequences, three role-groups of sixteen workgroups per tile resident only");
         return FOV_ERR_UNSUPPORTED;
@@ -1640,8 +1654,7 @@ int fov_colsum(const float* x, float* out, int64_t rows, int cols, int accumulat
     int rc = check_ws(workspace, workspace_bytes, sizeof(float) * ((size_t)256 * cols + 64));
     if (rc) return rc;
     if (rows == 0) {
-        if (!accumulate) (void)hipMemsetAsync(out, 0, sizeof(float) * cols, (hipStream_t)stream);
-        return FOV_OK;
+        return accumulate ? FOV_OK : zero_grad(out, (size_t)cols, (hipStream_t)stream);
     }
     return colsum(x, out, (long)rows, cols, accumulate, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }

@@ -159,6 +159,8 @@ int defer_begin(float* grad_base, size_t grad_floats, float* arena, size_t arena
 int defer_flush(const float* grad_base, hipStream_t stream);
 int defer_end(const float* grad_base, hipStream_t stream);
 int defer_touch(const float* out, size_t n, hipStream_t stream);
+int zero_grad(float* g, size_t n, hipStream_t stream);
+int zero_lstm_wgrads(float* dK, float* dR, float* db, int F, int H, hipStream_t stream);
 float* defer_alloc(const float* out, size_t n, size_t floats, hipStream_t stream);
 void defer_record(const float* part, float* out, long n, int S, int accumulate);
 int reduce_or_defer(bool deferred, const float* part, float* out, long n, int S, int accumulate, hipStream_t stream, const char* what);

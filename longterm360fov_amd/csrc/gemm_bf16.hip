@@ -554,8 +554,7 @@ int gemm_bf16_tn_fused(const float* a1, long lda1, long a1_so, int M1, int shift
         }
     }
     if (rows <= 0) {
-        if (!accumulate) (void)hipMemsetAsync(c, 0, sizeof(float) * (size_t)(M + bias_row) * ldc, stream);
-        return FOV_OK;
+        return accumulate ? FOV_OK : zero_grad(c, (size_t)(M + bias_row) * ldc, stream);
     }
     GemmTN g = {};
     g.a = a1; g.b = b; g.M = M; g.N = N; g.RO = RO; g.RI = RI; g.lda = lda1; g.ldb = ldb; g.a_so = a1_so; g.b_so = b_so; g.ldc = ldc;

@@ -789,7 +789,17 @@ size_t fov_mlp_head_bwd_workspace_bytes(int B, int L, const int* dims) {
 int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* masks, const float* const* acts, const float* dlast,
                      float* const* gW, float* const* gb, float* dx, const int* dims, const int* act_codes, int L, int B,
                      int accumulate, void* workspace, size_t workspace_bytes, fov_stream_t stream) {
-    if (B == 0) return FOV_OK;
+    if (B == 0) {       // the gradient of an empty sum: zero (accumulate = 0), unchanged (accumulate != 0)
+        if (accumulate) return FOV_OK;
+        if (!gW || !gb || !mlp_dims_ok(1, L, dims)) { set_error("fov_mlp_head_bwd: invalid argument"); return FOV_ERR_INVALID; }
+        for (int l = 0; l < L; ++l) {
+            if (!gW[l] || !gb[l]) { set_error("fov_mlp_head_bwd: null layer pointer"); return FOV_ERR_INVALID; }
+            int rc = zero_grad(gW[l], (size_t)dims[l] * dims[l + 1], (hipStream_t)stream);
+            if (!rc) rc = zero_grad(gb[l], (size_t)dims[l + 1], (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        return FOV_OK;
+    }
     if (!x || !W || !acts || !dlast || !gW || !gb || !dims || !act_codes) { set_error("fov_mlp_head_bwd: invalid argument"); return FOV_ERR_INVALID; }
     if (!mlp_dims_ok(B, L, dims)) { set_error("fov_mlp_head_bwd: unsupported shape"); return FOV_ERR_UNSUPPORTED; }
     if (!workspace || workspace_bytes < fov_mlp_head_bwd_workspace_bytes(B, L, dims)) { set_error("fov_mlp_head_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
@@ -814,6 +824,11 @@ int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* 
     int blk[MH_MAXL + 1] = {0, 0, 0, 0, 0};
     for (int l = 0; l < L; ++l) blk[l + 1] = blk[l] + (dims[l] + WG_IR - 1) / WG_IR;
     for (int l = L; l < MH_MAXL; ++l) blk[l + 1] = blk[L] + (1 << 28);      // unused layers: never reached
+    for (int l = 0; l < L; ++l) {       // the launch stores into gW / gb: pending deferred reductions over them go first
+        int rc = defer_touch(gW[l], (size_t)dims[l] * dims[l + 1], (hipStream_t)stream);
+        if (!rc) rc = defer_touch(gb[l], (size_t)dims[l + 1], (hipStream_t)stream);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(mlp_head_wgrad_kernel, dim3((unsigned)blk[L]), dim3(256), 0, (hipStream_t)stream, p, blk[1], blk[2], blk[3]);
     return mh_check("mlp head weight gradients");
 }

@@ -215,7 +215,17 @@ int fov_tf_head_bwd(const float* h, const float* mu_W1, const float* mu_W2, cons
                     const float* mu, const float* a3, const float* var, const float* dmu, const float* dvar, float* g_mu_W1,
                     float* g_mu_b1, float* g_mu_W2, float* g_mu_b2, float* g_var_W1, float* g_var_b1, float* g_var_W2, float* g_var_b2,
                     float* dh, int B, int H, int M, int O, int accumulate, fov_stream_t stream) {
-    if (B == 0) return FOV_OK;
+    float* const grads[8] = {g_mu_W1, g_mu_b1, g_mu_W2, g_mu_b2, g_var_W1, g_var_b1, g_var_W2, g_var_b2};
+    const size_t sizes[8] = {(size_t)H * M, (size_t)M, (size_t)M * O, (size_t)O, (size_t)H * M, (size_t)M, (size_t)M * O, (size_t)O};
+    if (B == 0) {       // the gradient of an empty sum: zero (accumulate = 0), unchanged (accumulate != 0)
+        if (accumulate) return FOV_OK;
+        if (!tf_head_shape_ok(1, H, M, O)) { set_error("fov_tf_head_bwd: unsupported shape (B <= 64, H <= 2048, M <= 32, O <= 8)"); return FOV_ERR_UNSUPPORTED; }
+        for (int i = 0; i < 8; ++i)
+            if (!grads[i]) { set_error("fov_tf_head_bwd: invalid argument"); return FOV_ERR_INVALID; }
+        for (int i = 0; i < 8; ++i)
+            if (int rc = zero_grad(grads[i], sizes[i], (hipStream_t)stream)) return rc;
+        return FOV_OK;
+    }
     if (!h || !mu_W1 || !mu_W2 || !var_W1 || !var_W2 || !a1 || !mu || !a3 || !var || !dmu || !dvar || !g_mu_W1 || !g_mu_b1 || !g_mu_W2 ||
         !g_mu_b2 || !g_var_W1 || !g_var_b1 || !g_var_W2 || !g_var_b2 || !dh) {
         set_error("fov_tf_head_bwd: invalid argument");
@@ -228,6 +238,8 @@ int fov_tf_head_bwd(const float* h, const float* mu_W1, const float* mu_W2, cons
     p.dmu = dmu; p.dvar = dvar;
     p.gW1m = g_mu_W1; p.gb1m = g_mu_b1; p.gW2m = g_mu_W2; p.gb2m = g_mu_b2; p.gW1v = g_var_W1; p.gb1v = g_var_b1; p.gW2v = g_var_W2; p.gb2v = g_var_b2;
     p.dh = dh; p.B = B; p.H = H; p.M = M; p.O = O; p.accumulate = accumulate ? 1 : 0;
+    for (int i = 0; i < 8; ++i)         // the launch stores into the eight gradients: pending deferred reductions over them go first
+        if (int rc = defer_touch(grads[i], sizes[i], (hipStream_t)stream)) return rc;
     const int blocksA = (H + 3) / 4, blocksB = ((H + 255) / 256) * ((B + 7) / 8);
     hipLaunchKernelGGL(tf_head_bwd_kernel, dim3((unsigned)(blocksA + blocksB + 1)), dim3(256), 0, (hipStream_t)stream, p, blocksA, blocksB);
     hipError_t e = hipGetLastError();

@@ -538,6 +538,14 @@ int defer_touch(const float* out, size_t n, hipStream_t stream) {
     }
     return FOV_OK;
 }
+// accumulate = 0 over an empty batch or sequence: [g, g + n) = 0, the gradient of an empty sum (after the pending records over it)
+int zero_grad(float* g, size_t n, hipStream_t stream) {
+    if (!g || n == 0) return FOV_OK;
+    if (int rc = defer_touch(g, n, stream)) return rc;
+    hipError_t e = hipMemsetAsync(g, 0, sizeof(float) * n, stream);
+    if (e != hipSuccess) { set_error("zero_grad: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    return FOV_OK;
+}
 // Where a split product with output [out, out + n) may put its `floats` of partial slices, or NULL: reduce at once.
 float* defer_alloc(const float* out, size_t n, size_t floats, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(g_defer_mu);
@@ -1317,8 +1325,7 @@ int gemm_f32(GemmArgs g, int accumulate, float* scratch, size_t scratch_floats, 
     if (g.M <= 0 || g.N <= 0) return FOV_OK;
     const long K = (long)g.KO * g.KI;
     if (K <= 0) {
-        if (!accumulate) (void)hipMemsetAsync(g.c, 0, sizeof(float) * (size_t)g.M * g.ldc, stream);
-        return FOV_OK;
+        return accumulate ? FOV_OK : zero_grad(g.c, (size_t)g.M * g.ldc, stream);
     }
     const size_t mn = (size_t)(g.M + g.bias_row) * g.N;
     // tile shape by M: short-and-wide weight-gradient products (M = F or Out) would waste a 128-row tile
@@ -1646,8 +1653,7 @@ int mix_head_wgrad(const float* h2, const float* dpre_p, const float* others, co
     const int ncol = H + 1 + n_oth + O + 1;
     const size_t n = (size_t)ncol * O;
     if (rows <= 0) {
-        if (!accumulate) (void)hipMemsetAsync(out, 0, sizeof(float) * n, stream);
-        return FOV_OK;
+        return accumulate ? FOV_OK : zero_grad(out, n, stream);
     }
     long chunks = rows / 32;
     if (chunks > 256) chunks = 256;
@@ -1919,7 +1925,8 @@ static int lstm_seq_weight_products(const float* x, const float* hs, const float
                       : gemm_f32(g, accumulate, scratch, scratch_floats, stream);
             if (rc) return rc;
         } else if (!accumulate) {
-            (void)hipMemsetAsync(dR, 0, sizeof(float) * (size_t)H * 4 * H, stream);
+            rc = zero_grad(dR, (size_t)H * 4 * H, stream);
+            if (rc) return rc;
         }
         if (h0 && T > 0) {
             GemmArgs g0 = {};
@@ -1963,17 +1970,22 @@ static void lstm_seq_wgrad_fusion(const float* x, const float* hs, const float* 
               wgrad_fusable(hs, H, (long)T * H, H, nullptr, 0, 0, 0, dz, N4, (long)T * N4, dR, N4) && !env_knobs().no_wgrad_fusion;
 }
 
+// accumulate = 0 on an empty batch or sequence: dK (F,4H), dR (H,4H), db (4H) = 0 (NULL ones are skipped)
+int zero_lstm_wgrads(float* dK, float* dR, float* db, int F, int H, hipStream_t stream) {
+    int rc = zero_grad(dK, (size_t)F * 4 * H, stream);
+    if (!rc) rc = zero_grad(dR, (size_t)H * 4 * H, stream);
+    if (!rc) rc = zero_grad(db, (size_t)4 * H, stream);
+    return rc;
+}
+
 // Weight gradients of one layer from a dz tape its BPTT left behind (fov_lstm_seq_bwd* with dK = dR = db = NULL): lets a trainer
 // put a layer's products on another stream than the next layer's recurrence.  Same arithmetic, same order as inside lstm_seq_bwd.
 int lstm_seq_wgrad(const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db, int B, int T,
                    int F, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream) {
     if (bf16 && H != 256) { set_error("lstm_seq_wgrad: the bf16 path is built for H = 256"); return FOV_ERR_UNSUPPORTED; }
     if (T == 0 || B == 0) {
-        if (!accumulate) {
-            if (dK) (void)hipMemsetAsync(dK, 0, sizeof(float) * (size_t)F * 4 * H, stream);
-            if (dR) (void)hipMemsetAsync(dR, 0, sizeof(float) * (size_t)H * 4 * H, stream);
-            if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)4 * H, stream);
-        }
+        if (!accumulate)
+            if (int rc = zero_lstm_wgrads(dK, dR, db, F, H, stream)) return rc;
         return FOV_OK;
     }
     const bool rows_form = lstm_seq_wgrad_rows(bf16, B, T, F, H, dz, dK, dR, db);
@@ -2019,11 +2031,8 @@ int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0
     if (bf16 && H != 256) { set_error("lstm_seq_bwd: the bf16 path is built for H = 256"); return FOV_ERR_UNSUPPORTED; }
     if (ws_floats < lstm_bwd_workspace_floats(B, T, F, H)) { set_error("lstm_seq_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
     if (T == 0) {
-        if (!accumulate) {
-            if (dK) (void)hipMemsetAsync(dK, 0, sizeof(float) * (size_t)F * 4 * H, stream);
-            if (dR) (void)hipMemsetAsync(dR, 0, sizeof(float) * (size_t)H * 4 * H, stream);
-            if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)4 * H, stream);
-        }
+        if (!accumulate)
+            if (int rc = zero_lstm_wgrads(dK, dR, db, F, H, stream)) return rc;
         const size_t bh0 = sizeof(float) * (size_t)B * H;
         if (dh0) (void)(dhT ? hipMemcpyAsync(dh0, dhT, bh0, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dh0, 0, bh0, stream));
         if (dc0) (void)(dcT ? hipMemcpyAsync(dc0, dcT, bh0, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dc0, 0, bh0, stream));
@@ -2276,13 +2285,14 @@ int mse_dense_grad(const float* y, const float* target, float* dpre, float* loss
 int mse_dense_grad_w(const float* y, const float* target, float* dpre, float* loss, long n, int activation, float weight,
                      int tmB, int tmT, int O, float* scratch, size_t scratch_floats, hipStream_t stream, float* db, int dbO) {
     if (n <= 0) {
-        if (db && dbO > 0) (void)hipMemsetAsync(db, 0, sizeof(float) * dbO, stream);
-        return FOV_OK;
+        return (db && dbO > 0) ? zero_grad(db, (size_t)dbO, stream) : FOV_OK;
     }
     const long blocks = (n + 255) / 256;
     if ((size_t)blocks * (db ? 9 : 1) + (db ? 4 : 0) > scratch_floats) { set_error("mse_dense_grad_w: scratch too small"); return FOV_ERR_WORKSPACE; }
     unsigned* ticket = loss ? loss_ticket_of(stream) : nullptr;
     const bool fused_db = db && ticket && dbO >= 1 && dbO <= 8 && tmT == 0 && n % dbO == 0;
+    if (fused_db)       // the kernel's last block stores db: pending deferred reductions over it go first
+        if (int rc = defer_touch(db, (size_t)dbO, stream)) return rc;
     hipLaunchKernelGGL(mse_dense_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, target, dpre, scratch, n,
                        weight / (float)n, activation, tmB, tmT, O, ticket, loss, weight / (float)n,
                        fused_db ? scratch + ((blocks + 3) & ~3L) : nullptr, fused_db ? db : nullptr, fused_db ? dbO : 0);
@@ -2367,6 +2377,7 @@ int act_bwd(const float* dy, const float* y, const float* base, float* out, long
 int adam_step(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2, float eps,
               const unsigned* const* guards, long long* applied, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
+    if (int rc = defer_touch(g, (size_t)n, stream)) return rc;      // pending deferred reductions into the gradients go first
     if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0 && n >= 1024)
         hipLaunchKernelGGL(adam_kernel4, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, p, g, m, v, n, lr_t, b1, b2, eps,
                            guards ? guards[0] : nullptr, guards ? guards[1] : nullptr, guards ? guards[2] : nullptr, applied);
@@ -2379,6 +2390,7 @@ int adam_step(float* p, const float* g, float* m, float* v, long n, float lr_t, 
 int rmsprop_step(float* p, const float* g, float* a, long n, float lr, float rho, float eps, const unsigned* const* guards,
                  long long* applied, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
+    if (int rc = defer_touch(g, (size_t)n, stream)) return rc;
     hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, a, n, lr, rho, eps,
                        guards ? guards[0] : nullptr, guards ? guards[1] : nullptr, guards ? guards[2] : nullptr, applied);
     return check_launch("rmsprop");
@@ -2444,6 +2456,7 @@ int sample_refeed_bwd(const float* dx, long ldx, const float* var, const float* 
 int rmsprop_tf_step(float* p, const float* g, float* ms, long n, float lr, float decay, float eps, float clip,
                     const unsigned* const* guards, long long* applied, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
+    if (int rc = defer_touch(g, (size_t)n, stream)) return rc;
     hipLaunchKernelGGL(rmsprop_tf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, ms, n, lr, decay, eps, clip,
                        guards ? guards[0] : nullptr, guards ? guards[1] : nullptr, guards ? guards[2] : nullptr, applied);
     return check_launch("rmsprop_tf");

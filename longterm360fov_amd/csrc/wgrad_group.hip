@@ -485,6 +485,17 @@ extern "C" int fov_debug_read_wg_stamps(unsigned long long* out) {
 }
 #endif
 
+// Both launches below store straight into the gradients: pending deferred reductions over any of them go first
+template <class Batch>
+static int touch_outputs(const Batch& g, hipStream_t stream) {
+    for (int i = 0; i < g.count; ++i) {
+        int rc = defer_touch(g.p[i].c, (size_t)g.p[i].M * g.p[i].ldc, stream);
+        if (!rc && g.p[i].bias) rc = defer_touch(g.p[i].bias, (size_t)g.p[i].N, stream);
+        if (rc) return rc;
+    }
+    return FOV_OK;
+}
+
 // rows small enough that one workgroup per output tile walking all of them beats the split products
 // ... AND tiles enough to occupy the chip: a workgroup walks all rows of its tile at ~2 400 cycles per 16 rows, so a product of a
 // dozen tiles (H = 128: 8) is faster split over the rows (measured: 36 us against 24 us for config 1's layers)
@@ -527,6 +538,8 @@ int wgrad_group_layers(int L, const float* const* x, const int* F, const float* 
         if (bias) { set_error("wgrad_group: db needs dK or dR of the same layer"); return FOV_ERR_INVALID; }
     }
     if (blocks == 0) return FOV_OK;
+    if (int rc = touch_outputs(g, stream)) return rc;
+    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] wgrad_group: %d problems, %d workgroups\n", g.count, blocks);
     hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("wgrad_group launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
@@ -578,6 +591,7 @@ int wgrad_rows_layers(int L, const float* const* x, const int* F, const int* T, 
         if (bias) { set_error("wgrad_rows: db needs dK or dR of the same layer"); return FOV_ERR_INVALID; }
     }
     if (blocks == 0) return FOV_OK;
+    if (int rc = touch_outputs(g, stream)) return rc;
     if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] wgrad_rows: %d problems, %d workgroups, M tiles %d\n", g.count, blocks, MT);
     const dim3 grid((unsigned)blocks), blk(256);
     if (MT == 2) hipLaunchKernelGGL((wgrad_rows_kernel<2, 10>), grid, blk, 0, stream, g);
