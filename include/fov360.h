@@ -269,6 +269,30 @@ int fov_wgrad_fused(const float* x1, int In1, const float* x2, int In2, const fl
 int fov_lstm_seq_fwd_bf16(const float* x, const float* K, const float* R, const float* b, const float* h0,
                           const float* c0, float* hs, float* hT, float* cT, float* reserve, int B, int T, int F, int H,
                           int act, void* workspace, size_t workspace_bytes, fov_stream_t stream);
+/* fov_seq2seq_decode_fwd with bf16 operands (BASELINE.json configs[1] shape; replaces the host loop of
+ * mycode/FoV_seq2seq.py:137-178 over encoder_model / decoder_model, batched): the encoder over T_in steps from a zero
+ * state, then T_out autoregressive decoder steps, each = LSTM step + Dense(F_dec, tanh) + feedback, in ONE persistent
+ * launch.  Every product with x or h on its left (encoder gates, decoder gates, the Dense head) rounds both operands to
+ * bf16 (round to nearest even) into the matrix core with fp32 accumulation; gates, cell state, y_t and every stored tensor
+ * stay fp32; the fed-back y_t is rounded only where it enters the next step's x . dec_K.  A decoder step equals one
+ * fov_lstm_seq_fwd_bf16 step from the fed-back state followed by fov_dense_fwd_bf16, bit for bit.
+ * Arguments as fov_seq2seq_decode_fwd without impl; shapes: H = 256, F_enc <= 256, F_dec <= 8, either activation (others:
+ * FOV_ERR_UNSUPPORTED).  B = 0: nothing is launched; T_in = 0: the decoder starts from a zero state; T_out = 0: the encoder
+ * alone, `out` is not written; hT / cT (B,H) or NULL: the final state of the last phase that ran.  Workspace: the size of
+ * fov_lstm_seq_fwd_bf16 (256 + 64 MB for B > 0), same header, sticky timeout word and fail-stop. */
+int fov_seq2seq_decode_fwd_bf16(const float* enc_in, const float* dec_in0,
+                                const float* enc_K, const float* enc_R, const float* enc_b,
+                                const float* dec_K, const float* dec_R, const float* dec_b,
+                                const float* dense_W, const float* dense_b,
+                                float* out, float* hT, float* cT,
+                                int B, int T_in, int T_out, int F_enc, int F_dec, int H,
+                                int act, void* workspace, size_t workspace_bytes, fov_stream_t stream);
+/* fov_dense_fwd with bf16 operands: y (N,Out) = act(x (N,In) . W (In,Out) + b), activation 0 = linear, 1 = tanh; b may be
+ * NULL.  The products and their summation order are those of fov_seq2seq_decode_fwd_bf16's head (hidden units summed in
+ * four 64-unit partials on the matrix core, added in order, then the bias): the teacher-forced paths use it
+ * (FoV_seq2seq.py:82-101 in bf16), so training, predict and the fused call compute one arithmetic.  In <= 256, Out <= 16. */
+int fov_dense_fwd_bf16(const float* x, const float* W, const float* b, float* y, int N, int In, int Out,
+                       int activation, fov_stream_t stream);
 /* Two stacked fp32 LSTM layers (F <= 96 -> 512 -> 512) in ONE launch - mycode/lstm.py:128-132,218-240: MultiRNNCell of two
  * LSTMCell(400) under dynamic_rnn with a fed state, zero-padded to the matrix-core width 512 (models.pad_lstm).  At the
  * script's batch a layer occupies 64 of 256 CUs, so layer 2 runs beside layer 1, a few steps behind: layer 1 publishes h_t of

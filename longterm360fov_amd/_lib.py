@@ -42,6 +42,8 @@ SIGNATURES = {
     "fov_mix_decoder_fwd": (_I, [_P] * 6 + [ctypes.c_int64] * 2 + [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_mix_decoder_fwd_bf16": (_I, [_P] * 6 + [ctypes.c_int64] * 2 + [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_lstm_seq_fwd_bf16": (_I, [_P] * 10 + [_I] * 5 + [_P, _SZ, _P]),
+    "fov_seq2seq_decode_fwd_bf16": (_I, [_P] * 13 + [_I] * 7 + [_P, _SZ, _P]),
+    "fov_dense_fwd_bf16": (_I, [_P] * 4 + [_I] * 4 + [_P]),
     "fov_mix_decoder_bwd_workspace_bytes": (_SZ, [_I] * 2),
     "fov_mix_decoder_bwd": (_I, [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_mix_decoder_bwd_bf16": (_I, [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),

@@ -502,6 +502,11 @@ __device__ __forceinline__ void q_spare_leaves(unsigned* status, bool exchanging
 // host side
 int launch_layer_bf16(const LstmParams& p, hipStream_t stream);   // lstm_layer_bf16.hip
 bool layer_bf16_shape_ok(int F, int H);
+// lstm_s2s_bf16.hip: the fused seq2seq call (encoder + autoregressive decoder + Dense head) and the Dense it uses
+bool s2s_bf16_shape_ok(int F_enc, int F_dec, int H);
+int launch_s2s_bf16(const LstmParams& p, hipStream_t stream);
+bool dense_bf16_shape_ok(int In, int Out);
+int launch_dense_bf16(const float* x, const float* W, const float* b, float* y, int N, int In, int Out, int act, hipStream_t stream);
 // lstm_stack2_bf16.hip: two stacked layers as one wavefront launch (F <= 96 -> 256 -> 256, zero initial state, one tile per group)
 bool stack2_bf16_shape_ok(int B, int T, int F, int H);
 int launch_stack2_bf16(const float* x, const float* K1, const float* R1, const float* b1, const float* K2, const float* R2,

@@ -642,6 +642,46 @@ int fov_lstm_seq_fwd_bf16(const float* x, const float* K, const float* R, const 
     return launch_layer_bf16(p, (hipStream_t)stream);
 }
 
+int fov_seq2seq_decode_fwd_bf16(const float* enc_in, const float* dec_in0, const float* enc_K, const float* enc_R,
+                                const float* enc_b, const float* dec_K, const float* dec_R, const float* dec_b,
+                                const float* dense_W, const float* dense_b, float* out, float* hT, float* cT, int B,
+                                int T_in, int T_out, int F_enc, int F_dec, int H, int act, void* workspace,
+                                size_t workspace_bytes, fov_stream_t stream) {
+    if (B < 0 || T_in < 0 || T_out < 0 || F_enc <= 0 || F_dec <= 0 || H <= 0 || !enc_K || !enc_R || !enc_b ||
+        !dec_K || !dec_R || !dec_b || !dense_W || !dense_b ||
+        (B > 0 && ((T_in > 0 && !enc_in) || !dec_in0 || (T_out > 0 && !out))) ||
+        (act != FOV_ACT_SIGMOID && act != FOV_ACT_HARD_SIGMOID)) {
+        set_error("fov_seq2seq_decode_fwd_bf16: invalid argument");
+        return FOV_ERR_INVALID;
+    }
+    if (!s2s_bf16_shape_ok(F_enc, F_dec, H)) {
+        set_error("fov_seq2seq_decode_fwd_bf16: H = 256, F_enc <= 256 and F_dec <= 8 only (got H=%d F_enc=%d F_dec=%d)", H, F_enc, F_dec);
+        return FOV_ERR_UNSUPPORTED;
+    }
+    int rc = check_ws(workspace, workspace_bytes, B > 0 ? kStatusBytes + kXchBytes : kStatusBytes);
+    if (rc) return rc;
+    LstmParams p = {};
+    p.x = enc_in; p.K = enc_K; p.R = enc_R; p.b = enc_b; p.hT = hT; p.cT = cT;
+    p.dec_in0 = dec_in0; p.dK = dec_K; p.dR = dec_R; p.db = dec_b; p.dW = dense_W; p.dbias = dense_b; p.out = out;
+    p.B = B; p.T = T_in; p.F = F_enc; p.H = H; p.T_out = T_out; p.F_dec = F_dec; p.act = act;
+    p.status = (unsigned*)workspace;
+    p.xch = (unsigned long long*)((char*)workspace + kStatusBytes);
+    return launch_s2s_bf16(p, (hipStream_t)stream);
+}
+
+int fov_dense_fwd_bf16(const float* x, const float* W, const float* b, float* y, int N, int In, int Out, int activation,
+                       fov_stream_t stream) {
+    if (N < 0 || In <= 0 || Out <= 0 || !W || (N > 0 && (!x || !y)) || (activation != 0 && activation != 1)) {
+        set_error("fov_dense_fwd_bf16: invalid argument");
+        return FOV_ERR_INVALID;
+    }
+    if (!dense_bf16_shape_ok(In, Out)) {
+        set_error("fov_dense_fwd_bf16: In <= 256 and Out <= 16 only (got In=%d Out=%d)", In, Out);
+        return FOV_ERR_UNSUPPORTED;
+    }
+    return launch_dense_bf16(x, W, b, y, N, In, Out, activation, (hipStream_t)stream);
+}
+
 int fov_lstm_stack2_supported_bf16(int B, int T, int F, int H) { return stack2_bf16_shape_ok(B, T, F, H) ? 1 : 0; }
 
 int fov_lstm_stack2_fwd_bf16(const float* x, const float* K1, const float* R1, const float* b1, const float* K2, const float* R2,

@@ -355,10 +355,20 @@ class _SubModel:
 
 
 class Seq2SeqLSTM(KerasModelSurface):
-    """Target-only seq2seq LSTM (1-layer encoder, 1-layer decoder, Dense(tanh) head)."""
+    """Target-only seq2seq LSTM (1-layer encoder, 1-layer decoder, Dense(tanh) head).
+
+    dtype 'bf16' (latent_dim = 256 only): every product with x or h on its left - both layers' gates and the Dense head -
+    takes bf16 operands on the matrix cores with fp32 accumulation, in inference (decode_sequence: one fused launch;
+    predict, encoder_model, decoder_model) and in training; gates, cell state, outputs and the weights the optimizer
+    updates (get_weights / set_weights / .h5) stay fp32.  Subclasses stay fp32."""
 
     def __init__(self, num_encoder_tokens=None, num_decoder_tokens=6, latent_dim=64, recurrent_activation=None,
-                 seed=None, impl="auto", device="cuda"):
+                 seed=None, impl="auto", device="cuda", dtype="f32"):
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("dtype must be 'f32' or 'bf16'")
+        if dtype == "bf16" and int(latent_dim) != 256:
+            raise ValueError("the bf16 path is built for latent_dim = 256")
+        self.dtype = dtype
         self.num_encoder_tokens = 3 * cfg.fps if num_encoder_tokens is None else int(num_encoder_tokens)
         self.num_decoder_tokens = int(num_decoder_tokens)
         self.latent_dim = int(latent_dim)
@@ -422,7 +432,7 @@ class Seq2SeqLSTM(KerasModelSurface):
         outs = []
         for lo in range(0, n, max(bs, 1)):
             o = ops.seq2seq_teacher_forced(self._dev(enc[lo:lo + bs]), self._dev(dec_in[lo:lo + bs]), dw,
-                                           act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
+                                           act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype)
             outs.append(o.cpu().numpy())
         self._ws.check()
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, dec_in.shape[1], self.num_decoder_tokens), np.float32)
@@ -448,7 +458,7 @@ class Seq2SeqLSTM(KerasModelSurface):
         outs = []
         for lo in range(0, n, max(bs, 1)):
             o = ops.seq2seq_decode(self._dev(input_seq[lo:lo + bs]), self._dev(first_decoder_input[lo:lo + bs]), dw,
-                                   T_out, act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
+                                   T_out, act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype)
             outs.append(o.cpu().numpy())
         self._ws.check()
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, self.num_decoder_tokens), np.float32)
@@ -456,9 +466,14 @@ class Seq2SeqLSTM(KerasModelSurface):
     def _encoder_predict(self, input_seq):
         """encoder_model.predict(input_seq) -> [state_h, state_c]   (FoV_seq2seq.py:137,156)."""
         ops, dw = self._ops(), self._device_weights()
-        _, hT, cT = ops.lstm_seq(self._dev(input_seq), dw["enc_K"], dw["enc_R"], dw["enc_b"],
-                                 act=self.recurrent_activation, impl=self.impl, return_sequences=False,
-                                 workspace=self._ws)
+        if self.dtype == "bf16":
+            x = self._dev(input_seq)
+            _, hT, cT, _ = ops.lstm_seq_bf16(x, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=self.recurrent_activation,
+                                             workspace=self._ws, reserve=False)
+        else:
+            _, hT, cT = ops.lstm_seq(self._dev(input_seq), dw["enc_K"], dw["enc_R"], dw["enc_b"],
+                                     act=self.recurrent_activation, impl=self.impl, return_sequences=False,
+                                     workspace=self._ws)
         self._ws.check()
         H = self.latent_dim
         return [hT.cpu().numpy()[:, :H], cT.cpu().numpy()[:, :H]]
@@ -471,9 +486,14 @@ class Seq2SeqLSTM(KerasModelSurface):
         H, Hp = self.latent_dim, self._run_width()
         if Hp != H:
             h, c = pad_cols(h, Hp), pad_cols(c, Hp)
-        hs, hT, cT = ops.lstm_seq(self._dev(target_seq), dw["dec_K"], dw["dec_R"], dw["dec_b"], self._dev(h),
-                                  self._dev(c), act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
-        y = ops.dense(hs, dw["dense_W"], dw["dense_b"], activation="tanh")
+        if self.dtype == "bf16":
+            hs, hT, cT, _ = ops.lstm_seq_bf16(self._dev(target_seq), dw["dec_K"], dw["dec_R"], dw["dec_b"], self._dev(h),
+                                              self._dev(c), act=self.recurrent_activation, workspace=self._ws, reserve=False)
+            y = ops.dense_bf16(hs, dw["dense_W"], dw["dense_b"], activation="tanh")
+        else:
+            hs, hT, cT = ops.lstm_seq(self._dev(target_seq), dw["dec_K"], dw["dec_R"], dw["dec_b"], self._dev(h),
+                                      self._dev(c), act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
+            y = ops.dense(hs, dw["dense_W"], dw["dense_b"], activation="tanh")
         self._ws.check()
         return [y.cpu().numpy(), hT.cpu().numpy()[:, :H], cT.cpu().numpy()[:, :H]]
 
@@ -481,7 +501,7 @@ class Seq2SeqLSTM(KerasModelSurface):
     def _make_trainer(self, optimizer):
         from .training import PaddedTrainer, Seq2SeqTrainer
         make = lambda w: Seq2SeqTrainer(w, act=self.recurrent_activation, impl=self.impl, optimizer=optimizer, lr=self._lr,
-                                        device=self.device)
+                                        device=self.device, dtype=self.dtype)
         Hp = self._run_width()
         if Hp != self.latent_dim:      # latent_dim = 32 / 40 / ...: train on the matrix-core kernels at the next supported width (exact)
             return PaddedTrainer(make, self._w, self.latent_dim, Hp)

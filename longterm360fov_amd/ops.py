@@ -169,12 +169,38 @@ def dense(x, W, b, activation="tanh", out=None):
     return y.reshape(*lead, Out)
 
 
+def dense_bf16(x, W, b, activation="tanh", out=None):
+    """dense() with bf16 operands on the matrix core (fov_dense_fwd_bf16: In <= 256, Out <= 16), fp32 accumulation and
+    output; the arithmetic of the fused bf16 seq2seq call's head."""
+    x, W, b = _dev(x, "x"), _dev(W, "W"), _dev(b, "b")
+    lead = x.shape[:-1]
+    In, Out = W.shape
+    x2 = x.reshape(-1, In)
+    y = torch.empty((x2.shape[0], Out), dtype=torch.float32, device=x.device) if out is None else _dev(out, "out")
+    assert y.numel() == x2.shape[0] * Out
+    check(_lib.lib().fov_dense_fwd_bf16(_ptr(x2), _ptr(W), _ptr(b), _ptr(y), x2.shape[0], In, Out,
+                                        1 if activation == "tanh" else 0, _stream()))
+    return y.reshape(*lead, Out)
+
+
 _W_ORDER = ("enc_K", "enc_R", "enc_b", "dec_K", "dec_R", "dec_b", "dense_W", "dense_b")
 
 
-def seq2seq_decode(enc_in, dec_in0, w, T_out, act="sigmoid", impl="auto", workspace=None, out=None, hT=None, cT=None):
+def _check_dtype(dtype):
+    if dtype not in ("f32", "bf16"):
+        raise ValueError("dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+
+
+def seq2seq_decode_bf16_supported(B, F_enc, F_dec, H):
+    """Shapes fov_seq2seq_decode_fwd_bf16 takes: H = 256, F_enc <= 256, F_dec <= 8 (any batch)."""
+    return B >= 0 and H == 256 and 1 <= F_enc <= 256 and 1 <= F_dec <= 8
+
+
+def seq2seq_decode(enc_in, dec_in0, w, T_out, act="sigmoid", impl="auto", workspace=None, out=None, hT=None, cT=None,
+                   dtype="f32"):
     """Fused encoder + autoregressive decoder (FoV_seq2seq.py:154-178, batched) -> (B,T_out,F_dec); hT / cT (B,H): the decoder's
-    final state, if wanted."""
+    final state, if wanted.  dtype 'bf16': bf16 matrix-core operands (fov_seq2seq_decode_fwd_bf16; impl is not used)."""
+    _check_dtype(dtype)
     enc_in, dec_in0 = _dev(enc_in, "enc_in"), _dev(dec_in0, "dec_in0")
     ws_t = [_dev(w[k], k) for k in _W_ORDER]
     B, T_in, F_enc = enc_in.shape
@@ -184,8 +210,15 @@ def seq2seq_decode(enc_in, dec_in0, w, T_out, act="sigmoid", impl="auto", worksp
     if out is None:
         out = torch.empty((B, T_out, F_dec), dtype=torch.float32, device=enc_in.device)
     L = _lib.lib()
-    impl = impl_code(impl)
     ws = (workspace or default_workspace(enc_in.device))
+    if dtype == "bf16":
+        # the workspace of a bf16 layer (fov_lstm_seq_fwd_bf16): header + granule area
+        buf = ws.get(L.fov_lstm_seq_workspace_bytes(B, T_in, 128, 256, IMPL_CLUSTER), enc_in.device)
+        check(L.fov_seq2seq_decode_fwd_bf16(_ptr(enc_in), _ptr(dec_in0), *[_ptr(t) for t in ws_t], _ptr(out),
+                                            None if hT is None else _ptr(_dev(hT, "hT")), None if cT is None else _ptr(_dev(cT, "cT")),
+                                            B, T_in, T_out, F_enc, F_dec, H, act_code(act), buf.data_ptr(), buf.numel(), _stream()))
+        return out
+    impl = impl_code(impl)
     buf = ws.get(L.fov_seq2seq_decode_workspace_bytes(B, T_in, T_out, F_enc, F_dec, H, impl), enc_in.device)
     check(L.fov_seq2seq_decode_fwd(_ptr(enc_in), _ptr(dec_in0), *[_ptr(t) for t in ws_t], _ptr(out),
                                    None if hT is None else _ptr(_dev(hT, "hT")), None if cT is None else _ptr(_dev(cT, "cT")),
@@ -213,13 +246,22 @@ def seq2seq_decoder(dec_in0, h0, c0, w, T_out, act="sigmoid", impl="auto", works
     return out
 
 
-def seq2seq_teacher_forced(enc_in, dec_in, w, act="sigmoid", impl="auto", workspace=None):
-    """Training-graph forward (FoV_seq2seq.py:82-101) -> (B,T_out,F_dec)."""
+def seq2seq_teacher_forced(enc_in, dec_in, w, act="sigmoid", impl="auto", workspace=None, dtype="f32"):
+    """Training-graph forward (FoV_seq2seq.py:82-101) -> (B,T_out,F_dec).  dtype 'bf16': the encoder and the decoder as
+    bf16 layers (lstm_seq_bf16, the decoder from the encoder's state), then dense_bf16 - the arithmetic of the bf16
+    trainer's forward and of the fused bf16 call's steps."""
+    _check_dtype(dtype)
     enc_in, dec_in = _dev(enc_in, "enc_in"), _dev(dec_in, "dec_in")
     ws_t = [_dev(w[k], k) for k in _W_ORDER]
     B, T_in, F_enc = enc_in.shape
     T_out, F_dec = dec_in.shape[1], dec_in.shape[2]
     H = ws_t[1].shape[0]
+    if dtype == "bf16":
+        e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=enc_in.device)
+        _, hT, cT, _ = lstm_seq_bf16(enc_in, ws_t[0], ws_t[1], ws_t[2], act=act, workspace=workspace, out=(None, e(B, H), e(B, H), None))
+        hs, _, _, _ = lstm_seq_bf16(dec_in, ws_t[3], ws_t[4], ws_t[5], hT, cT, act=act, workspace=workspace,
+                                    out=(e(B, T_out, H), None, None, None))
+        return dense_bf16(hs, ws_t[6], ws_t[7], activation="tanh")
     out = torch.empty((B, T_out, F_dec), dtype=torch.float32, device=enc_in.device)
     L = _lib.lib()
     impl = impl_code(impl)

@@ -347,9 +347,16 @@ class PaddedTrainer:
 class Seq2SeqTrainer(FlatParamTrainer):
     defer_reduces = True   # gradients are written by the library's weight-gradient entry points only
 
-    def __init__(self, weights, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda"):
-        self.act, self.impl = act, impl
+    def __init__(self, weights, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda", dtype="f32"):
+        """dtype 'bf16' (H = 256): the layers' forward and BPTT products and the Dense head's forward take bf16 operands on
+        the matrix cores with fp32 accumulation; the head's backward, the loss, the flat fp32 master weights, the
+        optimizer and the data-parallel all-reduce stay fp32."""
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("dtype must be 'f32' or 'bf16'")
+        self.act, self.impl, self.dtype = act, impl, dtype
         self._alloc(weights, _W_ORDER, optimizer, lr, device)
+        if dtype == "bf16" and self.w["enc_R"].shape[0] != 256:
+            raise ValueError("the bf16 path is built for H = 256")
         self._bufs = {}
 
     def _buffers(self, B, T_in, T_out):
@@ -373,6 +380,8 @@ class Seq2SeqTrainer(FlatParamTrainer):
         B, T_in, _ = enc.shape
         T_out = dec_in.shape[1]
         bufs = self._buffers(B, T_in, T_out)
+        if self.dtype == "bf16":
+            return self._forward_backward_bf16(enc, dec_in, target, grad_weight, bufs)
         ehs, ehT, ecT, eres = ops.lstm_seq_train(enc, w["enc_K"], w["enc_R"], w["enc_b"], act=self.act, impl=self.impl,
                                                  workspace=self.ws, out=bufs["enc"])
         dhs_, _, _, dres = ops.lstm_seq_train(dec_in, w["dec_K"], w["dec_R"], w["dec_b"], ehT, ecT, act=self.act,
@@ -406,8 +415,30 @@ class Seq2SeqTrainer(FlatParamTrainer):
                          dR=g["enc_R"], db=g["enc_b"], act=self.act, dz=bufs["dz_enc"], scratch=self.bwd_scratch)
         return loss, y
 
+    def _forward_backward_bf16(self, enc, dec_in, target, grad_weight, bufs):
+        """bf16 step: both layers' forward and BPTT with bf16 operands, the head forward as dense_bf16 (the prediction
+        equals seq2seq_teacher_forced(dtype='bf16') bit for bit); loss, head backward and all accumulation in fp32.
+        The few-row fp32 shortcuts (dense_mse_head, lstm_seq_wgrad_pair) are not used."""
+        w, g, act = self.w, self.g, self.act
+        ehs, ehT, ecT, eres = ops.lstm_seq_train(enc, w["enc_K"], w["enc_R"], w["enc_b"], act=act, workspace=self.ws,
+                                                 out=bufs["enc"], dtype="bf16")
+        dhs_, _, _, dres = ops.lstm_seq_train(dec_in, w["dec_K"], w["dec_R"], w["dec_b"], ehT, ecT, act=act,
+                                              workspace=self.ws, out=bufs["dec"], dtype="bf16")
+        y = ops.dense_bf16(dhs_, w["dense_W"], w["dense_b"], activation="tanh", out=bufs["y"])
+        dpre, loss = ops.mse_dense_grad(y, target, "tanh", scratch=self.scratch, dpre=bufs["dpre"], loss=self.loss_slot,
+                                        weight=grad_weight, db=g["dense_b"])
+        d_hs, _, _ = ops.dense_bwd(dhs_, w["dense_W"], dpre, dW=g["dense_W"], need_db=False, scratch=self.scratch)
+        bd = ops.lstm_seq_bwd(dec_in, w["dec_K"], w["dec_R"], dhs_, dres, h0=ehT, c0=ecT, dhs=d_hs, dK=g["dec_K"],
+                              dR=g["dec_R"], db=g["dec_b"], need_state_grads=True, act=act, dz=bufs["dz_dec"],
+                              scratch=self.bwd_scratch, dtype="bf16")
+        self.grads_final("dec_K")     # decoder + head + loss: all-reduced under the encoder's BPTT
+        ops.lstm_seq_bwd(enc, w["enc_K"], w["enc_R"], ehs, eres, dhT=bd["dh0"], dcT=bd["dc0"], dK=g["enc_K"],
+                         dR=g["enc_R"], db=g["enc_b"], act=act, dz=bufs["dz_enc"], scratch=self.bwd_scratch, dtype="bf16")
+        return loss, y
+
     def eval_loss(self, enc, dec_in, target):
-        y = ops.seq2seq_teacher_forced(enc, dec_in, self.w, act=self.act, impl=self.impl, workspace=self.ws)
+        y = ops.seq2seq_teacher_forced(enc, dec_in, self.w, act=self.act, impl=self.impl, workspace=self.ws,
+                                       dtype=self.dtype)
         _, loss = ops.mse_dense_grad(y, target, None, scratch=self.scratch)
         return loss
 
