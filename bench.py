@@ -11,8 +11,11 @@ of the timed region.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the step's two persistent-kernel launches
 together against the fp32 MFMA peak, with the duration taken from HIP events on the launch
-stream over the timed region; `kernels` breaks it down per launch (event-timed separately).
-`cpu_baseline` times the C oracle (oracle/lstm_ref.c, "port") on the host cores.
+stream over the timed region.  A plain run does nothing else after its timed steps; --full adds
+what takes work of its own: `kernels` breaks the step down per launch (event-timed separately),
+`parity` checks the output against the C oracle, `large_batch` times the call at 4x the batch,
+`cpu_baseline` times the C oracle (oracle/lstm_ref.c, "port") on the host cores, and at N > 1
+`extra` holds a data-parallel training probe.
 """
 import argparse
 import json
@@ -889,6 +892,73 @@ def bench_convlstm(args, rank, world, use_dist):
             "training": res_train, "cpu_baseline": cpu}), flush=True)
 
 
+def headline_full(args, world, w, enc, dec0, d_enc, d_dec0, dw, out, ws, f_enc, f_dec):
+    """--full, default mode, rank 0, after the timed region: what the line reports beyond its headline figure.  -> `kernels`
+    (the step's two kernels event-timed on their own), `parity` (the timed call's output against the C oracle), `large_batch`
+    (the same call at four times the batch, N = 1) and `cpu_baseline`."""
+    from longterm360fov_amd import ops
+    from oracle import c_oracle as C
+    from oracle import fov_oracle as O
+    B, T_in = enc.shape[:2]
+    T_out, F_dec = out.shape[1:]
+    # per-launch breakdown: each of the step's two kernels event-timed on its own (encoder layer launch; decoder
+    # launch from the encoder's final state)
+    log("per-launch breakdown")
+    iters = max(5, args.steps // 2)
+    _, hT, cT = ops.lstm_seq(d_enc, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=args.act, impl=args.impl,
+                             return_sequences=False, workspace=ws)
+    enc_ms = event_time_ms(lambda: ops.lstm_seq(d_enc, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=args.act, impl=args.impl,
+                                                return_sequences=False, workspace=ws), iters)
+    out2 = torch.empty_like(out)
+    dec_fn = lambda: ops.seq2seq_decoder(d_dec0, hT, cT, dw, T_out, act=args.act, impl=args.impl, workspace=ws, out=out2)
+    dec_fn()
+    dec_ms = event_time_ms(dec_fn, iters)
+    ws.check()
+
+    log("encoder %.4f ms, decoder %.4f ms; parity" % (enc_ms, dec_ms))
+    # parity on the measured configuration: first 64 sequences vs the C oracle; decoder-only call vs the fused call
+    nchk = min(64, B)
+    ref = C.seq2seq_decode(enc[:nchk], dec0[:nchk], w, T_out, ops.act_code(args.act))
+    got = out[:nchk].cpu().numpy()
+    max_abs = float(np.abs(got - ref).max()) if nchk else 0.0
+    mse = float(np.mean((got.astype(np.float64) - ref) ** 2)) if nchk else 0.0
+    split_equal = bool(torch.equal(out, out2))
+
+    # the persistent tile loop's sustained rate: four times the batch (every group walks four tiles; encoder and decoder as two
+    # launches, the state through the workspace) - reported beside the headline, not instead of it
+    large = None
+    if world == 1:
+        Bl = 4 * B
+        enc_l, dec0_l, _ = O.synthetic_batch(4321, Bl, T_in, T_out)
+        dl_enc, dl_dec0 = torch.from_numpy(enc_l).cuda(), torch.from_numpy(dec0_l).cuda()
+        out_l = torch.empty((Bl, T_out, F_dec), dtype=torch.float32, device="cuda")
+        ws_l = ops.Workspace()
+        fn_l = lambda: ops.seq2seq_decode(dl_enc, dl_dec0, dw, T_out, act=args.act, impl=args.impl, workspace=ws_l, out=out_l)
+        ms_l = event_time_ms(fn_l, 10)
+        ws_l.check()
+        ref_l = C.seq2seq_decode(enc_l[-nchk:], dec0_l[-nchk:], w, T_out, ops.act_code(args.act))
+        tf_l = (f_enc + f_dec) * Bl / (ms_l * 1e-3) / 1e12
+        large = {"batch": Bl, "ms_per_call": ms_l, "sequences_per_s": Bl / (ms_l * 1e-3), "tflops": tf_l, "frac": tf_l / PEAK_FP32_MFMA_TFLOPS,
+                 "max_abs_err_vs_oracle": float(np.abs(out_l[-nchk:].cpu().numpy() - ref_l).max()),
+                 "note": "same call at 4x the batch: the groups' tile loop (two launches), 10 event-timed calls"}
+        del dl_enc, dl_dec0, out_l, ws_l
+
+    cpu, cpu_out = None, None
+    if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (launchers also pin OMP_NUM_THREADS = 1)
+        cpu, cpu_out = cpu_baseline_seq2seq(enc, dec0, w, T_out, args.act, budget_s=args.cpu_budget, want_out=True)
+    return {
+        "kernels": {"encoder_ms": enc_ms, "decoder_ms": dec_ms,
+                    "encoder_tflops": f_enc * B / (enc_ms * 1e-3) / 1e12,
+                    "decoder_tflops": f_dec * B / (dec_ms * 1e-3) / 1e12,
+                    "note": "the two phases timed on their own through the layer and decoder-only entry points (two-launch form), %d back-to-back calls each; the fused call is one launch" % iters},
+        "parity": {"max_abs_err_vs_oracle": max_abs, "mse_vs_oracle": mse, "sequences_checked": nchk,
+                   "decoder_only_call_equals_fused_call": split_equal,
+                   "max_abs_err_vs_torch_cpu": None if cpu_out is None else float(np.abs(out.cpu().numpy() - cpu_out).max())},
+        "large_batch": large,
+        "cpu_baseline": cpu,
+    }
+
+
 def bench_dry_run(args, rank, world, use_dist):
     """Launch plumbing only (tests, no GPU): rendezvous, barrier, max-over-ranks, one JSON line from rank 0."""
     import torch.distributed as dist
@@ -921,8 +991,14 @@ def main():
                          "(modes train_mixing and infer_mixing)")
     ap.add_argument("--head", default="all", choices=["all", "meanvar", "gmm", "raw"],
                     help="a10 mode: which of lstm.py's heads to time a training step with besides the mean / variance one")
+    ap.add_argument("--full", action="store_true",
+                    help="default mode: after the headline, also measure and check everything else the line can report - the "
+                         "step's two kernels on their own (kernels), parity against the C oracle (parity), the call at 4x the "
+                         "batch (large_batch), the CPU baseline (cpu_baseline) and, at N > 1, the data-parallel probe (extra).  "
+                         "Without it a run only sets up, warms up, times the steps and prints the line.  The other modes always "
+                         "measure everything they report")
     ap.add_argument("--no-dp-probe", action="store_true",
-                    help="N > 1, default mode: skip the ten data-parallel configs[2] training steps that follow the timed region")
+                    help="N > 1, default mode with --full: skip the ten data-parallel configs[2] training steps that follow the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline timing (both legs together)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="threads of the CPU-baseline legs (default: one GPU's share of the host)")
@@ -1066,10 +1142,11 @@ def main():
         elapsed = float(t.item())
 
     # N > 1: the headline is replicas only (no data-path collective), so a scaling run of it exercises RCCL's start-up and one
-    # scalar all-reduce, nothing more.  Ten data-parallel training steps of configs[2] (512 sequences per rank, one SUM all-reduce
-    # of the 6.7 MB flat gradient buffer per step - given_others_gt_mean_var_seq2seq.py:494-506 under DP) ride along AFTER the
-    # timed region, so that the same run also says what the gradient all-reduce costs over xGMI.  Reported under `extra`.
-    probe_on = use_dist and world > 1 and not args.no_dp_probe
+    # scalar all-reduce, nothing more.  With --full, ten data-parallel training steps of configs[2] (512 sequences per rank, one
+    # SUM all-reduce of the 6.7 MB flat gradient buffer per step - given_others_gt_mean_var_seq2seq.py:494-506 under DP) ride
+    # along AFTER the timed region, so that the same run also says what the gradient all-reduce costs over xGMI.  Reported under
+    # `extra`.
+    probe_on = args.full and use_dist and world > 1 and not args.no_dp_probe
     extra = None
 
     result = None
@@ -1077,53 +1154,7 @@ def main():
         f_enc, f_dec = flops_per_seq(T_in, T_out, F_enc, F_dec, H)
         flop_step = (f_enc + f_dec) * B
         achieved = flop_step / (step_ms_events * 1e-3) / 1e12
-        # per-launch breakdown: each of the step's two kernels event-timed on its own (encoder layer launch; decoder
-        # launch from the encoder's final state)
-        log("timed region done: %.4f ms per step; per-launch breakdown" % step_ms_events)
-        iters = max(5, args.steps // 2)
-        _, hT, cT = ops.lstm_seq(d_enc, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=args.act, impl=args.impl,
-                                 return_sequences=False, workspace=ws)
-        enc_ms = event_time_ms(lambda: ops.lstm_seq(d_enc, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=args.act, impl=args.impl,
-                                                    return_sequences=False, workspace=ws), iters)
-        out2 = torch.empty_like(out)
-        dec_fn = lambda: ops.seq2seq_decoder(d_dec0, hT, cT, dw, T_out, act=args.act, impl=args.impl, workspace=ws, out=out2)
-        dec_fn()
-        dec_ms = event_time_ms(dec_fn, iters)
-        ws.check()
-
-        log("encoder %.4f ms, decoder %.4f ms; parity" % (enc_ms, dec_ms))
-        # parity on the measured configuration: first 64 sequences vs the C oracle; decoder-only call vs the fused call
-        from oracle import c_oracle as C
-        nchk = min(64, B)
-        ref = C.seq2seq_decode(enc[:nchk], dec0[:nchk], w, T_out, ops.act_code(args.act))
-        got = out[:nchk].cpu().numpy()
-        max_abs = float(np.abs(got - ref).max()) if nchk else 0.0
-        mse = float(np.mean((got.astype(np.float64) - ref) ** 2)) if nchk else 0.0
-        split_equal = bool(torch.equal(out, out2))
-
-        # the persistent tile loop's sustained rate: four times the batch (every group walks four tiles; encoder and decoder as two
-        # launches, the state through the workspace) - reported beside the headline, not instead of it
-        large = None
-        if world == 1:
-            Bl = 4 * B
-            enc_l, dec0_l, _ = O.synthetic_batch(4321, Bl, T_in, T_out)
-            dl_enc, dl_dec0 = torch.from_numpy(enc_l).cuda(), torch.from_numpy(dec0_l).cuda()
-            out_l = torch.empty((Bl, T_out, F_dec), dtype=torch.float32, device="cuda")
-            ws_l = ops.Workspace()
-            fn_l = lambda: ops.seq2seq_decode(dl_enc, dl_dec0, dw, T_out, act=args.act, impl=args.impl, workspace=ws_l, out=out_l)
-            ms_l = event_time_ms(fn_l, 10)
-            ws_l.check()
-            ref_l = C.seq2seq_decode(enc_l[-nchk:], dec0_l[-nchk:], w, T_out, ops.act_code(args.act))
-            tf_l = (f_enc + f_dec) * Bl / (ms_l * 1e-3) / 1e12
-            large = {"batch": Bl, "ms_per_call": ms_l, "sequences_per_s": Bl / (ms_l * 1e-3), "tflops": tf_l, "frac": tf_l / PEAK_FP32_MFMA_TFLOPS,
-                     "max_abs_err_vs_oracle": float(np.abs(out_l[-nchk:].cpu().numpy() - ref_l).max()),
-                     "note": "same call at 4x the batch: the groups' tile loop (two launches), 10 event-timed calls"}
-            del dl_enc, dl_dec0, out_l, ws_l
-
-        cpu, cpu_out = None, None
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only (launchers also pin OMP_NUM_THREADS = 1)
-            cpu, cpu_out = cpu_baseline_seq2seq(enc, dec0, w, T_out, args.act, budget_s=args.cpu_budget, want_out=True)
-
+        log("timed region done: %.4f ms per step" % step_ms_events)
         value = world * B * args.steps / elapsed
         # HBM-side bytes per step are not measurable from inside this process: they come from separate rocprofv3
         # --pmc passes over this same command (FETCH_SIZE and WRITE_SIZE, raw KiB per dispatch, encoder +
@@ -1146,20 +1177,13 @@ def main():
                          "traffic_source": traffic_src,
                          "flop_per_launch": flop_step, "launch_ms": step_ms_events,
                          "note": "launch = one step = ONE lstm_cluster_fused_kernel launch (encoder phase + decoder phase)"},
-            "kernels": {"encoder_ms": enc_ms, "decoder_ms": dec_ms,
-                        "encoder_tflops": f_enc * B / (enc_ms * 1e-3) / 1e12,
-                        "decoder_tflops": f_dec * B / (dec_ms * 1e-3) / 1e12,
-                        "note": "the two phases timed on their own through the layer and decoder-only entry points (two-launch form), %d back-to-back calls each; the fused call is one launch" % iters},
             "exchange": {"mode": xmode, "meaning": "1 = every group of the last launch verified a shared XCD and exchanged h "
                                                    "through that XCD's L2; 2 = at least one group on the write-through path"},
-            "parity": {"max_abs_err_vs_oracle": max_abs, "mse_vs_oracle": mse, "sequences_checked": nchk,
-                       "decoder_only_call_equals_fused_call": split_equal,
-                       "max_abs_err_vs_torch_cpu": None if cpu_out is None else float(np.abs(out.cpu().numpy() - cpu_out).max())},
-            "large_batch": large,
-            "cpu_baseline": cpu,
         }
-        if cpu:
-            result["speedup_vs_cpu_baseline"] = value / cpu["value"]
+        if args.full:
+            result.update(headline_full(args, world, w, enc, dec0, d_enc, d_dec0, dw, out, ws, f_enc, f_dec))
+            if result["cpu_baseline"]:
+                result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
     if probe_on:
         # The probe runs AFTER rank 0 has its line ready and under a watchdog: if a collective of the probe never returns, every
         # rank leaves after `limit` seconds and rank 0 still prints the headline line (with the failure under `extra`).

@@ -49,16 +49,17 @@ def test_dump_outputs_is_refused_where_it_is_not_implemented():
 @pytest.mark.gpu
 def test_bench_dumps_the_last_timed_step(tmp_path):
     """The headline run with --steps 3: three timed steps, and the dumped output is the fused call's result on the seeded
-    inputs (first 16 sequences against the C oracle)."""
+    inputs (first 16 sequences against the C oracle).  Without --full the line carries nothing that takes work of its own."""
     sys.path.insert(0, ROOT)
     from oracle import c_oracle as C
     from oracle import fov_oracle as O
     d = str(tmp_path / "dump")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+                        "--dump-outputs", d], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert res["steps"] == 3
+    assert not {"kernels", "parity", "large_batch", "cpu_baseline", "extra"} & set(res), sorted(res)
     out = np.load(os.path.join(d, "seq2seq_decode.npy"))
     assert out.shape == (1024, 30, 6) and out.dtype == np.float32
     w = O.init_seq2seq(1234, 90, 6, 256, bias_noise=0.05)

@@ -36,7 +36,7 @@ def _bench_two_ranks(extra_env, timeout):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FOV_FORCE_DIST"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "64",
-                           "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=timeout)
+                           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=timeout)
 
 
 def _json_line(stdout):
@@ -47,7 +47,7 @@ def _json_line(stdout):
 
 
 def test_bench_two_ranks_rehearsal_carries_the_data_parallel_probe():
-    """The N > 1 form of bench.py end to end on the one GPU of the box (two ranks over gloo, small batches so that both ranks'
+    """The N > 1 form of bench.py --full end to end on the one GPU of the box (two ranks over gloo, small batches so that both ranks'
     persistent grids are co-resident): rank 0's ONE line has n_gpus 2, the whole-job value, and under `extra` the data-parallel
     training probe's step and all-reduce times for fp32 and for bf16."""
     r = _bench_two_ranks({}, 900)

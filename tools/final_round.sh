@@ -5,7 +5,7 @@ out=$1; part=${2:-all}; mkdir -p $out
 # progress goes to $out/progress.log (gpurun takes a command that writes nothing for 7 minutes to be hung)
 exec >> $out/progress.log 2>&1
 if [ $part != pmc ]; then
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 echo "[final_round] bench done"
 for m in train infer_mixing train_mixing; do python3 bench.py --mode $m --steps 200 --warmup 10 --cpu-budget 8 > $out/$m.json 2> $out/$m.err; done
 for m in infer_mixing train_mixing; do python3 bench.py --mode $m --dtype bf16 --steps 200 --warmup 10 --cpu-budget 8 > $out/${m}_bf16.json 2> $out/${m}_bf16.err; done
@@ -22,8 +22,8 @@ python3 bench.py --mode convlstm > $out/convlstm.json 2> $out/convlstm.err
 echo "[final_round] convlstm done"
 fi
 if [ $part != bench ]; then
-bash tools/pmc_run.sh $out bench -- --steps 20 --warmup 3 --no-cpu-baseline
-bash tools/pmc_sq.sh $out bench -- --steps 20 --warmup 3 --no-cpu-baseline
+bash tools/pmc_run.sh $out bench -- --steps 20 --warmup 3 --no-cpu-baseline --full
+bash tools/pmc_sq.sh $out bench -- --steps 20 --warmup 3 --no-cpu-baseline --full
 echo "[final_round] headline PMC done"
 bash tools/prof_train_mixing.sh $out f32
 bash tools/prof_train_mixing.sh $out bf16
