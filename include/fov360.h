@@ -175,7 +175,10 @@ int fov_mix_decoder_fwd_bf16(const float* dec0, const float* h1, const float* c1
                              int B, int T_out, int H, int O, int act,
                              void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
-/* fov_mix_decoder_bwd with bf16 operands in its three transposed products (dz2 R2^T, dz2 K2^T, dz1 R1^T). */
+/* fov_mix_decoder_bwd with bf16 operands in its FOUR transposed products: the recurrences dz2 R2^T -> dh2_{t-1} and
+ * dz1 R1^T -> dh1_{t-1}, and the data products dz2 K2^T -> dh1_t and dz1 K1^T -> dx_t (the feedback gradient into the previous
+ * step's mixing output).  The mixing head's backward (dpre_m mix_Wp^T, dpre_p dense_W^T), gates backward, dc and every output
+ * (DZ1, DZ2 unrounded) stay fp32. */
 int fov_mix_decoder_bwd_bf16(const float* M, const float* P, const float* dloss, const float* res1, const float* res2,
                              const float* C1, const float* C2,
                              const float* dec1_K, const float* dec1_R, const float* dec2_K, const float* dec2_R,
@@ -185,10 +188,16 @@ int fov_mix_decoder_bwd_bf16(const float* M, const float* P, const float* dloss,
                              int B, int T_out, int H, int O, int act,
                              void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
-/* fov_lstm_seq_bwd / fov_dense_bwd with bf16 operands: the recurrence dh_{t-1} = dz_t R^T (eight-workgroup BPTT
- * kernel), the weight-gradient products x^T dz, h_prev^T dz and the data gradient dz K^T all round their operands to
- * bf16 on the fly and accumulate in fp32; gates backward, dz, dc stay fp32.  Same arguments, same workspaces.
- * fov_dense_bwd_bf16 uses the bf16 product for dW when Out >= 64 (the K / R gradients of an unrolled decoder). */
+/* fov_lstm_seq_bwd / fov_dense_bwd with bf16 operands (round-to-nearest-even on the fly, fp32 accumulation); gates backward,
+ * dz (stored unrounded), dc and db (the column sums of the unrounded dz) stay fp32.  Same arguments, same workspaces.
+ * fov_lstm_seq_bwd_bf16, per product:
+ *   - recurrence dh_{t-1} = dz_t R^T: always bf16 (eight-workgroup BPTT kernel); R must be 16-byte aligned (else FOV_ERR_INVALID);
+ *   - data gradient dx = dz K^T: bf16 when K is 16-byte aligned - inside the BPTT kernel when F == 256 and FOV_NO_DX_FUSION is
+ *     unset, else the bf16 NT product; fp32 when K is not aligned (a view at a 4-, 8- or 12-byte offset of a flat buffer);
+ *   - weight products x^T dz and h_{t-1}^T dz (h0^T dz_0 included): bf16, except dK = x^T dz for F <= 8 over >= 1024 rows
+ *     (the fp32 skinny product).
+ * fov_dense_bwd_bf16: dW = x^T dpre is bf16 only when Out >= 64, Out % 4 == 0 and dpre is 16-byte aligned (the K / R gradients
+ * of an unrolled decoder), fp32 otherwise; dx = dpre W^T and db are always fp32. */
 int fov_lstm_seq_bwd_bf16(const float* x, const float* K, const float* R, const float* h0, const float* c0,
                           const float* hs, const float* reserve, const float* dhs, const float* dhT, const float* dcT,
                           float* dz, float* dx, float* dK, float* dR, float* db, float* dh0, float* dc0,

@@ -445,8 +445,14 @@ def _rec_act_grad(a, act):
     return a * (1 - a)
 
 
-def lstm_layer_train(x, K, R, b, h0=None, c0=None, act="sigmoid"):
-    """Forward that also returns the reserve (i,f,g,o,c per step) the backward needs."""
+def _rb_if(flag):
+    """The operand map of a product: round_bf16 when its rounding switch is on, else the identity."""
+    return round_bf16 if flag else (lambda a: a)
+
+
+def lstm_layer_train(x, K, R, b, h0=None, c0=None, act="sigmoid", round_fwd=False):
+    """Forward that also returns the reserve (i,f,g,o,c per step) the backward needs.  round_fwd: both products of every
+    step take bf16-rounded operands (the bf16 forward kernels); off, the arithmetic is exactly the unrounded one."""
     B, T, _ = x.shape
     H = R.shape[0]
     h = np.zeros((B, H), x.dtype) if h0 is None else h0.astype(x.dtype)
@@ -454,8 +460,13 @@ def lstm_layer_train(x, K, R, b, h0=None, c0=None, act="sigmoid"):
     s = _rec_act(act)
     hs = np.empty((B, T, H), x.dtype)
     res = np.empty((B, T, 5, H), x.dtype)
+    if round_fwd:
+        Kr, Rr = round_bf16(K), round_bf16(R)
     for t in range(T):
-        z = x[:, t] @ K + b + h @ R
+        if round_fwd:
+            z = round_bf16(x[:, t]) @ Kr + b + round_bf16(h) @ Rr
+        else:
+            z = x[:, t] @ K + b + h @ R
         i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
         c = f * c + i * g
         h = o * np.tanh(c)
@@ -464,8 +475,13 @@ def lstm_layer_train(x, K, R, b, h0=None, c0=None, act="sigmoid"):
     return hs, h, c, res
 
 
-def lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs=None, dhT=None, dcT=None, act="sigmoid"):
-    """BPTT of one LSTM layer.  Returns dict(dx, dK, dR, db, dh0, dc0, dz)."""
+def lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs=None, dhT=None, dcT=None, act="sigmoid", round_rec=False,
+                        round_dx=False, round_wgrad=False):
+    """BPTT of one LSTM layer.  Returns dict(dx, dK, dR, db, dh0, dc0, dz).
+    Rounding switches (the bf16 backward kernels, see include/fov360.h): round_rec - the recurrence dh_{t-1} = dz_t R^T takes
+    bf16-rounded operands; round_dx - the data gradient dx = dz K^T does; round_wgrad - the weight products x^T dz and
+    h_{t-1}^T dz do.  db is always the sum of the unrounded dz, and dz itself is never rounded.  All off: the unrounded
+    arithmetic, bit for bit."""
     B, T, F = x.shape
     H = R.shape[0]
     dt = x.dtype
@@ -474,6 +490,8 @@ def lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs=None, dhT=None, dcT=None, 
     dh = np.zeros((B, H), dt) if dhT is None else dhT.astype(dt).copy()
     dc = np.zeros((B, H), dt) if dcT is None else dcT.astype(dt).copy()
     dz_all = np.empty((B, T, 4 * H), dt)
+    if round_rec:
+        RrT = round_bf16(R).T
     for t in range(T - 1, -1, -1):
         i, f, g, o, c = (res[:, t, q] for q in range(5))
         c_prev = res[:, t - 1, 4] if t > 0 else c0
@@ -486,11 +504,85 @@ def lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs=None, dhT=None, dcT=None, 
                              dc * i * (1 - g * g), do * _rec_act_grad(o, act)], axis=1)
         dz_all[:, t] = dz
         dc = dc * f
-        dh = dz @ R.T
+        dh = round_bf16(dz) @ RrT if round_rec else dz @ R.T
     hprev = np.concatenate([h0[:, None], hs[:, :-1]], axis=1)
     dz2 = dz_all.reshape(B * T, 4 * H)
-    return {"dx": (dz2 @ K.T).reshape(B, T, F), "dK": x.reshape(B * T, F).T @ dz2,
-            "dR": hprev.reshape(B * T, H).T @ dz2, "db": dz2.sum(axis=0), "dh0": dh, "dc0": dc, "dz": dz_all}
+    rx, rw = _rb_if(round_dx), _rb_if(round_wgrad)
+    return {"dx": (rx(dz2) @ rx(K).T).reshape(B, T, F), "dK": rw(x.reshape(B * T, F)).T @ rw(dz2),
+            "dR": rw(hprev.reshape(B * T, H)).T @ rw(dz2), "db": dz2.sum(axis=0), "dh0": dh, "dc0": dc, "dz": dz_all}
+
+
+# --------------------------------------------------------------------------------------
+# The unrolled others-mixing decoder of the a4 training graph (given_others_gt_mean_var_seq2seq.py:203-308) as the fused
+# decoder kernels see it: inputs are the encoder's final states, the decoder's first input dec0 (B,O) and the others'
+# projection oth_proj (B,T,O) = others_t . mix_W[others' rows] + mix_b.  Per step t (x_0 = dec0, x_{t+1} = m_t):
+#     h1, c1 = LSTM1(x_t, h1, c1);  h2, c2 = LSTM2(h1, h2, c2);  p_t = tanh(h2 dense_W + dense_b);
+#     m_t = tanh(p_t mix_Wp + oth_proj_t)                  (mix_Wp = the prediction's (O,O) rows of mix_W)
+# Tapes, time-major like ops.mix_decoder(train=...): P, M (T,B,O); H1, C1, H2, C2 (T,B,H) = states AFTER step t;
+# res1, res2 (T,B,5,H) = activated i, f, g, o and c of step t.
+# --------------------------------------------------------------------------------------
+def mix_decoder_train_forward(dec0, h1, c1, h2, c2, oth_proj, w, mix_Wp, T_out, act="sigmoid", round_fwd=False):
+    """round_fwd: the two gate products of each layer and the Dense head's product take bf16-rounded operands (the bf16
+    decoder kernel); the mixing product p mix_Wp stays unrounded.  -> dict(M, P, H1, C1, H2, C2, res1, res2)."""
+    s = _rec_act(act)
+    r = _rb_if(round_fwd)
+    K1, R1, K2, R2, Wd = (r(w[k]) for k in ("dec1_K", "dec1_R", "dec2_K", "dec2_R", "dense_W"))
+    B, H = h1.shape
+    x = dec0.reshape(B, -1)
+    tape = {k: [] for k in ("M", "P", "H1", "C1", "H2", "C2", "res1", "res2")}
+
+    def step(x, h, c, K, R, b):
+        z = r(x) @ K + b + r(h) @ R
+        i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
+        c = f * c + i * g
+        return o * np.tanh(c), c, np.stack([i, f, g, o, c], axis=1)
+
+    for t in range(T_out):
+        h1, c1, q1 = step(x, h1, c1, K1, R1, w["dec1_b"])
+        h2, c2, q2 = step(h1, h2, c2, K2, R2, w["dec2_b"])
+        p = np.tanh(r(h2) @ Wd + w["dense_b"])
+        x = np.tanh(p @ mix_Wp + oth_proj[:, t])
+        for k, v in (("M", x), ("P", p), ("H1", h1), ("C1", c1), ("H2", h2), ("C2", c2), ("res1", q1), ("res2", q2)):
+            tape[k].append(v)
+    return {k: np.stack(v) for k, v in tape.items()}
+
+
+def mix_decoder_backward(M, P, dloss, res1, res2, C1, C2, w, mix_Wp, act="sigmoid", round_rec=False, round_dx=False):
+    """BPTT through the unrolled decoder from the fused kernels' own tapes: what ops.mix_decoder_bwd returns.
+    M, P, dloss (T,B,O) - dloss = dL/d(pre-tanh of m_t) from the loss alone; res1, res2 (T,B,5,H); C1, C2: >= T rows of
+    (B,H), row t = the cell state BEFORE step t.  The feedback x_{t+1} = m_t adds dx_{t+1} (1 - m_t^2) to dpre_m of step t.
+    round_rec: the recurrences dz2 R2^T and dz1 R1^T take bf16-rounded operands; round_dx: the data-gradient products
+    dz2 K2^T (-> dh1_t) and dz1 K1^T (-> dx_t, the feedback) do.  The head (dpre_m mix_Wp^T, dpre_p dense_W^T) is unrounded.
+    -> dict(DZ1, DZ2 (T,B,4H), dpre_m, dpre_p (T,B,O), dh1_0, dc1_0, dh2_0, dc2_0 (B,H))."""
+    T, B, O = M.shape
+    H = w["dec1_R"].shape[0]
+    ar, ax = _rb_if(round_rec), _rb_if(round_dx)
+    R1T, R2T, K1T, K2T = ar(w["dec1_R"]).T, ar(w["dec2_R"]).T, ax(w["dec1_K"]).T, ax(w["dec2_K"]).T
+    dt = M.dtype
+    dh1, dc1, dh2, dc2 = (np.zeros((B, H), dt) for _ in range(4))
+    dx = np.zeros((B, O), dt)
+    out = {"DZ1": np.empty((T, B, 4 * H), dt), "DZ2": np.empty((T, B, 4 * H), dt),
+           "dpre_m": np.empty((T, B, O), dt), "dpre_p": np.empty((T, B, O), dt)}
+
+    def gates(q, c_prev, dh, dc):
+        i, f, g, o, c = (q[:, k] for k in range(5))
+        tc = np.tanh(c)
+        dc = dc + dh * o * (1 - tc * tc)
+        dz = np.concatenate([dc * g * _rec_act_grad(i, act), dc * c_prev * _rec_act_grad(f, act),
+                             dc * i * (1 - g * g), dh * tc * _rec_act_grad(o, act)], axis=1)
+        return dz, dc * f
+
+    for t in range(T - 1, -1, -1):
+        dm = dloss[t] + dx * (1 - M[t] * M[t])
+        dpp = (dm @ mix_Wp.T) * (1 - P[t] * P[t])
+        dz2, dc2 = gates(res2[t], C2[t], dpp @ w["dense_W"].T + dh2, dc2)
+        dh2 = ar(dz2) @ R2T
+        dz1, dc1 = gates(res1[t], C1[t], ax(dz2) @ K2T + dh1, dc1)
+        dh1 = ar(dz1) @ R1T
+        dx = ax(dz1) @ K1T
+        out["dpre_m"][t], out["dpre_p"][t], out["DZ2"][t], out["DZ1"][t] = dm, dpp, dz2, dz1
+    out.update(dh1_0=dh1, dc1_0=dc1, dh2_0=dh2, dc2_0=dc2)
+    return out
 
 
 def seq2seq_loss_and_grads(enc_in, dec_in, target, w, act="sigmoid"):

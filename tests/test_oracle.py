@@ -165,6 +165,190 @@ def test_bptt_hard_sigmoid_finite_differences():
             assert abs(fd - g[k][idx]) < 1e-7 + 1e-5 * abs(fd), (k, idx, fd, g[k][idx])
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# bf16 rounding switches of the backward restatements (the references of tests/test_gpu_bf16_backward.py)
+# ---------------------------------------------------------------------------------------------------------------
+def _layer_train_before_switches(x, K, R, b, h0, c0, act):
+    """lstm_layer_train / lstm_layer_backward as they read before the rounding switches: the pin of 'switches off =
+    bit-identical'."""
+    B, T, _ = x.shape
+    H = R.shape[0]
+    h = np.zeros((B, H)) if h0 is None else h0
+    c = np.zeros((B, H)) if c0 is None else c0
+    s = O.hard_sigmoid if act == "hard_sigmoid" else O.sigmoid
+    hs, res = np.empty((B, T, H)), np.empty((B, T, 5, H))
+    for t in range(T):
+        z = x[:, t] @ K + b + h @ R
+        i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
+        c = f * c + i * g
+        h = o * np.tanh(c)
+        hs[:, t] = h
+        res[:, t, 0], res[:, t, 1], res[:, t, 2], res[:, t, 3], res[:, t, 4] = i, f, g, o, c
+    return hs, h, c, res
+
+
+def _layer_backward_before_switches(x, K, R, h0, c0, hs, res, dhs, dhT, dcT, act):
+    B, T, F = x.shape
+    H = R.shape[0]
+    h0 = np.zeros((B, H)) if h0 is None else h0
+    c0 = np.zeros((B, H)) if c0 is None else c0
+    dh = np.zeros((B, H)) if dhT is None else dhT.copy()
+    dc = np.zeros((B, H)) if dcT is None else dcT.copy()
+    dz_all = np.empty((B, T, 4 * H))
+    ag = (lambda a: np.where((a > 0) & (a < 1), 0.2, 0.0)) if act == "hard_sigmoid" else (lambda a: a * (1 - a))
+    for t in range(T - 1, -1, -1):
+        i, f, g, o, c = (res[:, t, q] for q in range(5))
+        c_prev = res[:, t - 1, 4] if t > 0 else c0
+        if dhs is not None:
+            dh = dh + dhs[:, t]
+        tc = np.tanh(c)
+        do = dh * tc
+        dc = dc + dh * o * (1 - tc * tc)
+        dz = np.concatenate([dc * g * ag(i), dc * c_prev * ag(f), dc * i * (1 - g * g), do * ag(o)], axis=1)
+        dz_all[:, t] = dz
+        dc = dc * f
+        dh = dz @ R.T
+    hprev = np.concatenate([h0[:, None], hs[:, :-1]], axis=1)
+    dz2 = dz_all.reshape(B * T, 4 * H)
+    return {"dx": (dz2 @ K.T).reshape(B, T, F), "dK": x.reshape(B * T, F).T @ dz2,
+            "dR": hprev.reshape(B * T, H).T @ dz2, "db": dz2.sum(axis=0), "dh0": dh, "dc0": dc, "dz": dz_all}
+
+
+def _layer_case(seed, B, T, F, H, state):
+    rng = np.random.default_rng(seed)
+    K, R, b = (a.astype(np.float64) for a in O.init_lstm(rng, F, H))
+    b = b + 0.2 * rng.standard_normal(b.shape)
+    x = rng.uniform(-1, 1, (B, T, F))
+    h0 = 0.3 * rng.standard_normal((B, H)) if state else None
+    c0 = 0.3 * rng.standard_normal((B, H)) if state else None
+    up = [0.1 * rng.standard_normal(s) for s in ((B, T, H), (B, H), (B, H))]
+    return x, K, R, b, h0, c0, up
+
+
+@pytest.mark.parametrize("act,state", [("sigmoid", True), ("hard_sigmoid", False)])
+def test_layer_rounding_switches_off_are_bit_identical(act, state):
+    x, K, R, b, h0, c0, (dhs, dhT, dcT) = _layer_case(7, 5, 4, 6, 8, state)
+    new = O.lstm_layer_train(x, K, R, b, h0, c0, act=act)
+    old = _layer_train_before_switches(x, K, R, b, h0, c0, act)
+    for u, v in zip(new, old):
+        np.testing.assert_array_equal(u, v)
+    hs, _, _, res = old
+    gn = O.lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs, dhT, dcT, act=act)
+    go = _layer_backward_before_switches(x, K, R, h0, c0, hs, res, dhs, dhT, dcT, act)
+    for k in go:
+        np.testing.assert_array_equal(gn[k], go[k], err_msg=k)
+
+
+def _torch_layer_grads(x, K, R, b, h0, c0, dhs, dhT, dcT, act, fwd, rec, dx, wgrad):
+    """Independent reference: autograd through the layer with bf16_autograd's product -> (tapes, grads)."""
+    from oracle import bf16_autograd as A
+    B, T, _ = x.shape
+    H = R.shape[0]
+    t = {k: A.leaf(v) for k, v in (("x", x), ("K", K), ("R", R), ("b", b))}
+    h = A.leaf(h0) if h0 is not None else torch.zeros(B, H, dtype=torch.float64)
+    c = A.leaf(c0) if c0 is not None else torch.zeros(B, H, dtype=torch.float64)
+    h_in, c_in, keep, hs = h, c, [], []
+    for s in range(T):
+        h, c = A.lstm_step(t["x"][:, s], h, c, t["K"], t["R"], t["b"], act, fwd, rec, dx, wgrad, keep)
+        hs.append(h)
+    hs = torch.stack(hs, 1)
+    loss = (hs * torch.tensor(dhs)).sum() + (h * torch.tensor(dhT)).sum() + (c * torch.tensor(dcT)).sum()
+    loss.backward()
+    g = {"dx": t["x"].grad, "dK": t["K"].grad, "dR": t["R"].grad, "db": t["b"].grad,
+         "dz": torch.stack([z.grad for z, _ in keep], 1)}
+    if h0 is not None:
+        g["dh0"], g["dc0"] = h_in.grad, c_in.grad
+    tape = (hs.detach().numpy(), torch.stack([q for _, q in keep], 1).detach().numpy())
+    return tape, {k: v.numpy() for k, v in g.items()}
+
+
+@pytest.mark.parametrize("rec,dx,wgrad", [(True, True, True), (True, False, False), (False, True, False), (False, False, True),
+                                          (False, False, False)])
+@pytest.mark.parametrize("act,state", [("sigmoid", True), ("hard_sigmoid", False)])
+def test_layer_backward_rounding_matches_autograd(rec, dx, wgrad, act, state):
+    """Each switch of lstm_layer_backward against torch.autograd in fp64 with the bf16-operand product rounding exactly the
+    same products (forward rounded too, through lstm_layer_train's switch), to 1e-10 of each tensor's scale."""
+    x, K, R, b, h0, c0, (dhs, dhT, dcT) = _layer_case(11, 6, 5, 7, 8, state)
+    (ths, tres), tg = _torch_layer_grads(x, K, R, b, h0, c0, dhs, dhT, dcT, act, True, rec, dx, wgrad)
+    hs, _, _, res = O.lstm_layer_train(x, K, R, b, h0, c0, act=act, round_fwd=True)
+    assert np.abs(hs - ths).max() <= 1e-12 and np.abs(res - tres).max() <= 1e-12
+    g = O.lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs, dhT, dcT, act=act, round_rec=rec, round_dx=dx, round_wgrad=wgrad)
+    plain = O.lstm_layer_backward(x, K, R, h0, c0, hs, res, dhs, dhT, dcT, act=act)
+    for k in tg:
+        scale = np.abs(tg[k]).max()
+        assert np.abs(g[k] - tg[k]).max() <= 1e-10 * scale + 1e-300, k
+    # the switches do something: each rounded product moves its outputs by far more than the agreement above
+    moved = {"dK": wgrad or rec, "dR": wgrad or rec, "dx": dx or rec, "dz": rec}
+    for k, on in moved.items():
+        d = np.abs(g[k] - plain[k]).max() / np.abs(plain[k]).max()
+        assert (d > 1e-5) if on else (d < 1e-12), (k, d)
+
+
+def _decoder_case(seed, B, T, H, O_, act):
+    rng = np.random.default_rng(seed)
+    w = {k: v.astype(np.float64) for k, v in O.init_others_mixing(seed, F_enc=5, F_dec=O_, H=H, num_user=3, bias_noise=0.2).items()}
+    mix_Wp = w["mix_W"][-O_:]
+    st = [0.4 * rng.standard_normal((B, H)) for _ in range(4)]
+    dec0 = rng.uniform(-1, 1, (B, O_))
+    oth = 0.3 * rng.standard_normal((B, T, O_))
+    G = 0.2 * rng.standard_normal((T, B, O_))
+    return w, mix_Wp, st, dec0, oth, G
+
+
+def _torch_decoder(w, mix_Wp, st, dec0, oth, G, T, act, fwd, rec, dx):
+    """Autograd through the unrolled decoder of oracle.mix_decoder_train_forward, loss sum_t <G_t, m_t>."""
+    from oracle import bf16_autograd as A
+    tw = {k: A.leaf(w[k]) for k in ("dec1_K", "dec1_R", "dec1_b", "dec2_K", "dec2_R", "dec2_b", "dense_W", "dense_b")}
+    s0 = [A.leaf(a) for a in st]
+    h1, c1, h2, c2 = s0
+    x = torch.tensor(dec0)
+    k1, k2, pre_p, pre_m, ms, ps = [], [], [], [], [], []
+    for t in range(T):
+        h1, c1 = A.lstm_step(x, h1, c1, tw["dec1_K"], tw["dec1_R"], tw["dec1_b"], act, fwd, rec, dx, False, k1)
+        h2, c2 = A.lstm_step(h1, h2, c2, tw["dec2_K"], tw["dec2_R"], tw["dec2_b"], act, fwd, rec, dx, False, k2)
+        a = A.mm(h2, tw["dense_W"], fwd) + tw["dense_b"]
+        p = torch.tanh(a)
+        zm = p @ torch.tensor(mix_Wp) + torch.tensor(oth[:, t])
+        x = torch.tanh(zm)
+        for v, l in ((a, pre_p), (zm, pre_m)):
+            v.retain_grad()
+            l.append(v)
+        ms.append(x)
+        ps.append(p)
+    M = torch.stack(ms)
+    (M * torch.tensor(G)).sum().backward()
+    g = {"DZ1": torch.stack([z.grad for z, _ in k1]), "DZ2": torch.stack([z.grad for z, _ in k2]),
+         "dpre_m": torch.stack([v.grad for v in pre_m]), "dpre_p": torch.stack([v.grad for v in pre_p]),
+         "dh1_0": s0[0].grad, "dc1_0": s0[1].grad, "dh2_0": s0[2].grad, "dc2_0": s0[3].grad}
+    tape = {"M": M, "P": torch.stack(ps), "res1": torch.stack([q for _, q in k1]), "res2": torch.stack([q for _, q in k2])}
+    return {k: v.detach().numpy() for k, v in tape.items()}, {k: v.numpy() for k, v in g.items()}
+
+
+@pytest.mark.parametrize("fwd,rec,dx", [(False, False, False), (True, True, True), (True, True, False), (True, False, True)])
+@pytest.mark.parametrize("act", ["sigmoid", "hard_sigmoid"])
+def test_mix_decoder_restatement_matches_autograd(fwd, rec, dx, act):
+    """oracle.mix_decoder_train_forward / mix_decoder_backward (head, both layers, the feedback x_{t+1} = m_t) against
+    torch.autograd in fp64 on the same decoder graph, to 1e-10 of each tensor's scale: rounding off, and with the bf16
+    product rounding the recurrences and / or the data-gradient products of both layers."""
+    B, T, H, O_ = 5, 4, 8, 3
+    w, mix_Wp, st, dec0, oth, G = _decoder_case(3, B, T, H, O_, act)
+    tt, tg = _torch_decoder(w, mix_Wp, st, dec0, oth, G, T, act, fwd, rec, dx)
+    tp = O.mix_decoder_train_forward(dec0, *st, oth, w, mix_Wp, T, act=act, round_fwd=fwd)
+    for k in tt:
+        assert np.abs(tp[k] - tt[k]).max() <= 1e-12, k
+    C1 = np.concatenate([st[1][None], tp["C1"]])        # row t = cell state before step t
+    C2 = np.concatenate([st[3][None], tp["C2"]])
+    dloss = G * (1 - tp["M"] ** 2)
+    g = O.mix_decoder_backward(tp["M"], tp["P"], dloss, tp["res1"], tp["res2"], C1, C2, w, mix_Wp, act=act,
+                               round_rec=rec, round_dx=dx)
+    plain = O.mix_decoder_backward(tp["M"], tp["P"], dloss, tp["res1"], tp["res2"], C1, C2, w, mix_Wp, act=act)
+    for k in tg:
+        scale = np.abs(tg[k]).max()
+        assert scale > 0 and np.abs(g[k] - tg[k]).max() <= 1e-10 * scale, (k, np.abs(g[k] - tg[k]).max(), scale)
+    d = max(np.abs(g[k] - plain[k]).max() / np.abs(plain[k]).max() for k in ("DZ1", "dh1_0"))
+    assert (d > 1e-5) if (rec or dx) else (d == 0)
+
+
 def test_adam_matches_torch_with_keras_epsilon_placement():
     """Keras applies eps OUTSIDE the bias-corrected sqrt: p -= lr_t*m/(sqrt(v)+eps).  torch.optim.Adam
     uses eps/sqrt(1-b2^t) scaling differently, so compare against the formula, and against torch for a
