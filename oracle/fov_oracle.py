@@ -1053,3 +1053,442 @@ def init_others_future_convlstm(seed, F_enc=90, F_dec=6, H=64, num_user=34, fps=
         for k in ("enc_b", "dec_b", "oth_b", "flat_b", "dense_b"):
             w[k] = (w[k] + bias_noise * rng.standard_normal(w[k].shape)).astype(dtype)
     return w
+
+
+# --------------------------------------------------------------------------------------
+# Value regimes (tests/test_gpu_value_regimes.py): weights, inputs and states for which stated shares of the
+# pre-activations are clamped / saturated / overflowing IN THE fp64 FORWARD OF THIS FILE, and the yardstick the tests
+# there measure the kernels with.  The default initialisers above keep a gate pre-activation near a standard deviation
+# of 0.3: no element ever meets the clamp of hard_sigmoid, a saturated sigmoid / tanh or a large cell state.
+# The spread sits on the BIAS (a wide normal) and on x K; the recurrent kernel stays orthogonal at gain `r_gain` (1-2, one
+# bf16 case at 4): a large recurrent gain that is not fully saturated makes the recurrence chaotic, fp32 and fp64 then part
+# ways for legitimate reasons and no bound means anything.  With the saturation coming from x K + b the step stays
+# contractive.
+#   R1 clamped      hard_sigmoid: about half of the i / f / o pre-activations beyond +-2.5, the rest on the linear piece
+#   R2 saturated    sigmoid: >= 20 % of the gate pre-activations beyond +-17 (fp32 sigmoid is 0 / 1), >= 20 % of the
+#                   arguments of tanh beyond +-9 (fp32 tanh is +-1): g through the bias; c through a wide initial cell state on
+#                   the 35 % of the units whose forget bias pins f at 1 ("trained forget gates sit at 1").  The other units start
+#                   from a cell state of order 1: an error dz in a forget gate ON ITS SLOPE reaches c as |c_prev| s'(z) dz, so a
+#                   wide c_prev there would turn the last bit of a 256-term sum (1e-6, and dependent on its order) into an error
+#                   of the size of the written 2e-5 - a statement about summation order, not about the kernel
+#   R3 overflow     R2 plus rows `extreme` of the first 16-sequence tile whose pre-activations pass +-100 and +-200 (exp
+#                   overflows to inf on one side and flushes to 0 on the other): the last input feature is theirs alone (zero in
+#                   every other row), its kernel row is +-1, and they carry +-A on it (A = 130 / 300, sign alternating in time;
+#                   one row ordinary until mid-sequence).  EVERY pre-activation of such a row moves by A, so that none of its
+#                   elements is a cancellation of partial sums of magnitude 32 .. 64 that lands back on a slope: such an element
+#                   carries half an ulp of the partial sum per accumulation step, in an order-dependent way (1.5e-5 over 64 steps),
+#                   against a written bound of 2e-5.  `x_edge` is a second batch for the SAME K, R with a zero bias `b_edge`: its
+#                   second tile is all zero (inputs and state), its last tile holds inputs of order 1e-6 from zero state (tanh
+#                   cancels: absolute bounds only)
+#   R4 accumulating forget gate pinned at 1, i * g of one sign per unit through the bias, zero initial state: |c| grows
+#                   linearly with T (T = 256: max |c| passes 50)
+# --------------------------------------------------------------------------------------
+REGIMES = ("R1", "R2", "R3", "R4")
+REGIME_ACT = {"R1": "hard_sigmoid", "R2": "sigmoid", "R3": "sigmoid", "R4": "sigmoid"}
+_REGIME_SPREAD = {      # bias std of (i, f, g, o), std of x K, share of units with the forget gate pinned at 1
+    "R1": ((3.0, 3.0, 3.0, 3.0), 1.5, 0.0),
+    "R2": ((20.0, 20.0, 20.0, 20.0), 4.0, 0.35),
+    "R3": ((20.0, 20.0, 20.0, 20.0), 4.0, 0.35),
+}
+FORGET_PINNED = 30.0    # a forget bias from here on: f = 1.0 exactly in fp32 whatever x K + h R add (|.| < 12)
+
+
+def regime_layer(rng, F, H, regime, x_rms, r_gain=1.0, act=None, dtype=np.float32, xk=None):
+    """K (F,4H), R (H,4H), b (4H,) of one layer in `regime`, for inputs whose elements have root mean square `x_rms`.
+    xk: the spread of x K, overriding the regime's.  A layer whose input is COMPUTED (a hidden state, a fed-back output) keeps it
+    at 0.25 .. 0.5: in the bf16 kernels such an input is rounded to 8 bits before the product, an element on a rounding boundary
+    may round either way, and one bf16 ulp times a large K would move a pre-activation by more than the bound it is held to."""
+    R = (r_gain * _orthogonal(rng, H, 4 * H, np.float64)).astype(dtype)
+    b = np.empty(4 * H)
+    if regime == "R4":
+        hard = act_code(act or REGIME_ACT[regime]) == ACT_HARD_SIGMOID
+        sgn = np.where(rng.random(H) < 0.5, -1.0, 1.0)
+        b[:H] = rng.normal(2.0, 0.5, H)                       # i in (0.6, 1)
+        b[H:2 * H] = 10.0 if hard else 30.0                   # f = 1.0 exactly in both formats
+        b[2 * H:3 * H] = sgn * rng.uniform(1.5, 2.5, H)       # g of one sign per unit (h R stays below 1.5)
+        b[3 * H:] = rng.normal(0.0, 1.0, H)
+        xk = 0.15                                             # (its own, below the ordinary spread: the sign of g must hold)
+    else:
+        sb, xk0, pinned = _REGIME_SPREAD[regime]
+        xk = xk0 if xk is None else xk
+        for q in range(4):
+            b[q * H:(q + 1) * H] = rng.normal(0.0, sb[q], H)
+        bf = b[H:2 * H]
+        bf[bf >= FORGET_PINNED - 15.0] -= 15.0                 # nothing in between: a unit is pinned or well below the pin
+        pin = rng.permutation(H) < int(np.ceil(pinned * H))
+        bf[pin] = rng.uniform(FORGET_PINNED, FORGET_PINNED + 15.0, int(pin.sum()))
+    K = rng.normal(0.0, xk / (np.sqrt(F) * x_rms), (F, 4 * H))
+    return K.astype(dtype), R, b.astype(dtype)
+
+
+def regime_state(rng, B, b, regime, dtype=np.float32):
+    """(h0, c0) (B,H) for a layer with bias b: h0 inside (-1, 1); c0 of order 1, and +-(12 .. 40) on the units whose forget gate
+    is pinned at 1 (R2 / R3)."""
+    H = b.shape[0] // 4
+    h0 = np.clip(0.5 * rng.standard_normal((B, H)), -1, 1)
+    c0 = 0.5 * rng.standard_normal((B, H))
+    pin = b[H:2 * H] >= FORGET_PINNED
+    if regime in ("R2", "R3") and pin.any():
+        wide = rng.uniform(12.0, 40.0, (B, H)) * np.where(rng.random((B, H)) < 0.5, -1.0, 1.0)
+        c0 = np.where(pin[None, :], wide, c0)
+    return h0.astype(dtype), c0.astype(dtype)
+
+
+BF16_XK = 0.3    # the spread of x K in the bf16 cases: the ordinary one (Glorot K, inputs in (-1, 1)).  The product's operands round to 8
+# bits, the bias is added in fp32 and never rounded: with the whole spread on the bias the bf16 kernels stay within the 5e-3 of the
+# FULL-precision oracle that tests/test_gpu_bf16.py holds them to, and the value-regime cases assert it too
+
+
+def regime_lstm(seed, F, H, regime, B, T, act=None, r_gain=1.0, state=True, dtype=np.float32, xk=None):
+    """One LSTM layer's case in a value regime -> dict(K, R, b, x (B,T,F), h0, c0 (B,H) or None, act, regime) and, for R3,
+    extreme (row indices), x_edge, b_edge.  state=False: zero initial state (entry points that take none); R2 / R3 then
+    saturate tanh through g alone."""
+    assert regime in REGIMES
+    act = act or REGIME_ACT[regime]
+    rng = np.random.default_rng(seed)
+    K, R, b = regime_layer(rng, F, H, regime, 1.0 / np.sqrt(3.0), r_gain, act, dtype, xk=xk)
+    x = rng.uniform(-1, 1, (B, T, F)).astype(dtype)
+    p = {"K": K, "R": R, "b": b, "x": x, "h0": None, "c0": None, "act": act, "regime": regime}
+    if regime != "R4" and state:
+        p["h0"], p["c0"] = regime_state(rng, B, b, regime, dtype)
+    if regime == "R3":
+        assert B > 16
+        rows = np.array([3, 9, 12])
+        p["extreme"] = rows
+        K[F - 1] = np.where(rng.random(4 * H) < 0.5, -1.0, 1.0)      # the extreme rows' own feature
+        x[:, :, F - 1] = 0
+        for r, A, t0 in ((rows[0], 130.0, 0), (rows[1], 300.0, 0), (rows[2], 300.0, T // 2)):   # ordinary until t0, then extreme
+            x[r, t0:, F - 1] = A * (-1.0) ** np.arange(t0, T)
+        xe = x.copy()
+        xe[:, :, F - 1] = 0
+        xe[16:32] = 0
+        xe[32:] = rng.uniform(-1e-6, 1e-6, xe[32:].shape)
+        p["x_edge"], p["b_edge"] = xe.astype(dtype), np.zeros_like(b)
+    return p
+
+
+def regime_preactivations(x, K, R, b, hs, h0=None, bf16=False):
+    """z (B,T,4H) of a forward whose hidden states are hs: x_t K + b + h_{t-1} R (bf16: operands rounded as the bf16 kernels do)."""
+    B, T, _ = x.shape
+    H = R.shape[0]
+    hp = np.concatenate([(np.zeros((B, 1, H), x.dtype) if h0 is None else h0[:, None]), hs[:, :-1]], axis=1)
+    r = _rb_if(bf16)
+    return r(x) @ r(K) + b + r(hp) @ r(R)
+
+
+def regime_shares(p, rows=None):
+    """Shares of the fp64 forward of case p (rows: a subset of the batch): gate_clamped (i / f / o beyond +-2.5),
+    gate_sat (beyond +-17), g_sat / c_sat / tanh_sat (arguments of tanh beyond +-9: g's, c's, both pooled), z100 / z200
+    (any pre-activation beyond +-100 / +-200, and the smaller of the two signs' shares), c_max."""
+    f = lambda a: None if a is None else np.asarray(a, np.float64)
+    x, K, R, b, h0, c0 = (f(p[k]) for k in ("x", "K", "R", "b", "h0", "c0"))
+    hs, _, _, res = lstm_layer_train(x, K, R, b, h0, c0, act=p["act"])
+    z = regime_preactivations(x, K, R, b, hs, h0)
+    if rows is not None:
+        z, res = z[rows], res[rows]
+    H = R.shape[0]
+    gates = np.concatenate([z[..., :2 * H], z[..., 3 * H:]], axis=-1)
+    zg, c = z[..., 2 * H:3 * H], res[:, :, 4]
+    two = lambda t: float(min((z > t).mean(), (z < -t).mean()))
+    return {"gate_clamped": float((np.abs(gates) > 2.5).mean()), "gate_sat": float((np.abs(gates) > 17).mean()),
+            "g_sat": float((np.abs(zg) > 9).mean()), "c_sat": float((np.abs(c) > 9).mean()),
+            "tanh_sat": float((np.abs(np.concatenate([zg, c], axis=-1)) > 9).mean()),
+            "z100": two(100.0), "z200": two(200.0), "c_max": float(np.abs(c).max())}
+
+
+# The yardstick.  Written bounds, as a weight per element (error / weight <= 1 is the bound):
+#   "f32"   fp32 values: 1e-3 |ref| + 1e-5 per element AND 2e-5 absolute, per unit of magnitude for a cell state that leaves
+#           (-1, 1): 2e-5 max(1, |ref|)                                  (assert_parity of tests/test_gpu_parity.py)
+#   "abs"   2e-5 absolute alone (inputs of order 1e-6: tanh cancels)
+#   "bf16"  1e-3 max(1, |ref|) against the bf16-operand restatement      (TIGHT of tests/test_gpu_bf16.py)
+#   a float gradients: that fraction of the tensor's max |ref| (+ 1e-9)  (1e-4 fp32; 1e-3 / 2e-3 bf16)
+def regime_error(got, ref, kind):
+    """max over the elements of |got - ref| / (written bound): <= 1 means the written bound holds."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    a = np.abs(ref)
+    if kind == "f32":
+        w = np.minimum(1e-3 * a + 1e-5, 2e-5 * np.maximum(1.0, a))
+    elif kind == "abs":
+        w = 2e-5
+    elif kind == "bf16":
+        w = 1e-3 * np.maximum(1.0, a)
+    else:
+        w = float(kind) * (a.max() if a.size else 0.0) + 1e-9
+    return float((np.abs(got - ref) / w).max()) if got.size else 0.0
+
+
+REGIME_YARDSTICK = 8.0      # fov_common.h documents 3e-7 absolute for tanh_f / sigmoid_f, NumPy's half ulp at 1 is 6e-8: a
+REGIME_YARDSTICK_CAP = 10.0  # factor of 5, rounded up to a power of two.  8 e_ref may not pass 10 written bounds.
+
+
+def regime_bound(e_ref):
+    """The asserted bound in units of the written one: max(1, 8 e_ref)."""
+    return max(1.0, REGIME_YARDSTICK * e_ref)
+
+
+def _cast(p, dt):
+    return [None if p[k] is None else np.asarray(p[k], dt) for k in ("x", "K", "R", "b", "h0", "c0")]
+
+
+def regime_forward_tensors(hs, hT, cT, res):
+    out = {"hs": hs, "hT": hT, "cT": cT}
+    if res is not None:
+        out.update({n: res[:, :, q] for q, n in enumerate("ifgoc")})
+    return out
+
+
+def regime_forward_reference(p, bf16=False, x=None, b=None):
+    """-> (ref, e_ref): the fp64 forward tensors (hs, hT, cT, i, f, g, o, c) of case p and, per tensor, the disagreement of
+    the SAME functions run on fp32 arrays, in units of the written bound.  bf16: both runs round the operands of the two
+    products (lstm_layer_train(round_fwd=True))."""
+    q = dict(p)
+    if x is not None:
+        q["x"], q["b"], q["h0"], q["c0"] = x, b, None, None
+    kind = "bf16" if bf16 else ("abs" if x is not None else "f32")
+    a64, a32 = _cast(q, np.float64), _cast(q, np.float32)
+    r64 = regime_forward_tensors(*lstm_layer_train(*a64, act=p["act"], round_fwd=bf16))
+    r32 = regime_forward_tensors(*lstm_layer_train(*a32, act=p["act"], round_fwd=bf16))
+    return r64, {k: regime_error(r32[k], r64[k], kind) for k in r64}
+
+
+GRAD_KEYS = ("dz", "dx", "dK", "dR", "db", "dh0", "dc0")
+
+
+def regime_upstream(seed, B, T, H, dtype=np.float32):
+    rng = np.random.default_rng(seed)
+    return tuple((0.1 * rng.standard_normal(s)).astype(dtype) for s in ((B, T, H), (B, H), (B, H)))
+
+
+def regime_grad_bounds(bf16):
+    return {k: ((2e-3 if k == "dh0" else 1e-3) if bf16 else 1e-4) for k in GRAD_KEYS}
+
+
+def regime_backward_reference(p, hs, res, ups, bf16=False, dt=np.float64):
+    """lstm_layer_backward of case p on the tape (hs, res) cast to dt; bf16: the products the bf16 BPTT kernel rounds."""
+    x, K, R, _, h0, c0 = _cast(p, dt)
+    c = lambda a: np.asarray(a, dt)
+    return lstm_layer_backward(x, K, R, h0, c0, c(hs), c(res), c(ups[0]), c(ups[1]), c(ups[2]), act=p["act"],
+                               round_rec=bf16, round_dx=bf16, round_wgrad=bf16)
+
+
+def regime_backward_e_ref(p, ups, bf16=False):
+    """Per gradient, the disagreement (in written bounds) of lstm_layer_backward in fp64 and on fp32 arrays, both fed the
+    tape of the fp32 forward of this file: one tape, so both sides take the same branch of every derivative."""
+    hs, _, _, res = lstm_layer_train(*_cast(p, np.float32), act=p["act"], round_fwd=bf16)
+    g64 = regime_backward_reference(p, hs, res, ups, bf16, np.float64)
+    g32 = regime_backward_reference(p, hs, res, ups, bf16, np.float32)
+    tol = regime_grad_bounds(bf16)
+    return {k: regime_error(g32[k], g64[k], tol[k]) for k in GRAD_KEYS}
+
+
+# ---- models built from regime layers --------------------------------------------------------------------------------
+DENSE_SATURATING_BIAS = (12.0, -12.0, 3.0, -3.0, 0.5, -0.5)   # a tanh head whose outputs sit at +-1, near it, and on the slope
+
+
+def _regime_head(rng, H, O, dtype):
+    """Dense(O, tanh) head at gain 1 whose spread sits on the bias: the fed-back output saturates without a loop gain above 1."""
+    W = rng.normal(0.0, 1.0 / np.sqrt(H), (H, O)).astype(dtype)
+    return W, np.resize(np.array(DENSE_SATURATING_BIAS), O).astype(dtype)
+
+
+def regime_seq2seq(seed, regime, B, T_in, H=256, F_enc=90, F_dec=6, r_gain=1.0, dtype=np.float32, xk=None):
+    """Target-only seq2seq (init_seq2seq's keys) with the encoder and the DECODER in `regime` (R1 / R2) and a saturating head.
+    -> (w, enc_in (B,T_in,F_enc), dec_in0 (B,1,F_dec), act)."""
+    assert regime in ("R1", "R2")
+    rng = np.random.default_rng(seed)
+    w = {}
+    w["enc_K"], w["enc_R"], w["enc_b"] = regime_layer(rng, F_enc, H, regime, 1.0 / np.sqrt(3.0), r_gain, None, dtype, xk=xk)
+    w["dec_K"], w["dec_R"], w["dec_b"] = regime_layer(rng, F_dec, H, regime, 0.8, r_gain, None, dtype, xk=0.25)
+    w["dense_W"], w["dense_b"] = _regime_head(rng, H, F_dec, dtype)
+    enc = rng.uniform(-1, 1, (B, T_in, F_enc)).astype(dtype)
+    dec0 = rng.uniform(-1, 1, (B, 1, F_dec)).astype(dtype)
+    return w, enc, dec0, REGIME_ACT[regime]
+
+
+def regime_decode(enc, dec0, w, T_out, act, bf16=False, dt=np.float64):
+    """seq2seq_decode in dtype dt, also returning the decoder's pre-activations: -> dict(out (B,T_out,O), hT, cT, z (B,T_out,4H),
+    pre (B,T_out,O) = the head's arguments of tanh, c (B,T_out,H)).  bf16: every product with x or h on its left rounds both
+    operands (the fused bf16 call)."""
+    c_ = lambda a: np.asarray(a, dt)
+    w = {k: c_(v) for k, v in w.items()}
+    rnd = round_bf16 if bf16 else (lambda a: a)
+    if bf16:
+        with bf16_operands():
+            _, h, c = lstm_layer(c_(enc), w["enc_K"], w["enc_R"], w["enc_b"], act=act)
+    else:
+        _, h, c = lstm_layer(c_(enc), w["enc_K"], w["enc_R"], w["enc_b"], act=act)
+    y = c_(dec0)[:, 0]
+    H = h.shape[1]
+    s = _rec_act(act)
+    out, zs, pres, cs = [], [], [], []
+    for _ in range(T_out):
+        z = rnd(y) @ rnd(w["dec_K"]) + w["dec_b"] + rnd(h) @ rnd(w["dec_R"])
+        c = s(z[:, H:2 * H]) * c + s(z[:, :H]) * np.tanh(z[:, 2 * H:3 * H])
+        h = s(z[:, 3 * H:]) * np.tanh(c)
+        pre = rnd(h) @ rnd(w["dense_W"]) + w["dense_b"]
+        y = np.tanh(pre)
+        out.append(y); zs.append(z); pres.append(pre); cs.append(c)
+    st = lambda v: np.stack(v, axis=1)
+    return {"out": st(out), "hT": h, "cT": c, "z": st(zs), "pre": st(pres), "c": st(cs)}
+
+
+def regime_stack2(seed, regime, B, T, F=90, H=512, state=True, dtype=np.float32, xk=None):
+    """Two stacked layers, both in `regime`: -> (layers [(K, R, b)] * 2, x (B,T,F), states [(h0, c0) or None] * 2, act, p1) with
+    p1 the first layer's regime_lstm case (R3: its extreme rows and edge batch)."""
+    p1 = regime_lstm(seed, F, H, regime, B, T, state=state, dtype=dtype, xk=xk)
+    rng = np.random.default_rng(seed + 1000)
+    l2 = regime_layer(rng, H, H, regime, 0.5, 1.0, None, dtype, xk=0.5)
+    st = [None, None]
+    if p1["h0"] is not None:
+        st[0] = (p1["h0"], p1["c0"])
+        st[1] = regime_state(rng, B, l2[2], regime, dtype)
+    return [(p1["K"], p1["R"], p1["b"]), l2], p1["x"], st, p1["act"], p1
+
+
+def regime_mix_decoder(seed, regime, B, T, H=256, O=6, dtype=np.float32):
+    """The fused others-mixing decoder's inputs with both layers in `regime`: -> (w, mix_Wp (O,O), states [h1, c1, h2, c2],
+    dec0 (B,O), oth_proj (B,T,O), act, extra).  R3 reaches LAYER 1 AND THE HEAD only: row 9's first input is +-500 (layer 1's
+    pre-activations of step 0 pass +-100 and +-200), row 3's others-projection is scaled by 100 (the mixing tanh's arguments pass
+    +-200 at every step); layer 2 reads a hidden state in (-1, 1) and every later input is a tanh output.  extra (R3): rows (3, 9),
+    dec0_calm / oth_calm (the two rows ordinary), and an edge batch under zero biases (w_edge) whose second tile is all zero:
+    dec0_edge, oth_edge, st_edge."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    w["dec1_K"], w["dec1_R"], w["dec1_b"] = regime_layer(rng, O, H, regime, 0.8, 1.0, None, dtype, xk=0.25)
+    w["dec2_K"], w["dec2_R"], w["dec2_b"] = regime_layer(rng, H, H, regime, 0.5, 1.0, None, dtype, xk=0.5)
+    w["dense_W"], w["dense_b"] = _regime_head(rng, H, O, dtype)
+    mix_Wp = (0.5 * rng.standard_normal((O, O))).astype(dtype)
+    st = list(regime_state(rng, B, w["dec1_b"], regime, dtype) + regime_state(rng, B, w["dec2_b"], regime, dtype))
+    dec0 = rng.uniform(-1, 1, (B, O)).astype(dtype)
+    oth = (np.resize(np.array(DENSE_SATURATING_BIAS), O) / 2 + 0.3 * rng.standard_normal((B, T, O))).astype(dtype)
+    extra = {}
+    if regime == "R3":
+        assert B > 16
+        extra = {"rows": np.array([3, 9]), "dec0_calm": dec0.copy(), "oth_calm": oth.copy()}
+        oth[3] *= 100.0
+        dec0[9] = np.where(dec0[9] < 0, -500.0, 500.0)
+        de, oe, se = extra["dec0_calm"].copy(), extra["oth_calm"].copy(), [a.copy() for a in st]
+        for a in [de, oe] + se:
+            a[16:32] = 0
+        extra.update(dec0_edge=de, oth_edge=oe, st_edge=se,
+                     w_edge={k: (np.zeros_like(v) if k.endswith("_b") else v) for k, v in w.items()})
+    return w, mix_Wp, st, dec0, oth, REGIME_ACT[regime], extra
+
+
+def mix_decoder_preactivations(tape, dec0, st, oth_proj, w, mix_Wp, bf16=False):
+    """The pre-activations of a decoder forward whose tapes are `tape` (mix_decoder_train_forward's, any float dtype):
+    -> z1, z2 (T,B,4H) of the two layers and pre_m (T,B,O), the mixing tanh's arguments.  bf16: the operands the bf16 kernel
+    rounds."""
+    r = _rb_if(bf16)
+    B = dec0.shape[0]
+    x = np.concatenate([dec0.reshape(1, B, -1), tape["M"][:-1]])
+    h1p = np.concatenate([st[0][None], tape["H1"][:-1]])
+    h2p = np.concatenate([st[2][None], tape["H2"][:-1]])
+    z1 = r(x) @ r(w["dec1_K"]) + w["dec1_b"] + r(h1p) @ r(w["dec1_R"])
+    z2 = r(tape["H1"]) @ r(w["dec2_K"]) + w["dec2_b"] + r(h2p) @ r(w["dec2_R"])
+    return z1, z2, tape["P"] @ mix_Wp + np.swapaxes(oth_proj, 0, 1)
+
+
+def regime_tape_shares(res, act):
+    """The shares of regime_shares read off a tape of ACTIVATED values res (..., 5, H) = i, f, g, o, c (fp64): a hard_sigmoid
+    gate is exactly 0 / 1 iff its pre-activation lies beyond +-2.5; sigmoid(17) = 1 - 4.14e-8 and tanh(9) = 1 - 3.05e-8."""
+    gates = np.stack([res[..., 0, :], res[..., 1, :], res[..., 3, :]])
+    g, c = res[..., 2, :], res[..., 4, :]
+    if act_code(act) == ACT_HARD_SIGMOID:
+        clamped = float(((gates == 0) | (gates == 1)).mean())
+        sat = 0.0
+    else:
+        s17 = float(sigmoid(np.array([17.0]))[0])
+        sat = float(((gates > s17) | (gates < 1 - s17)).mean())
+        clamped = float(((gates > float(sigmoid(np.array([2.5]))[0])) | (gates < float(sigmoid(np.array([-2.5]))[0]))).mean())
+    g_sat, c_sat = float((np.abs(g) > np.tanh(9.0)).mean()), float((np.abs(c) > 9).mean())
+    return {"gate_clamped": clamped, "gate_sat": sat, "g_sat": g_sat, "c_sat": c_sat, "tanh_sat": 0.5 * (g_sat + c_sat),
+            "c_max": float(np.abs(c).max())}
+
+
+def regime_stack2_forward(layers, x, states, act, dt=np.float64, bf16=False):
+    """-> [(hs, hT, cT, res)] * 2 of two stacked layers in dtype dt (layer 2 reads layer 1's hs)."""
+    c_ = lambda a: None if a is None else np.asarray(a, dt)
+    out, inp = [], c_(x)
+    for (K, R, b), st in zip(layers, states):
+        h0, c0 = (None, None) if st is None else st
+        out.append(lstm_layer_train(inp, c_(K), c_(R), c_(b), c_(h0), c_(c0), act=act, round_fwd=bf16))
+        inp = out[-1][0]
+    return out
+
+
+def regime_stack2_upstream(seed, B, T, H, dtype=np.float32):
+    """dhs2 (B,T,H), dhT2, dcT2, dhT1, dcT1 (B,H)."""
+    rng = np.random.default_rng(seed)
+    return tuple((0.1 * rng.standard_normal(s)).astype(dtype) for s in ((B, T, H),) + ((B, H),) * 4)
+
+
+def regime_stack2_backward(layers, x, states, tapes, ups, act, dt=np.float64):
+    """BPTT of the two stacked layers on the tapes [(hs1, res1), (hs2, res2)] cast to dt: layer 2 from (dhs2, dhT2, dcT2), its
+    dx is layer 1's dhs.  -> dict(dz1, dz2, dK1, dR1, db1, dK2, dR2, db2, dh0_1, dc0_1, dh0_2, dc0_2)."""
+    c_ = lambda a: None if a is None else np.asarray(a, dt)
+    (K1, R1, _), (K2, R2, _) = layers
+    s1, s2 = ((None, None) if s is None else s for s in states)
+    (hs1, res1), (hs2, res2) = tapes
+    dhs2, dhT2, dcT2, dhT1, dcT1 = (c_(u) for u in ups)
+    g2 = lstm_layer_backward(c_(hs1), c_(K2), c_(R2), c_(s2[0]), c_(s2[1]), c_(hs2), c_(res2), dhs2, dhT2, dcT2, act=act)
+    g1 = lstm_layer_backward(c_(x), c_(K1), c_(R1), c_(s1[0]), c_(s1[1]), c_(hs1), c_(res1), g2["dx"], dhT1, dcT1, act=act)
+    out = {}
+    for n, g in (("1", g1), ("2", g2)):
+        out.update({"dz" + n: g["dz"], "dK" + n: g["dK"], "dR" + n: g["dR"], "db" + n: g["db"], "dh0_" + n: g["dh0"],
+                    "dc0_" + n: g["dc0"]})
+    return out
+
+
+def keras_to_tf_cell(K, R, b, forget_bias=1.0):
+    """(K, R, b) in Keras' gate order i, f, c, o -> tf.contrib LSTMCell's (W (F+H,4H), b) in its order i, j, f, o; the cell adds
+    forget_bias itself."""
+    H = R.shape[0]
+    W = np.concatenate([K, R], axis=0)
+    blk = lambda a, q: a[..., q * H:(q + 1) * H]
+    Wt = np.concatenate([blk(W, 0), blk(W, 2), blk(W, 1), blk(W, 3)], axis=-1)
+    bt = np.concatenate([blk(b, 0), blk(b, 2), blk(b, 1) - b.dtype.type(forget_bias), blk(b, 3)])
+    return Wt, bt
+
+
+def regime_convlstm_cell(seed, B, H, W, C, F, k, act, dtype=np.float32):
+    """One ConvLSTM2D step in R3: a wide bias (saturated gates), a wide cell state on the channels whose forget gate is pinned at
+    1, and in map 0 three pixels, far apart, that carry +-A (130, 300, 300) on the last input channel - theirs alone, with kernel
+    taps of +-1 - so that every pre-activation under their taps passes +-100 / +-200 (see R3 above).
+    -> dict(K, R, b, x, h, c, act, x_calm (the extreme pixels removed), b_edge (zeros), x_edge / h_edge / c_edge (last batch
+    element all zero))."""
+    rng = np.random.default_rng(seed)
+    hard = act_code(act) == ACT_HARD_SIGMOID
+    K = (rng.standard_normal((k, k, C, 4 * F)) / np.sqrt(k * k * C)).astype(dtype)
+    K[:, :, C - 1] = np.where(rng.random((k, k, 4 * F)) < 0.5, -1.0, 1.0)
+    R = (rng.standard_normal((k, k, F, 4 * F)) / np.sqrt(k * k * F)).astype(dtype)
+    b = rng.normal(0.0, 3.0 if hard else 20.0, 4 * F)
+    pin = rng.permutation(F) < int(np.ceil(0.35 * F))
+    b[F:2 * F][pin] = 10.0 if hard else FORGET_PINNED
+    b = b.astype(dtype)
+    x = rng.standard_normal((B, H, W, C)).astype(dtype)
+    x[..., C - 1] = 0
+    h = np.clip(0.5 * rng.standard_normal((B, H, W, F)), -1, 1).astype(dtype)
+    wide = rng.uniform(12.0, 40.0, (B, H, W, F)) * np.where(rng.random((B, H, W, F)) < 0.5, -1.0, 1.0)
+    c = np.where(pin, wide, 0.5 * rng.standard_normal((B, H, W, F))).astype(dtype)
+    x_calm = x.copy()
+    for n, (y, xx) in enumerate(((H // 2, W // 2), (0, 0), (H - 1, W - 1))):
+        x[0, y, xx, C - 1] = (300.0 if n else 130.0) * (-1.0) ** n
+    xe, he, ce = x_calm.copy(), h.copy(), c.copy()
+    xe[-1], he[-1], ce[-1] = 0, 0, 0
+    return {"K": K, "R": R, "b": b, "x": x, "h": h, "c": c, "act": act, "x_calm": x_calm, "b_edge": np.zeros_like(b),
+            "x_edge": xe, "h_edge": he, "c_edge": ce}
+
+
+def regime_convlstm_reference(p, dt=np.float64, x=None, b=None, h=None, c=None):
+    """-> dict(h, c, gates (B,H,W,4F) activated i, f, g, o, z (pre-activations)) of one ConvLSTM2D step in dtype dt."""
+    c_ = lambda a: np.asarray(a, dt)
+    x, b = c_(p["x"] if x is None else x), c_(p["b"] if b is None else b)
+    h, c = c_(p["h"] if h is None else h), c_(p["c"] if c is None else c)
+    F = p["R"].shape[2]
+    z = conv2d_same(x, c_(p["K"]), b) + conv2d_same(h, c_(p["R"]))
+    s = _rec_act(p["act"])
+    gates = np.concatenate([s(z[..., :F]), s(z[..., F:2 * F]), np.tanh(z[..., 2 * F:3 * F]), s(z[..., 3 * F:])], axis=-1).astype(dt)
+    cn = gates[..., F:2 * F] * c + gates[..., :F] * gates[..., 2 * F:3 * F]
+    return {"h": (gates[..., 3 * F:] * np.tanh(cn)).astype(dt), "c": cn.astype(dt), "gates": gates, "z": z}

@@ -670,3 +670,189 @@ def test_dilated_conv_and_convlstm_step_against_torch():
     hn = hs(z[..., 9:]) * np.tanh(cn)
     h2, c2 = O.convlstm2d_step(x, h, c, K, R, b, "hard_sigmoid", dilation=2)
     assert np.abs(h2 - hn).max() < 1e-12 and np.abs(c2 - cn).max() < 1e-12
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The value-regime generator (tests/test_gpu_value_regimes.py): for every case of that file's tables the promised shares of
+# clamped / saturated / overflowing pre-activations hold in the fp64 forward, and the yardstick's condition holds: 8 e_ref
+# (fp64 against the same functions on fp32 arrays, in written bounds) is at most 10.  A later edit of the generator cannot
+# quietly move the cases back into the linear regime or into one where the reference itself is ill-conditioned.
+# ---------------------------------------------------------------------------------------------------------------------
+def _cap(tag, e_ref):
+    for k, v in e_ref.items():
+        assert O.REGIME_YARDSTICK * v <= O.REGIME_YARDSTICK_CAP, "%s %s: 8 e_ref = %.3g" % (tag, k, 8 * v)
+
+
+def _assert_shares(tag, regime, sh, state=True):
+    if regime == "R1":
+        assert 0.30 <= sh["gate_clamped"] <= 0.70, (tag, sh)
+    if regime in ("R2", "R3"):
+        assert sh["gate_sat"] >= 0.20 and sh["g_sat"] >= 0.20 and sh["tanh_sat"] >= 0.20, (tag, sh)
+        if state:
+            assert sh["c_sat"] >= 0.20, (tag, sh)
+    if regime == "R4":
+        assert sh["c_max"] > 50, (tag, sh)
+
+
+def _regime_layer_case(tag, p, bf16, backward_seed=None):
+    regime = p["regime"]
+    B = p["x"].shape[0]
+    if regime == "R3":
+        rows = p["extreme"]
+        _assert_shares(tag, regime, O.regime_shares(p, np.setdiff1d(np.arange(16), rows)))       # the tile-mates stay in R2
+        ex = O.regime_shares(p, rows[:2])
+        assert ex["z100"] >= 0.10 and ex["z200"] >= 0.05, (tag, ex)                               # both signs, each
+        late = O.regime_shares({**p, "x": p["x"][:, :p["x"].shape[1] // 2]}, rows[2:])
+        assert late["z100"] == 0.0, (tag, late)                                                   # ordinary until mid-sequence
+        xe = p["x_edge"]
+        assert (xe[16:32] == 0).all() and 0 < np.abs(xe[32:]).max() <= 1e-6 and (p["b_edge"] == 0).all()
+        _cap(tag + " edge", O.regime_forward_reference(p, bf16=bf16, x=xe, b=p["b_edge"])[1])
+    else:
+        sh = O.regime_shares(p)
+        _assert_shares(tag, regime, sh)
+        if regime == "R4":
+            H = p["R"].shape[0]
+            res = O.lstm_layer_train(*[None if p[k] is None else p[k].astype(np.float64) for k in ("x", "K", "R", "b", "h0", "c0")],
+                                     act=p["act"])[3]
+            assert (res[:, :, 1].astype(np.float32) == 1.0).all()                                 # forget gate: exactly 1 in fp32
+            ig = res[:, :, 0] * res[:, :, 2]
+            assert ((ig > 0).all(axis=(0, 1)) | (ig < 0).all(axis=(0, 1))).all()                  # one sign per unit
+            assert p["b"].astype(np.float32)[H:2 * H].min() >= 10.0
+    _cap(tag, O.regime_forward_reference(p, bf16=bf16)[1])
+    if backward_seed is not None:
+        T, H = p["x"].shape[1], p["R"].shape[0]
+        _cap(tag + " backward", O.regime_backward_e_ref(p, O.regime_upstream(backward_seed, B, T, H), bf16=bf16))
+
+
+@pytest.mark.parametrize("regime", O.REGIMES)
+def test_value_regime_layer_cases_hold_their_shares_and_the_yardstick_condition(regime):
+    import test_gpu_value_regimes as V
+    for impl, H in sorted({(i, h) for i, h, _ in V.LAYER_FORWARD}):
+        for B, T in V.LAYER_SHAPE[regime]:
+            _regime_layer_case("%s H%d %s B%d" % (impl, H, regime, B), O.regime_lstm(V.layer_seed(H, regime, B), 90, H, regime, B, T), False)
+    for r, B, T, gain, seed in V.BF16_LAYER:
+        if r == regime:
+            _regime_layer_case("bf16 layer %s gain %g" % (r, gain), O.regime_lstm(V.layer_seed(256, r, B) + seed, 90, 256, r, B, T, r_gain=gain, xk=O.BF16_XK), True)
+    B, T = V.BACKWARD_SHAPE[regime]
+    for name, H, _, dtype in V.BACKWARD_FORMS:
+        bf = dtype == "bf16"
+        p = O.regime_lstm(V.layer_seed(H, regime, B) + 1, 90 if bf else 11, H, regime, B, T, xk=O.BF16_XK if bf else None)
+        _regime_layer_case("%s %s" % (name, regime), p, bf, backward_seed=V.layer_seed(H, regime, B) + 2)
+
+
+def test_value_regime_generator_is_seeded_and_keeps_the_recurrent_kernel_orthogonal():
+    a, b = O.regime_lstm(3, 11, 64, "R3", 37, 8), O.regime_lstm(3, 11, 64, "R3", 37, 8)
+    for k in ("K", "R", "b", "x", "h0", "c0", "x_edge"):
+        np.testing.assert_array_equal(a[k], b[k])
+    for gain in (1.0, 2.0, 4.0):
+        R = O.regime_lstm(4, 11, 64, "R1", 16, 2, r_gain=gain)["R"].astype(np.float64)
+        np.testing.assert_allclose(R @ R.T, gain * gain * np.eye(64), atol=1e-5)
+
+
+def test_value_regime_model_cases_hold_their_shares_and_the_yardstick_condition():
+    import test_gpu_value_regimes as V
+    H = 256
+    T_in, T_out = V.DECODE_T
+    for regime, B, dtype, _ in V.DECODE:
+        bf = dtype == "bf16"
+        w, enc, dec0, act = O.regime_seq2seq(50 + B, regime, B, T_in, xk=O.BF16_XK if bf else None)
+        if not bf:      # regime_decode exposes the pre-activations; it is seq2seq_decode, bit for bit
+            np.testing.assert_array_equal(O.regime_decode(enc, dec0, w, T_out, act)["out"],
+                                          O.seq2seq_decode(enc.astype(np.float64), dec0.astype(np.float64),
+                                                           {k: v.astype(np.float64) for k, v in w.items()}, T_out, act))
+        r64, r32 = O.regime_decode(enc, dec0, w, T_out, act, bf, np.float64), O.regime_decode(enc, dec0, w, T_out, act, bf, np.float32)
+        z = r64["z"]
+        gates = np.concatenate([z[..., :2 * H], z[..., 3 * H:]], axis=-1)
+        tag = "decode %s B%d %s" % (regime, B, dtype)
+        if regime == "R1":
+            assert 0.30 <= (np.abs(gates) > 2.5).mean() <= 0.70, tag
+        else:
+            assert (np.abs(gates) > 17).mean() >= 0.20, tag
+            assert (np.abs(np.concatenate([z[..., 2 * H:3 * H], r64["c"]], axis=-1)) > 9).mean() >= 0.20, tag
+        assert (np.abs(r64["pre"]) > 9).mean() >= 0.20 and (r64["pre"] > 10.5).any() and (r64["pre"] < -10.5).any(), tag
+        kind = "bf16" if bf else "f32"
+        _cap(tag, {k: O.regime_error(r32[k], r64[k], kind) for k in ("out", "hT", "cT")})
+    B, T, F = V.STACK2_SHAPE
+    for regime, Hh in V.STACK2:
+        layers, x, st, act, p1 = O.regime_stack2(70 + O.REGIMES.index(regime), regime, B, T, F, Hh)
+        f64, f32 = O.regime_stack2_forward(layers, x, st, act, np.float64), O.regime_stack2_forward(layers, x, st, act, np.float32)
+        for l in range(2):
+            tag = "stack2 H%d %s layer %d" % (Hh, regime, l + 1)
+            keep = np.setdiff1d(np.arange(B), p1["extreme"]) if regime == "R3" else np.arange(B)
+            _assert_shares(tag, regime, O.regime_tape_shares(f64[l][3][keep], act))
+            t64, t32 = O.regime_forward_tensors(*f64[l]), O.regime_forward_tensors(*f32[l])
+            _cap(tag, {k: O.regime_error(t32[k], t64[k], "f32") for k in t64})
+        ups = O.regime_stack2_upstream(80, B, T, Hh)
+        tapes = [(f32[0][0], f32[0][3]), (f32[1][0], f32[1][3])]
+        y64 = O.regime_stack2_backward(layers, x, st, tapes, ups, act, np.float64)
+        y32 = O.regime_stack2_backward(layers, x, st, tapes, ups, act, np.float32)
+        _cap("stack2 %s backward" % regime, {k: O.regime_error(y32[k], y64[k], 1e-4) for k in y64})
+    for regime in V.STACK2_BF16:
+        layers, x, st, act, p1 = O.regime_stack2(75 + O.REGIMES.index(regime), regime, B, T, F, 256, state=False, xk=O.BF16_XK)
+        f64 = O.regime_stack2_forward(layers, x, st, act, np.float64, bf16=True)
+        f32 = O.regime_stack2_forward(layers, x, st, act, np.float32, bf16=True)
+        keep = np.setdiff1d(np.arange(B), p1["extreme"]) if regime == "R3" else np.arange(B)
+        for l in range(2):
+            tag = "stack2 bf16 %s layer %d" % (regime, l + 1)
+            _assert_shares(tag, regime, O.regime_tape_shares(f64[l][3][keep], act), state=False)
+            t64, t32 = O.regime_forward_tensors(*f64[l]), O.regime_forward_tensors(*f32[l])
+            _cap(tag, {k: O.regime_error(t32[k], t64[k], "bf16") for k in t64})
+    for regime in V.TF_STACK:       # the same two layers at 400 units, through the tf.contrib cell (one product over [x, h])
+        layers, x, st, act, p1 = O.regime_stack2(90 + O.REGIMES.index(regime), regime, B, T, F, 400)
+        f64 = O.regime_stack2_forward(layers, x, st, act, np.float64)
+        keep = np.setdiff1d(np.arange(B), p1["extreme"]) if regime == "R3" else np.arange(B)
+        for l in range(2):
+            _assert_shares("tf stack %s layer %d" % (regime, l + 1), regime, O.regime_tape_shares(f64[l][3][keep], act))
+        cells = [O.keras_to_tf_cell(*l) for l in layers]
+        st0 = np.stack([np.stack([s_[1], s_[0]]) for s_ in st]).astype(np.float32)
+        r64 = O.tf_dynamic_rnn(x.astype(np.float64), [(W.astype(np.float64), b.astype(np.float64)) for W, b in cells], st0.astype(np.float64))
+        r32 = O.tf_dynamic_rnn(x, cells, st0)
+        np.testing.assert_allclose(r64[0], f64[1][0], atol=1e-6)       # the mapping to tf.contrib's gate order (b_f - 1 rounds in fp32)
+        _cap("tf stack %s" % regime, {"states_series": O.regime_error(r32[0], r64[0], "f32"),
+                                      "current_state": O.regime_error(r32[1], r64[1], "f32")})
+    B, T, O_ = V.MIX_SHAPE
+    for regime, dtype in V.MIX:
+        bf = dtype == "bf16"
+        w, mix_Wp, st, dec0, oth, act, extra = O.regime_mix_decoder(60 + O.REGIMES.index(regime), regime, B, T, H, O_)
+
+        def fwd(dt):
+            c_ = lambda a: np.asarray(a, dt)
+            return O.mix_decoder_train_forward(c_(dec0), *[c_(s) for s in st], c_(oth), {k: c_(v) for k, v in w.items()}, c_(mix_Wp), T,
+                                               act=act, round_fwd=bf)
+        r64, r32 = fwd(np.float64), fwd(np.float32)
+        tag = "mix decoder %s %s" % (regime, dtype)
+        for n in ("res1", "res2"):
+            _assert_shares(tag + " " + n, regime, O.regime_tape_shares(r64[n], act))
+        if regime == "R3":      # layer 1 at row 9, step 0 and the mixing head at row 3 see overflowing arguments of both signs
+            f64_ = lambda a: np.asarray(a, np.float64)
+            z1, z2, pre_m = O.mix_decoder_preactivations(r64, f64_(dec0), [f64_(a) for a in st], f64_(oth),
+                                                         {k: f64_(v) for k, v in w.items()}, f64_(mix_Wp), bf16=bf)
+            for t_ in (100, 200):
+                assert (z1[0, 9] > t_).sum() >= 50 and (z1[0, 9] < -t_).sum() >= 50, (tag, t_)
+            assert (pre_m[:, 3] > 200).sum() > 0 and (pre_m[:, 3] < -200).sum() > 0, tag
+            assert np.abs(z2).max() < 100                                       # layer 2 is not reached
+            for k in ("dec0_edge", "oth_edge"):
+                assert (extra[k][16:32] == 0).all()
+            assert all((a[16:32] == 0).all() for a in extra["st_edge"]) and all((extra["w_edge"][k] == 0).all() for k in w if k.endswith("_b"))
+            keep = np.setdiff1d(np.arange(B), extra["rows"])
+            np.testing.assert_array_equal(extra["dec0_calm"][keep], dec0[keep])
+            np.testing.assert_array_equal(extra["oth_calm"][keep], oth[keep])
+        kind = "bf16" if bf else "f32"
+        _cap(tag, {k: O.regime_error(r32[k], r64[k], kind) for k in r64})
+        G = (0.2 * np.random.default_rng(61).standard_normal((T, B, O_))).astype(np.float32)
+        C1, C2 = np.concatenate([st[1][None], r32["C1"]]), np.concatenate([st[3][None], r32["C2"]])
+
+        def bwd(dt):
+            c_ = lambda a: np.asarray(a, dt)
+            return O.mix_decoder_backward(c_(r32["M"]), c_(r32["P"]), c_(G * (1 - r32["M"] * r32["M"])), c_(r32["res1"]), c_(r32["res2"]),
+                                          c_(C1), c_(C2), {k: c_(v) for k, v in w.items()}, c_(mix_Wp), act=act, round_rec=bf, round_dx=bf)
+        y64, y32 = bwd(np.float64), bwd(np.float32)
+        _cap(tag + " backward", {k: O.regime_error(y32[k], y64[k], ((2e-3 if k in ("dh1_0", "dh2_0") else 1e-3) if bf else 1e-4))
+                                 for k in y64})
+    for shape, act in V.CONV:
+        p = O.regime_convlstm_cell(40 + shape[3], *shape, act)
+        r64, r32 = O.regime_convlstm_reference(p), O.regime_convlstm_reference(p, np.float32)
+        z = r64["z"]
+        assert min((z > 100).sum(), (z < -100).sum(), (z > 200).sum(), (z < -200).sum()) >= 100, (shape, act)
+        assert (p["x_edge"][-1] == 0).all() and (p["h_edge"][-1] == 0).all() and (p["c_edge"][-1] == 0).all()
+        _cap("convlstm cell %s %s" % (shape, act), {k: O.regime_error(r32[k], r64[k], "f32") for k in ("h", "c", "gates")})
