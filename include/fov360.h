@@ -664,6 +664,23 @@ int fov_conv2d_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batch_strid
                    const float* add, float* y, int B, int H, int W, int C, int N, int kh, int kw, int activation,
                    fov_stream_t stream);
 
+/* fov_conv2d_fwd with bf16 matrix-core operands - inference of the Conv2D / Conv1D prediction head
+ * (convlstm_seq2seq.py:176-181,231-238).  Arithmetic contract:
+ *     y = act(conv2d_same(bf16(x), bf16(w)) + b)
+ * both operands of every product rounded to bf16 round-to-nearest-even, products accumulated in fp32 in an order the
+ * kernel chooses, bias added and relu applied in fp32, y stored fp32.  Stride 1, 'same' zero padding, odd kh, kw,
+ * dilation 1.  The weights are constant across a predict call, so they are packed ONCE: fov_conv2d_pack_bf16 writes
+ * fov_conv2d_bf16_packed_bytes(C, N, kh, kw) bytes (16-byte aligned, caller-owned device memory) from the fp32
+ * (kh,kw,C,N) kernel; the layout is private to the library and depends on (C, N, kh, kw) only. */
+size_t fov_conv2d_bf16_packed_bytes(int C, int N, int kh, int kw);
+/* convlstm_seq2seq.py:176-181,231-238: the head's kernels, rounded and reordered for fov_conv2d_fwd_bf16. */
+int fov_conv2d_pack_bf16(const float* w, void* packed, int C, int N, int kh, int kw, fov_stream_t stream);
+/* convlstm_seq2seq.py:176-181,231-238: x, its strides, b, y, B .. activation as in fov_conv2d_fwd; w_packed is what
+ * fov_conv2d_pack_bf16 wrote for the same (C, N, kh, kw).  The empty batch is FOV_OK; operands beyond 2 GiB are
+ * FOV_ERR_UNSUPPORTED. */
+int fov_conv2d_fwd_bf16(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, const void* w_packed, const float* b,
+                        float* y, int B, int H, int W, int C, int N, int kh, int kw, int activation, fov_stream_t stream);
+
 /* The same convolution over the channel concatenation [x1 | x2] (w: (kh,kw,C1+C2,N)) without the concatenated
  * map ever existing: one ConvLSTM2D step is z = conv([x_t | h_{t-1}], [K ; R]) + b in ONE launch
  * (convlstm_seq2seq.py:100-126: Keras runs input_conv and recurrent_conv separately and adds). */

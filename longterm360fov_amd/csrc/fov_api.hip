@@ -1543,6 +1543,35 @@ int fov_conv2d_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batch_strid
     return conv2d_fwd(x, (long)x_pixel_stride, (long)x_batch_stride, w, b, add, y, B, H, W, C, N, kh, kw, activation, (hipStream_t)stream);
 }
 
+size_t fov_conv2d_bf16_packed_bytes(int C, int N, int kh, int kw) {
+    if (C <= 0 || N <= 0 || kh <= 0 || kw <= 0) return 0;
+    return conv2d_bf16_packed_bytes(C, N, kh, kw);
+}
+
+int fov_conv2d_pack_bf16(const float* w, void* packed, int C, int N, int kh, int kw, fov_stream_t stream) {
+    if (!w || !packed || (((uintptr_t)packed) & 15) || C <= 0 || N <= 0 || kh <= 0 || kw <= 0 || (kh & 1) == 0 || (kw & 1) == 0) {
+        set_error("fov_conv2d_pack_bf16: invalid argument (odd kernel sizes only, packed 16-byte aligned)");
+        return FOV_ERR_INVALID;
+    }
+    if (conv2d_bf16_packed_bytes(C, N, kh, kw) >= ((size_t)1 << 31) || (int64_t)kh * kw * C * N * 4 >= ((int64_t)1 << 31)) {
+        set_error("fov_conv2d_pack_bf16: operand larger than 2 GiB");
+        return FOV_ERR_UNSUPPORTED;
+    }
+    return conv2d_pack_bf16(w, packed, C, N, kh, kw, (hipStream_t)stream);
+}
+
+int fov_conv2d_fwd_bf16(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, const void* w_packed, const float* b,
+                        float* y, int B, int H, int W, int C, int N, int kh, int kw, int activation, fov_stream_t stream) {
+    if (B < 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || kh <= 0 || kw <= 0 || (kh & 1) == 0 || (kw & 1) == 0 ||
+        x_pixel_stride < C || x_batch_stride < (int64_t)H * W * x_pixel_stride || !w_packed || (((uintptr_t)w_packed) & 15) ||
+        (B > 0 && (!x || !y)) || (activation != 0 && activation != 2)) {
+        set_error("fov_conv2d_fwd_bf16: invalid argument (odd kernel sizes only, activation 0 or 2, w_packed 16-byte aligned)");
+        return FOV_ERR_INVALID;
+    }
+    return conv2d_fwd_bf16(x, (long)x_pixel_stride, (long)x_batch_stride, w_packed, b, y, B, H, W, C, N, kh, kw, activation,
+                           (hipStream_t)stream);
+}
+
 int fov_conv2d_dilated_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, const float* w, const float* b,
                            const float* add, float* y, int B, int H, int W, int C, int N, int kh, int kw, int dilation, int activation,
                            fov_stream_t stream) {

@@ -130,6 +130,11 @@ int convlstm_gates(const float* z, float* c, float* h, long ldh, long rows, int 
 bool conv_patch_shape_ok(const float* x, long ldx, long ldb, int B, int H, int W, int C, int N, int kh, int kw);
 int launch_conv_patch(const float* x, long ldx, long ldb, const float* w, const float* bias, const float* add, float* y, int B, int H,
                       int W, int C, int N, int kh, int kw, int act, hipStream_t stream);
+// the same convolution with bf16 matrix-core operands on weights packed once (conv_patch_bf16.hip): inference of the ConvLSTM head
+size_t conv2d_bf16_packed_bytes(int C, int N, int kh, int kw);
+int conv2d_pack_bf16(const float* w, void* packed, int C, int N, int kh, int kw, hipStream_t stream);
+int conv2d_fwd_bf16(const float* x, long ldx, long ldb, const void* w_packed, const float* bias, float* y, int B, int H, int W, int C,
+                    int N, int kh, int kw, int act, hipStream_t stream);
 bool cell_patch_shape_ok(const float* x, long ldx, long ldb, int C, const float* h_prev, long ldx2, long ldb2, int F, int H, int W,
                          int kh, int kw);
 int launch_cell_patch(const float* x, long ldx, long ldb, int C, const float* h_prev, long ldx2, long ldb2, const float* w,

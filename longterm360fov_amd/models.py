@@ -1344,6 +1344,9 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
       head 'conv1d' (xyz mode, (1,30,3) "images"): Conv1D k=7 512 -> 1024 -> 3, relu, relu, softmax
       head 'dense'  (cfg.predict_mean_var with cfg.input_mean_var, 1x1 maps of 6 channels, :171,225-227,272-273):
                     Flatten + Dense(6, linear), output (N,T_out,6) fed back as the next 1x1x6 input map
+    dtype 'bf16' (heads 'conv2d' / 'conv1d', inference only): the three head convolutions run with bf16 matrix-core operands
+    and fp32 accumulation (ops.conv2d_bf16) on weights packed once per set of weights; the ConvLSTM cells, the softmax, all
+    stored tensors and the weights the model holds stay fp32.  Train an fp32 model and hand its get_weights() to a bf16 one.
     predict([encoder_input (N,T_in,H,W,C), decoder_input (N,1,H,W,C)]) -> (N,T_out,H,W,C_out).
     compile('RMSprop', loss=costfunc._mse | 'mean_squared_error') / fit / train_on_batch train the same unrolled
     graph (convlstm_seq2seq.py:287,396-420) through training.ConvLSTMTrainer, with Keras's per-gate input
@@ -1354,8 +1357,13 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
     _default_optimizer = "rmsprop"      # convlstm_seq2seq.py:287
 
     def __init__(self, weights, head="conv2d", recurrent_activation="hard_sigmoid", device="cuda", dropout_rate=0.0,
-                 add_xyz_sum1=None, dilation_rate=None):
+                 add_xyz_sum1=None, dilation_rate=None, dtype="f32"):
         from .training import convlstm_weight_order
+        if dtype not in ("f32", "bf16"):
+            raise ValueError("dtype must be 'f32' or 'bf16'")
+        if dtype == "bf16" and head == "dense":
+            raise ValueError("dtype='bf16' needs a convolutional head ('conv2d' / 'conv1d'): the 'dense' head is one small Dense")
+        self.dtype = dtype
         self.add_xyz_sum1 = bool(cfg.add_xyz_sum1 if add_xyz_sum1 is None else add_xyz_sum1)
         # cfg.dilation_rate (config.py:105) -> the six ConvLSTM2D layers' input convolutions (:102,110,120,148,155,162)
         self.dilation_rate = int(cfg.dilation_rate if dilation_rate is None else dilation_rate)
@@ -1378,6 +1386,9 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         self._trainer = None
 
     def _make_trainer(self, optimizer):
+        if self.dtype == "bf16":
+            raise NotImplementedError("ConvLSTMSeq2Seq(dtype='bf16') is inference only: train a dtype='f32' model and hand its "
+                                      "get_weights() to a bf16 one")
         from .training import ConvLSTMTrainer
         return ConvLSTMTrainer(self._w, head=self.head, act=self.act, optimizer=optimizer, lr=self._lr, device=self.device,
                                dropout_rate=self.dropout_rate, add_xyz_sum1=self.add_xyz_sum1, loss=self.loss or "mse",
@@ -1412,6 +1423,9 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                     if pad:   # zero weight rows for the zero channels the input map is padded with (16-byte pixel gather)
                         K = torch.cat([K, torch.zeros(K.shape[:2] + (pad, K.shape[3]), dtype=K.dtype, device=K.device)], 2)
                     self._dw["%s%d_KR" % (side, l)] = torch.cat([K, R], 2).contiguous()
+            if self.dtype == "bf16":        # the head's kernels as bf16 in fragment order: rebuilt whenever _dw is dropped
+                for i in range(3):
+                    self._dw["head%d_P" % i] = ops.conv2d_pack_bf16(self._dw["head%d_W" % i])
         dw, act = self._dw, self.act
         filters = [dw["enc%d_R" % l].shape[2] for l in range(3)]
         cat = sum(filters)
@@ -1464,9 +1478,15 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                 else:
                     inp = y.reshape(B, 1, 1, 6)
                 continue
-            y = ops.conv2d(feat, dw["head0_W"], dw["head0_b"], activation="relu")
-            y = ops.conv2d(y, dw["head1_W"], dw["head1_b"], activation="relu")
-            y = ops.conv2d(y, dw["head2_W"], dw["head2_b"], activation="relu" if self.head == "conv2d" else None)
+            last = "relu" if self.head == "conv2d" else None
+            if self.dtype == "bf16":
+                y = ops.conv2d_bf16(feat, dw["head0_W"], dw["head0_b"], activation="relu", packed=dw["head0_P"])
+                y = ops.conv2d_bf16(y, dw["head1_W"], dw["head1_b"], activation="relu", packed=dw["head1_P"])
+                y = ops.conv2d_bf16(y, dw["head2_W"], dw["head2_b"], activation=last, packed=dw["head2_P"])
+            else:
+                y = ops.conv2d(feat, dw["head0_W"], dw["head0_b"], activation="relu")
+                y = ops.conv2d(y, dw["head1_W"], dw["head1_b"], activation="relu")
+                y = ops.conv2d(y, dw["head2_W"], dw["head2_b"], activation=last)
             y = ops.softmax_lastdim(y)
             out[:, t] = y
             if pad:

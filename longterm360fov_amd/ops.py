@@ -1115,6 +1115,42 @@ def conv2d(x, w, b=None, add=None, activation=None, out=None, in_channels=None, 
     return y
 
 
+def conv2d_pack_bf16(w):
+    """The fp32 (kh,kw,C,N) kernel rounded to bf16 (round-to-nearest-even) in the order conv2d_bf16's kernels read it:
+    a device byte tensor of fov_conv2d_bf16_packed_bytes.  Pack once per set of weights; the layout is the library's own."""
+    w = _dev(w, "w")
+    assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous()
+    kh, kw, C, N = w.shape
+    L = _lib.lib()
+    packed = torch.empty((int(L.fov_conv2d_bf16_packed_bytes(C, N, kh, kw)),), dtype=torch.uint8, device=w.device)
+    check(L.fov_conv2d_pack_bf16(_ptr(w), _ptr(packed), C, N, kh, kw, _stream()))
+    return packed
+
+
+def conv2d_bf16(x, w, b=None, activation=None, out=None, packed=None):
+    """y (B,H,W,N) = act(conv2d_same(bf16(x), bf16(w)) + b): both operands of every product rounded to bf16, fp32
+    accumulation, bias / relu / y in fp32 (inference of the ConvLSTM head).  x as in conv2d (channel-slice views allowed);
+    w the fp32 (kh,kw,C,N) kernel - it gives the shape -, packed = conv2d_pack_bf16(w) when the caller keeps it (without
+    it the call packs first)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(3) == 1
+    B, H, W, C = x.shape
+    ldx = x.stride(2)
+    ldb = x.stride(0) if B > 1 else H * W * ldx
+    assert x.stride(1) == W * ldx and ldb >= H * W * ldx, "x must be NHWC with a uniform pixel stride"
+    w = _dev(w, "w")
+    kh, kw, Cw, N = w.shape
+    assert Cw == C
+    L = _lib.lib()
+    if packed is None:
+        packed = conv2d_pack_bf16(w)
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.numel() == L.fov_conv2d_bf16_packed_bytes(C, N, kh, kw)
+    y = torch.empty((B, H, W, N), dtype=torch.float32, device=x.device) if out is None else out
+    act = {None: 0, "linear": 0, "relu": 2}[activation]
+    check(L.fov_conv2d_fwd_bf16(x.data_ptr(), ldx, ldb, _ptr(packed), _ptr(_dev(b, "b")), _ptr(y), B, H, W, C, N, kh, kw, act,
+                                _stream()))
+    return y
+
+
 def conv2d_cat(x1, x2, w, b=None, activation=None, out=None):
     """y = act(conv2d_same([x1 | x2], w) + b): convolution over the channel concatenation of two NHWC maps (each may
     be a channel-slice / batch-strided view) without materialising it; w (kh,kw,C1+C2,N)."""
