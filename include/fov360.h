@@ -653,7 +653,9 @@ int fov_guard_flag(const void* guard0, const void* guard1, const void* guard2, f
 /* =======================================================================================
  * ConvLSTM2D seq2seq building blocks (a8/a9) - mycode/convlstm_seq2seq.py:100-126,146-165 (ConvLSTM2D),
  * :170-189,224-258 (Conv2D / Conv1D heads, channel Softmax).  NHWC activations, Keras kernel layout
- * (kh,kw,C,N), zero 'same' padding, stride 1, dilation 1, odd kernel sizes.
+ * (kh,kw,C,N), zero 'same' padding, stride 1, dilation 1, odd kernel sizes.  The inference forms with bf16 matrix-core
+ * operands - fov_conv2d_fwd_bf16 (the head) and fov_convlstm_cell_fwd_bf16 (the cells) - take weights packed once by
+ * their fov_*_pack_bf16; everything they read or store besides is the fp32 tensor of the fp32 entry point.
  * ===================================================================================== */
 
 /* y (B,H,W,N) = act(conv2d_same(x, w) + b + add);  x may be strided: x_pixel_stride >= C floats (a layer can
@@ -704,6 +706,31 @@ int fov_convlstm_cell_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batc
                           const float* w, const float* b, const float* c_prev, float* c_new,
                           float* h, int64_t h_pixel_stride, float* gates,
                           int B, int H, int W, int F, int kh, int kw, int recurrent_activation, fov_stream_t stream);
+
+/* fov_convlstm_cell_fwd with bf16 matrix-core operands - inference of the six ConvLSTM2D layers
+ * (convlstm_seq2seq.py:100-126,146-165).  Arithmetic contract:
+ *     z = conv_same(bf16([x_t | h_prev]), bf16([K ; R])) + b
+ *     i,f,o = recurrent_activation(z_i, z_f, z_o);  g = tanh(z_c)
+ *     c_new = f * c_prev + i * g;  h = o * tanh(c_new)
+ * both operands of every product rounded to bf16 round-to-nearest-even, products accumulated in fp32 in an order the
+ * kernel chooses; bias, gates and cell update in fp32 with the activations fov_convlstm_cell_fwd uses; c_new, h and the
+ * optional activated-gates tape stored fp32 - h is rounded only where a later product takes it as an operand, so every
+ * other consumer of h sees fp32.  Stride 1, 'same' zero padding, odd kh, kw, dilation 1.  The weights are constant across
+ * a predict call, so they are packed ONCE: fov_convlstm_cell_pack_bf16 writes fov_convlstm_cell_bf16_packed_bytes(Ctot, F,
+ * kh, kw) bytes (16-byte aligned, caller-owned device memory) from the fp32 (kh,kw,Ctot,4F) stack [K ; R], Ctot = C + F
+ * (or from K alone, Ctot = C, for the zero state); the layout is private to the library and depends on (Ctot, F, kh, kw)
+ * only. */
+size_t fov_convlstm_cell_bf16_packed_bytes(int Ctot, int F, int kh, int kw);
+/* convlstm_seq2seq.py:100-126,146-165: a cell's kernels, rounded and reordered for fov_convlstm_cell_fwd_bf16. */
+int fov_convlstm_cell_pack_bf16(const float* w, void* packed, int Ctot, int F, int kh, int kw, fov_stream_t stream);
+/* convlstm_seq2seq.py:100-126,146-165: the parameters and aliasing rules of fov_convlstm_cell_fwd, with w_packed - what
+ * fov_convlstm_cell_pack_bf16 wrote for (C + F, F, kh, kw), or for (C, F, kh, kw) when h_prev is NULL - in place of w.
+ * c_prev NULL is the zero state.  The empty batch is FOV_OK; operands beyond 2 GiB are FOV_ERR_UNSUPPORTED. */
+int fov_convlstm_cell_fwd_bf16(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, int C,
+                               const float* h_prev, int64_t h_prev_pixel_stride, int64_t h_prev_batch_stride,
+                               const void* w_packed, const float* b, const float* c_prev, float* c_new,
+                               float* h, int64_t h_pixel_stride, float* gates,
+                               int B, int H, int W, int F, int kh, int kw, int recurrent_activation, fov_stream_t stream);
 
 /* ConvLSTM2DCell gates on z (rows, 4F) = conv(x,K)+b+conv(h,R), channel blocks i,f,c,o; c (rows,F) is
  * updated in place; h is written with pixel stride h_pixel_stride >= F. */

@@ -107,6 +107,9 @@ SIGNATURES = {
     "fov_rmsprop_step_guarded": (_I, [_P] * 3 + [ctypes.c_int64] + [ctypes.c_float] * 3 + [_P] * 5),
     "fov_conv2d_fwd": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "fov_convlstm_cell_fwd": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _I, _P, ctypes.c_int64, ctypes.c_int64] + [_P] * 5 + [ctypes.c_int64, _P] + [_I] * 7 + [_P]),
+    "fov_convlstm_cell_bf16_packed_bytes": (ctypes.c_size_t, [_I] * 4),
+    "fov_convlstm_cell_pack_bf16": (_I, [_P, _P] + [_I] * 4 + [_P]),
+    "fov_convlstm_cell_fwd_bf16": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _I, _P, ctypes.c_int64, ctypes.c_int64] + [_P] * 5 + [ctypes.c_int64, _P] + [_I] * 7 + [_P]),
     "fov_conv2d_bf16_packed_bytes": (ctypes.c_size_t, [_I] * 4),
     "fov_conv2d_pack_bf16": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "fov_conv2d_fwd_bf16": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P] + [_I] * 8 + [_P]),

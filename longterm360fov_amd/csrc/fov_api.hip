@@ -1614,6 +1614,40 @@ int fov_convlstm_cell_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batc
                              recurrent_activation, (hipStream_t)stream);
 }
 
+size_t fov_convlstm_cell_bf16_packed_bytes(int Ctot, int F, int kh, int kw) {
+    if (Ctot <= 0 || F <= 0 || kh <= 0 || kw <= 0) return 0;
+    return convlstm_cell_bf16_packed_bytes(Ctot, F, kh, kw);
+}
+
+int fov_convlstm_cell_pack_bf16(const float* w, void* packed, int Ctot, int F, int kh, int kw, fov_stream_t stream) {
+    if (!w || !packed || (((uintptr_t)packed) & 15) || Ctot <= 0 || F <= 0 || kh <= 0 || kw <= 0 || (kh & 1) == 0 || (kw & 1) == 0) {
+        set_error("fov_convlstm_cell_pack_bf16: invalid argument (odd kernel sizes only, packed 16-byte aligned)");
+        return FOV_ERR_INVALID;
+    }
+    if (convlstm_cell_bf16_packed_bytes(Ctot, F, kh, kw) >= ((size_t)1 << 31) || (int64_t)kh * kw * Ctot * 4 * F * 4 >= ((int64_t)1 << 31)) {
+        set_error("fov_convlstm_cell_pack_bf16: operand larger than 2 GiB");
+        return FOV_ERR_UNSUPPORTED;
+    }
+    return convlstm_cell_pack_bf16(w, packed, Ctot, F, kh, kw, (hipStream_t)stream);
+}
+
+int fov_convlstm_cell_fwd_bf16(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, int C, const float* h_prev,
+                               int64_t h_prev_pixel_stride, int64_t h_prev_batch_stride, const void* w_packed, const float* b,
+                               const float* c_prev, float* c_new, float* h, int64_t h_pixel_stride, float* gates, int B, int H, int W,
+                               int F, int kh, int kw, int recurrent_activation, fov_stream_t stream) {
+    if (B < 0 || H <= 0 || W <= 0 || C <= 0 || F <= 0 || kh <= 0 || kw <= 0 || !(kh & 1) || !(kw & 1) || !w_packed ||
+        (((uintptr_t)w_packed) & 15) || (B > 0 && (!x || !c_new || !h)) || x_pixel_stride < C ||
+        x_batch_stride < (int64_t)H * W * x_pixel_stride || h_pixel_stride < F ||
+        (h_prev && (h_prev_pixel_stride < F || h_prev_batch_stride < (int64_t)H * W * h_prev_pixel_stride || h_prev == h)) ||
+        (recurrent_activation != FOV_ACT_SIGMOID && recurrent_activation != FOV_ACT_HARD_SIGMOID)) {
+        set_error("fov_convlstm_cell_fwd_bf16: invalid argument (odd kernel sizes only, w_packed 16-byte aligned)");
+        return FOV_ERR_INVALID;
+    }
+    return convlstm_cell_fwd_bf16(x, (long)x_pixel_stride, (long)x_batch_stride, C, h_prev, (long)h_prev_pixel_stride,
+                                  (long)h_prev_batch_stride, w_packed, b, c_prev, c_new, h, (long)h_pixel_stride, gates, B, H, W, F,
+                                  kh, kw, recurrent_activation, (hipStream_t)stream);
+}
+
 int fov_convlstm_cell_dilated_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, int C, const float* h_prev,
                                   int64_t h_prev_pixel_stride, int64_t h_prev_batch_stride, const float* w, const float* b,
                                   const float* c_prev, float* c_new, float* h, int64_t h_pixel_stride, float* gates, int B, int H, int W,

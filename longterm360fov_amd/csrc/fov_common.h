@@ -135,6 +135,12 @@ size_t conv2d_bf16_packed_bytes(int C, int N, int kh, int kw);
 int conv2d_pack_bf16(const float* w, void* packed, int C, int N, int kh, int kw, hipStream_t stream);
 int conv2d_fwd_bf16(const float* x, long ldx, long ldb, const void* w_packed, const float* bias, float* y, int B, int H, int W, int C,
                     int N, int kh, int kw, int act, hipStream_t stream);
+// one ConvLSTM2D step with bf16 matrix-core operands on weights packed once (convlstm_patch_bf16.hip): inference of the ConvLSTM cells
+size_t convlstm_cell_bf16_packed_bytes(int Ctot, int F, int kh, int kw);
+int convlstm_cell_pack_bf16(const float* w, void* packed, int Ctot, int F, int kh, int kw, hipStream_t stream);
+int convlstm_cell_fwd_bf16(const float* x, long ldx, long ldb, int C, const float* h_prev, long ldx2, long ldb2, const void* w_packed,
+                           const float* bias, const float* c_prev, float* c_new, float* h, long ldh, float* gates, int B, int H, int W,
+                           int F, int kh, int kw, int act, hipStream_t stream);
 bool cell_patch_shape_ok(const float* x, long ldx, long ldb, int C, const float* h_prev, long ldx2, long ldb2, int F, int H, int W,
                          int kh, int kw);
 int launch_cell_patch(const float* x, long ldx, long ldb, int C, const float* h_prev, long ldx2, long ldb2, const float* w,

@@ -1347,6 +1347,9 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
     dtype 'bf16' (heads 'conv2d' / 'conv1d', inference only): the three head convolutions run with bf16 matrix-core operands
     and fp32 accumulation (ops.conv2d_bf16) on weights packed once per set of weights; the ConvLSTM cells, the softmax, all
     stored tensors and the weights the model holds stay fp32.  Train an fp32 model and hand its get_weights() to a bf16 one.
+    cell_dtype 'bf16' (every head, inference only, dilation_rate 1; independent of dtype): the six ConvLSTM2D layers run with
+    bf16 matrix-core operands and fp32 accumulation (ops.convlstm_cell_bf16) on [K ; R] stacks packed once per set of weights;
+    gates, cell update, h, c and every other consumer of h stay fp32.
     predict([encoder_input (N,T_in,H,W,C), decoder_input (N,1,H,W,C)]) -> (N,T_out,H,W,C_out).
     compile('RMSprop', loss=costfunc._mse | 'mean_squared_error') / fit / train_on_batch train the same unrolled
     graph (convlstm_seq2seq.py:287,396-420) through training.ConvLSTMTrainer, with Keras's per-gate input
@@ -1357,18 +1360,22 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
     _default_optimizer = "rmsprop"      # convlstm_seq2seq.py:287
 
     def __init__(self, weights, head="conv2d", recurrent_activation="hard_sigmoid", device="cuda", dropout_rate=0.0,
-                 add_xyz_sum1=None, dilation_rate=None, dtype="f32"):
+                 add_xyz_sum1=None, dilation_rate=None, dtype="f32", cell_dtype="f32"):
         from .training import convlstm_weight_order
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
+        if cell_dtype not in ("f32", "bf16"):
+            raise ValueError("cell_dtype must be 'f32' or 'bf16'")
         if dtype == "bf16" and head == "dense":
             raise ValueError("dtype='bf16' needs a convolutional head ('conv2d' / 'conv1d'): the 'dense' head is one small Dense")
-        self.dtype = dtype
+        self.dtype, self.cell_dtype = dtype, cell_dtype
         self.add_xyz_sum1 = bool(cfg.add_xyz_sum1 if add_xyz_sum1 is None else add_xyz_sum1)
         # cfg.dilation_rate (config.py:105) -> the six ConvLSTM2D layers' input convolutions (:102,110,120,148,155,162)
         self.dilation_rate = int(cfg.dilation_rate if dilation_rate is None else dilation_rate)
         if self.dilation_rate < 1:
             raise ValueError("dilation_rate must be >= 1")
+        if cell_dtype == "bf16" and self.dilation_rate > 1:
+            raise ValueError("cell_dtype='bf16' needs dilation_rate 1: the bf16 cell has no dilated form")
         self.head, self.act = head, recurrent_activation
         self._w = {k: _as_f32(v) for k, v in weights.items()}
         self._init_surface(convlstm_weight_order(self._w), None, device)
@@ -1389,6 +1396,9 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         if self.dtype == "bf16":
             raise NotImplementedError("ConvLSTMSeq2Seq(dtype='bf16') is inference only: train a dtype='f32' model and hand its "
                                       "get_weights() to a bf16 one")
+        if self.cell_dtype == "bf16":
+            raise NotImplementedError("ConvLSTMSeq2Seq(cell_dtype='bf16') is inference only: train a cell_dtype='f32' model and "
+                                      "hand its get_weights() to a bf16 one")
         from .training import ConvLSTMTrainer
         return ConvLSTMTrainer(self._w, head=self.head, act=self.act, optimizer=optimizer, lr=self._lr, device=self.device,
                                dropout_rate=self.dropout_rate, add_xyz_sum1=self.add_xyz_sum1, loss=self.loss or "mse",
@@ -1426,7 +1436,17 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             if self.dtype == "bf16":        # the head's kernels as bf16 in fragment order: rebuilt whenever _dw is dropped
                 for i in range(3):
                     self._dw["head%d_P" % i] = ops.conv2d_pack_bf16(self._dw["head%d_W" % i])
+            if self.cell_dtype == "bf16":   # the cells' [K ; R] stacks likewise
+                for side in ("enc", "dec"):
+                    for l in range(3):
+                        self._dw["%s%d_P" % (side, l)] = ops.convlstm_cell_pack_bf16(self._dw["%s%d_KR" % (side, l)])
         dw, act = self._dw, self.act
+        if self.cell_dtype == "bf16":
+            cell = lambda x, h, name, c, h_out: ops.convlstm_cell_bf16(x, h, dw[name + "_KR"], dw[name + "_b"], c, h_out, act,
+                                                                       packed=dw[name + "_P"])
+        else:
+            cell = lambda x, h, name, c, h_out: ops.convlstm_cell(x, h, dw[name + "_KR"], dw[name + "_b"], c, h_out, act,
+                                                                  dilation=self.dilation_rate)
         filters = [dw["enc%d_R" % l].shape[2] for l in range(3)]
         cat = sum(filters)
         offs = [0, filters[0], filters[0] + filters[1]]
@@ -1448,12 +1468,11 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         for l, F in enumerate(filters):
             h = torch.zeros((B, H, W, F), dtype=torch.float32, device=self.device)
             c = torch.zeros((B, H, W, F), dtype=torch.float32, device=self.device)
-            KR, b = dw["enc%d_KR" % l], dw["enc%d_b" % l]
             nxt = []
             for t in range(T_in):
                 hn = e4(B, H, W, F)
                 # conv(x_t, K) + conv(h, R) + b, gates, c / h update: one launch
-                ops.convlstm_cell(seq[t], h, KR, b, c, hn, act, dilation=self.dilation_rate)
+                cell(seq[t], h, "enc%d" % l, c, hn)
                 h = hn
                 nxt.append(h)
             seq = nxt
@@ -1466,8 +1485,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             cur = inp
             for l, F in enumerate(filters):
                 hslot = feat[..., offs[l]:offs[l] + F]
-                ops.convlstm_cell(cur, states[l][0], dw["dec%d_KR" % l], dw["dec%d_b" % l], states[l][1], hslot, act,
-                                  dilation=self.dilation_rate)
+                cell(cur, states[l][0], "dec%d" % l, states[l][1], hslot)
                 states[l][0] = hslot
                 cur = hslot
             if dense_head:   # Flatten + Dense(6): cfg.predict_mean_var, output fed back as a 1x1x6 map

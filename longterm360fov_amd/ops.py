@@ -1221,6 +1221,63 @@ def convlstm_cell(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new=None
     return h_out, c_new
 
 
+def convlstm_cell_pack_bf16(w):
+    """The fp32 (kh,kw,Ctot,4F) stack [K ; R] of a ConvLSTM2D cell (or K alone, for the zero state) rounded to bf16
+    (round-to-nearest-even) in the order convlstm_cell_bf16's kernels read it: a device byte tensor of
+    fov_convlstm_cell_bf16_packed_bytes.  Pack once per set of weights; the layout is the library's own."""
+    w = _dev(w, "w")
+    assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous() and w.shape[3] % 4 == 0
+    kh, kw, Ctot, N = w.shape
+    L = _lib.lib()
+    packed = torch.empty((int(L.fov_convlstm_cell_bf16_packed_bytes(Ctot, N // 4, kh, kw)),), dtype=torch.uint8, device=w.device)
+    check(L.fov_convlstm_cell_pack_bf16(_ptr(w), _ptr(packed), Ctot, N // 4, kh, kw, _stream()))
+    return packed
+
+
+def convlstm_cell_bf16(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new=None, gates=None, packed=None):
+    """convlstm_cell with bf16 matrix-core operands: z = conv_same(bf16([x | h_prev]), bf16([K ; R])) + b with fp32
+    accumulation; bias, gates, cell update and everything stored in fp32 (inference of the ConvLSTM cells) -> (h_out, c_new).
+    The arguments of convlstm_cell (no dilation); w the fp32 (kh,kw,C+F,4F) stack - it gives the shape -, packed =
+    convlstm_cell_pack_bf16(w) when the caller keeps it (without it the call packs first)."""
+    def geom(t):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
+        B, H, W, C = t.shape
+        ldx = t.stride(2)
+        ldb = t.stride(0) if B > 1 else H * W * ldx
+        assert t.stride(1) == W * ldx and ldb >= H * W * ldx, "NHWC with a uniform pixel stride"
+        return B, H, W, C, ldx, ldb
+    B, H, W, C, ldx, ldb = geom(x)
+    w = _dev(w, "w")
+    kh, kw, Cw, N = w.shape
+    F = N // 4
+    assert N == 4 * F
+    ldx2 = ldb2 = 0
+    if h_prev is not None:
+        B2, H2, W2, F2, ldx2, ldb2 = geom(h_prev)
+        assert (B2, H2, W2, F2) == (B, H, W, F) and Cw == C + F
+    else:
+        assert Cw == C
+    L = _lib.lib()
+    if packed is None:
+        packed = convlstm_cell_pack_bf16(w)
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.numel() == L.fov_convlstm_cell_bf16_packed_bytes(Cw, F, kh, kw)
+    c_prev = _dev(c_prev, "c_prev")
+    if c_new is None:
+        c_new = c_prev if c_prev is not None else torch.empty((B, H, W, F), dtype=torch.float32, device=x.device)
+    c_new = _dev(c_new, "c_new")
+    assert c_new.shape == (B, H, W, F) and (c_prev is None or c_prev.shape == c_new.shape)
+    assert h_out.is_cuda and h_out.dtype == torch.float32 and h_out.stride(-1) == 1 and h_out.shape == c_new.shape
+    assert h_out.stride(1) == W * h_out.stride(2) and (B == 1 or h_out.stride(0) == H * W * h_out.stride(2)), "h_out: uniform pixel stride"
+    if gates is not None:
+        gates = _dev(gates, "gates")
+        assert gates.shape == (B, H, W, N)
+    _sync_env()
+    check(L.fov_convlstm_cell_fwd_bf16(x.data_ptr(), ldx, ldb, C, h_prev.data_ptr() if h_prev is not None else None, ldx2, ldb2,
+                                       _ptr(packed), _ptr(_dev(b, "b")), _ptr(c_prev), _ptr(c_new), h_out.data_ptr(),
+                                       h_out.stride(-2), _ptr(gates), B, H, W, F, kh, kw, act_code(act), _stream()))
+    return h_out, c_new
+
+
 def convlstm_gates(z, c, h_out, act="hard_sigmoid"):
     """Gates + cell update: z (B,H,W,4F), c (B,H,W,F) updated in place, h written into h_out, which may be
     a channel-slice view of a concatenated feature map."""
