@@ -350,12 +350,6 @@ __global__ __launch_bounds__(256) void softmax_lastdim_kernel(const float* __res
     for (int i = 0; i < n; ++i) yp[i] = __expf(xp[i] - mx) * inv;
 }
 
-static int conv_check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
-}
-
 int conv2d_fwd(const float* x, long ldx, long ldb, const float* w, const float* bias, const float* add, float* y, int B, int H,
                int W, int C, int N, int kh, int kw, int act, hipStream_t stream, int dil) {
     return conv2d_fwd2(x, ldx, ldb, C, nullptr, 0, 0, 0, w, bias, add, y, B, H, W, N, kh, kw, act, stream, dil);
@@ -371,12 +365,7 @@ int conv2d_fwd2(const float* x, long ldx, long ldb, int C, const float* x2, long
     g.x2 = x2; g.C2 = x2 ? C2 : 0; g.ldx2 = ldx2; g.ldb2 = ldb2;
     const long M = (long)B * H * W;
     if (M == 0 || N == 0) return FOV_OK;
-    // 31-bit byte offsets inside one buffer descriptor
-    if ((long)B * ldb * 4 >= (1L << 31) || (x2 && (long)B * ldb2 * 4 >= (1L << 31)) ||
-        (long)kh * kw * (C + g.C2) * N * 4 >= (1L << 31)) {
-        set_error("conv2d: operand larger than 2 GiB");
-        return FOV_ERR_UNSUPPORTED;
-    }
+    if (!operand_fits_31bit("conv2d", B, ldb, x2, ldb2, (long)kh * kw * (C + g.C2) * N * 4)) return FOV_ERR_UNSUPPORTED;
     // one input segment, a map small enough to sit in LDS, enough channels to be worth it: the map-resident form (conv_patch.hip)
     if (!x2 && g.dil == 1 && conv_patch_shape_ok(x, ldx, ldb, B, H, W, C, N, kh, kw))
         return launch_conv_patch(x, ldx, ldb, w, bias, add, y, B, H, W, C, N, kh, kw, act, stream);
@@ -401,7 +390,7 @@ int conv2d_fwd2(const float* x, long ldx, long ldb, int C, const float* x2, long
         FOV_CONV_LAUNCH(4, 4, 2, grid);
     }
 #undef FOV_CONV_LAUNCH
-    return conv_check_launch("conv2d_igemm");
+    return launch_check("conv2d_igemm");
 }
 
 // One ConvLSTM2D step: h, c <- cell(conv([x | h_prev], [K ; R]) + b, c_prev).  h_prev may be NULL (zero state: w then holds
@@ -416,11 +405,7 @@ int convlstm_cell_fwd(const float* x, long ldx, long ldb, int C, const float* h_
     g.c_prev = c_prev; g.c_new = c_new; g.h = h; g.ldh = ldh; g.gates = gates;
     const long M = (long)B * H * W;
     if (M == 0 || F == 0) return FOV_OK;
-    if ((long)B * ldb * 4 >= (1L << 31) || (h_prev && (long)B * ldb2 * 4 >= (1L << 31)) ||
-        (long)kh * kw * (C + g.C2) * 4 * F * 4 >= (1L << 31)) {
-        set_error("convlstm_cell: operand larger than 2 GiB");
-        return FOV_ERR_UNSUPPORTED;
-    }
+    if (!operand_fits_31bit("convlstm_cell", B, ldb, h_prev, ldb2, (long)kh * kw * (C + g.C2) * 4 * F * 4)) return FOV_ERR_UNSUPPORTED;
     // the LDS-resident-patch form (convlstm_patch.hip): every tap reads the same staged patch, no barrier in the k loop
     if (g.dil == 1 && cell_patch_shape_ok(x, ldx, ldb, C, h_prev, ldx2, ldb2, F, H, W, kh, kw))
         return launch_cell_patch(x, ldx, ldb, C, h_prev, ldx2, ldb2, w, bias, c_prev, c_new, h, ldh, gates, B, H, W, F, kh, kw, act, stream);
@@ -452,7 +437,7 @@ int convlstm_cell_fwd(const float* x, long ldx, long ldb, int C, const float* h_
     else FOV_CELL_SHAPES(FOV_ACT_SIGMOID);
 #undef FOV_CELL_SHAPES
 #undef FOV_CELL_LAUNCH
-    return conv_check_launch("convlstm_cell");
+    return launch_check("convlstm_cell");
 }
 
 int convlstm_gates(const float* z, float* c, float* h, long ldh, long rows, int F, int act, hipStream_t stream) {
@@ -463,13 +448,13 @@ int convlstm_gates(const float* z, float* c, float* h, long ldh, long rows, int 
         hipLaunchKernelGGL(convlstm_gates_kernel<FOV_ACT_HARD_SIGMOID>, grid, dim3(256), 0, stream, z, c, h, ldh, rows, F);
     else
         hipLaunchKernelGGL(convlstm_gates_kernel<FOV_ACT_SIGMOID>, grid, dim3(256), 0, stream, z, c, h, ldh, rows, F);
-    return conv_check_launch("convlstm_gates");
+    return launch_check("convlstm_gates");
 }
 
 int softmax_lastdim(const float* x, float* y, long rows, int n, hipStream_t stream) {
     if (rows == 0) return FOV_OK;
     hipLaunchKernelGGL(softmax_lastdim_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, x, y, rows, n);
-    return conv_check_launch("softmax_lastdim");
+    return launch_check("softmax_lastdim");
 }
 
 }  // namespace fov

@@ -273,9 +273,7 @@ int launch_conv_patch(const float* x, long ldx, long ldb, const float* w, const 
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.nblocks * B)), dim3(256), lds, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("conv2d_patch launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("conv2d_patch");
 }
 
 }  // namespace fov

@@ -325,25 +325,19 @@ int conv2d_pack_bf16(const float* w, void* packed, int C, int N, int kh, int kw,
     const long total = (long)kh * kw * nkb * ntl * 64;
     hipLaunchKernelGGL(conv2d_pack_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (qu32x4*)packed, C, N,
                        nkb, ntl, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("conv2d_pack_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("conv2d_pack_bf16");
 }
 
 int conv2d_fwd_bf16(const float* x, long ldx, long ldb, const void* w_packed, const float* bias, float* y, int B, int H, int W, int C,
                     int N, int kh, int kw, int act, hipStream_t stream) {
     const long M = (long)B * H * W;
     if (M == 0 || N == 0) return FOV_OK;
-    // 31-bit byte offsets inside one buffer descriptor
-    if ((long)B * ldb * 4 >= (1L << 31) || conv2d_bf16_packed_bytes(C, N, kh, kw) >= ((size_t)1 << 31) || (M + 15) / 16 >= (1L << 31)) {
-        set_error("conv2d_bf16: operand larger than 2 GiB");
+    if (!operand_fits_31bit("conv2d_bf16", B, ldb, nullptr, 0, (long)conv2d_bf16_packed_bytes(C, N, kh, kw), (M + 15) / 16))
         return FOV_ERR_UNSUPPORTED;
-    }
     ConvBf16Args g = {};
     g.x = x; g.wp = w_packed; g.bias = bias; g.y = y; g.ldx = ldx; g.ldb = ldb;
     g.B = B; g.H = H; g.W = W; g.C = C; g.N = N; g.kh = kh; g.kw = kw; g.act = act;
     g.nkb = pb_nkb(C); g.ntl = pb_ntl(N);
-    hipError_t e;
     if (patch_bf16_shape_ok(x, ldx, ldb, B, H, W, C, N, kh, kw)) {
         g.per = W / gcd_b(16, W);
         g.rs = 16 * g.per / W;
@@ -357,14 +351,10 @@ int conv2d_fwd_bf16(const float* x, long ldx, long ldb, const void* w_packed, co
         int rc = ensure_dynamic_lds((const void*)kern, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks * B)), dim3(256), lds, stream, g);
-        e = hipGetLastError();
-        if (e != hipSuccess) { set_error("conv2d_patch_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-        return FOV_OK;
+        return launch_check("conv2d_patch_bf16");
     }
     hipLaunchKernelGGL(conv2d_plain_bf16_kernel, dim3((unsigned)((M + 15) / 16), (unsigned)((g.ntl + 3) / 4)), dim3(256), 0, stream, g);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error("conv2d_plain_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("conv2d_plain_bf16");
 }
 
 }  // namespace fov

@@ -294,12 +294,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs g) {
             }
 }
 
-static int ct_check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
-}
-
 size_t conv2d_wgrad_workspace_floats(int C, int N, int kh, int kw) {
     // up to 64 split-K slices; narrow layers (conv_wgrad_lines.hip splits over the maps): up to 256 slices within 128 MB
     const size_t wn = (size_t)kh * kw * C * N;
@@ -370,7 +364,7 @@ int conv2d_wgrad(const float* x, long ldx, const float* dz, float* dw, int B, in
     else if (variant == 3) FOV_WGRAD_LAUNCH(4, 2, 4);
     else FOV_WGRAD_LAUNCH(4, 4, 2);
 #undef FOV_WGRAD_LAUNCH
-    int rc = ct_check_launch("conv_wgrad");
+    int rc = launch_check("conv_wgrad");
     if (rc || !via_scratch) return rc;
     return splitk_reduce(scratch, dw, (long)wn, split, accumulate, stream);
 }
@@ -386,7 +380,7 @@ int convlstm_gates_train(const float* z, const float* c_prev, float* c_new, floa
     else
         hipLaunchKernelGGL(convlstm_gates_train_kernel<FOV_ACT_SIGMOID>, grid, dim3(256), 0, stream, z, c_prev, c_new, h, ldh,
                            gates, rows, F);
-    return ct_check_launch("convlstm_gates_train");
+    return launch_check("convlstm_gates_train");
 }
 
 int convlstm_gates_bwd(const float* dh, long lddh, float* dc, const float* gates, const float* c_prev, const float* c_new,
@@ -400,20 +394,20 @@ int convlstm_gates_bwd(const float* dh, long lddh, float* dc, const float* gates
     else
         hipLaunchKernelGGL(convlstm_gates_bwd_kernel<FOV_ACT_SIGMOID>, grid, dim3(256), 0, stream, dh, lddh, dc, gates, c_prev,
                            c_new, dz, rows, F);
-    return ct_check_launch("convlstm_gates_bwd");
+    return launch_check("convlstm_gates_bwd");
 }
 
 int conv_weight_transpose(const float* w, float* wt, int kh, int kw, int C, int N, hipStream_t stream) {
     const long total = (long)kh * kw * C * N;
     if (total == 0) return FOV_OK;
     hipLaunchKernelGGL(conv_weight_transpose_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, wt, kh, kw, C, N);
-    return ct_check_launch("conv_weight_transpose");
+    return launch_check("conv_weight_transpose");
 }
 
 int softmax_lastdim_bwd(const float* dp, const float* p, float* dy, long rows, int n, hipStream_t stream) {
     if (rows == 0) return FOV_OK;
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, dp, p, dy, rows, n);
-    return ct_check_launch("softmax_bwd");
+    return launch_check("softmax_bwd");
 }
 
 }  // namespace fov

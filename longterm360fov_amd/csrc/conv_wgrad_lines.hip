@@ -288,8 +288,7 @@ int conv_wgrad_lines(const float* x, long ldx, const float* dz, float* dw, int B
         else FOV_WLINES(4, 2, 3);
     }
 #undef FOV_WLINES
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("conv_wgrad_lines launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    if (int rc = launch_check("conv_wgrad_lines")) return rc;
     if (!via_scratch) return FOV_OK;
     return splitk_reduce(scratch, dw, (long)wn, (int)split, accumulate, stream);
 }

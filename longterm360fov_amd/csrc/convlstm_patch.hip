@@ -213,9 +213,7 @@ int launch_patch_t(const CellPatchArgs& g, int act, size_t lds, hipStream_t stre
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.B * g.groups)), dim3(256), lds, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("convlstm_cell_patch launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("convlstm_cell_patch");
 }
 
 }  // namespace

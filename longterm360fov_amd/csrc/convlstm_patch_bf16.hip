@@ -313,9 +313,7 @@ int launch_patch_bf16_t(const CellBf16Args& g, int act, size_t lds, hipStream_t 
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.B * g.groups)), dim3(256), lds, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("convlstm_cell_patch_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("convlstm_cell_patch_bf16");
 }
 
 }  // namespace
@@ -327,9 +325,7 @@ int convlstm_cell_pack_bf16(const float* w, void* packed, int Ctot, int F, int k
     const long total = (long)kh * kw * nkb * ntl * 64;
     hipLaunchKernelGGL(convlstm_cell_pack_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, (qu32x4*)packed,
                        Ctot, F, nkb, ntl, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("convlstm_cell_pack_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("convlstm_cell_pack_bf16");
 }
 
 // One ConvLSTM2D step on packed bf16 weights; the aliasing rules of convlstm_cell_fwd.
@@ -339,13 +335,10 @@ int convlstm_cell_fwd_bf16(const float* x, long ldx, long ldb, int C, const floa
     const long M = (long)B * H * W;
     if (M == 0 || F == 0) return FOV_OK;
     const int Ctot = C + (h_prev ? F : 0);
-    // 31-bit byte offsets inside one buffer descriptor.  The plain kernel addresses with 64-bit pointers and would not need the
-    // limit; it is applied to both forms on purpose, so that what a call accepts does not depend on the form that runs it.
-    if ((long)B * ldb * 4 >= (1L << 31) || (h_prev && (long)B * ldb2 * 4 >= (1L << 31)) ||
-        convlstm_cell_bf16_packed_bytes(Ctot, F, kh, kw) >= ((size_t)1 << 31) || (M + 15) / 16 >= (1L << 31)) {
-        set_error("convlstm_cell_bf16: operand larger than 2 GiB");
+    // The plain kernel addresses with 64-bit pointers and would not need the 31-bit limit; it is applied to both forms on
+    // purpose, so that what a call accepts does not depend on the form that runs it.
+    if (!operand_fits_31bit("convlstm_cell_bf16", B, ldb, h_prev, ldb2, (long)convlstm_cell_bf16_packed_bytes(Ctot, F, kh, kw), (M + 15) / 16))
         return FOV_ERR_UNSUPPORTED;
-    }
     CellBf16Args g = {};
     g.x = x; g.h_prev = h_prev; g.wp = w_packed; g.bias = bias; g.c_prev = c_prev; g.c_new = c_new; g.h = h; g.gates = gates;
     g.ldx = ldx; g.ldb = ldb; g.ldx2 = ldx2; g.ldb2 = ldb2; g.ldh = ldh;
@@ -364,9 +357,7 @@ int convlstm_cell_fwd_bf16(const float* x, long ldx, long ldb, int C, const floa
     const dim3 grid((unsigned)((M + 15) / 16), (unsigned)((g.ntl / 2 + 3) / 4));
     if (act == FOV_ACT_HARD_SIGMOID) hipLaunchKernelGGL(convlstm_cell_plain_bf16_kernel<FOV_ACT_HARD_SIGMOID>, grid, dim3(256), 0, stream, g);
     else hipLaunchKernelGGL(convlstm_cell_plain_bf16_kernel<FOV_ACT_SIGMOID>, grid, dim3(256), 0, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("convlstm_cell_plain_bf16 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("convlstm_cell_plain_bf16");
 }
 
 }  // namespace fov

@@ -22,6 +22,19 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long ldb2, long weight_bytes, long tiles) {
+    const long lim = 1L << 31;
+    if ((long)B * ldb * 4 < lim && (!x2 || (long)B * ldb2 * 4 < lim) && weight_bytes < lim && tiles < lim) return true;
+    set_error("%s: operand larger than 2 GiB", what);
+    return false;
+}
+
+int launch_check(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    return FOV_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // Dense: y = act(x W + b).  One wave per output row; lanes stride over In, shuffle-reduce.
 // Memory-bound streaming op (x is read once; W stays in L2): used for the teacher-forced
@@ -197,9 +210,7 @@ static int launch_dense(const float* x, const float* W, const float* b, const fl
         const size_t lds = sizeof(float) * ((size_t)DW_ROWS * In + DW_KQ * DW_ROWS * DW_OT);
         hipLaunchKernelGGL(dense_fewrows_kernel, dim3((unsigned)((N + DW_ROWS - 1) / DW_ROWS)), dim3(256), lds, stream, x, W, b, add,
                            add_stride, y, N, In, Out, activation);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("dense launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-        return FOV_OK;
+        return launch_check("dense");
     }
     if (Out <= 8 && In <= 2048 && N >= 64) {
         long blocks = ((long)N + 15) / 16;
@@ -214,9 +225,7 @@ static int launch_dense(const float* x, const float* W, const float* b, const fl
         hipLaunchKernelGGL(dense_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, x, W, b, add, add_stride, y, N, In, Out,
                            activation);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dense launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("dense");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1183,9 +1192,7 @@ int fov_mix_head_fwd(const float* h, const float* dense_W, const float* dense_b,
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(mix_head_fwd_kernel, dim3((unsigned)blocks), dim3(256), sizeof(float) * (8 * H + 64), (hipStream_t)stream, h,
                        dense_W, dense_b, mix_Wp, add, (long)add_row_stride, p, m, N, H, O);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_head_fwd launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("mix_head_fwd");
 }
 
 int fov_mix_head_bwd(const float* dm_loss, const float* dm_feedback, const float* m, const float* p, const float* mix_Wp,
@@ -1198,9 +1205,7 @@ int fov_mix_head_bwd(const float* dm_loss, const float* dm_feedback, const float
     const long n = (long)N * H;
     hipLaunchKernelGGL(mix_head_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dm_loss, dm_feedback,
                        m, p, mix_Wp, dense_W, dpre_m, dpre_p, dh, N, H, O);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_head_bwd launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("mix_head_bwd");
 }
 
 size_t fov_mix_head_wgrad_workspace_bytes(int B, int T_out, int H, int O, int n_others) {
@@ -1474,9 +1479,7 @@ int fov_meanvar_xyz(const float* y, float* out, int64_t rows, int fps, fov_strea
     const long n = rows * 3;
     hipLaunchKernelGGL(meanvar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, out,
                        (long)rows, fps);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("meanvar launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("meanvar");
 }
 
 int fov_workspace_init(void* workspace, size_t workspace_bytes, fov_stream_t stream) {
@@ -1773,9 +1776,7 @@ int fov_fov_hit_rate(const float* pred_xyz, int64_t pred_row_stride, const float
     const float d2r = 3.14159265358979323846f / 180.f;
     hipLaunchKernelGGL(hit_rate_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred_xyz,
                        (long)pred_row_stride, gt_xyz, (long)gt_row_stride, out, (long)rows, span_deg * d2r, gt_span_deg * d2r);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("hit_rate launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("hit_rate");
 }
 
 int64_t fov_window_count(int S, int T, int stride) {
@@ -1796,9 +1797,7 @@ int fov_window_stacks(const float* x, float* enc, float* fut, float* fut_in, int
     const long total = (long)W * U * T * feat;
     hipLaunchKernelGGL(window_stacks_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, enc,
                        fut, fut_in, U, S, feat, T, stride, T / stride, W, collapse_user ? 1 : 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("window_stacks launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("window_stacks");
 }
 
 int fov_exchange_mode(const void* workspace, size_t workspace_bytes, fov_stream_t stream) {

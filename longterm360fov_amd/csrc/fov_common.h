@@ -100,6 +100,11 @@ void xch_note_force_safe(void* workspace, int on);
 void xch_set_epoch_for_test(void* workspace, unsigned long long epoch);
 int ensure_dynamic_lds(const void* kern, size_t lds, int block = 256);  // cached hipFuncSetAttribute(MaxDynamicSharedMemorySize) + occupancy check (>= 1 workgroup per CU)
 void set_error(const char* fmt, ...);
+// 31-bit byte offsets inside one buffer descriptor: B maps of batch stride ldb (and of ldb2 when there is a second input x2),
+// weight_bytes of weights and, for the bf16 forms, `tiles` 16-row tiles.  false with the error "<what>: operand larger than
+// 2 GiB" when one of them does not fit.
+bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long ldb2, long weight_bytes, long tiles = 0);
+int launch_check(const char* what);   // after a launch: FOV_OK, or FOV_ERR_LAUNCH with the error "<what> launch: <hip string>"
 // wide-input layer, H = 256, 96 < F <= 256 (lstm_wide.hip)
 bool wide_shape_ok(int F, int H);
 bool wide_narrow_preferred(int B, int F, int H);

@@ -597,8 +597,7 @@ int gemm_bf16_tn_fused(const float* a1, long lda1, long a1_so, int M1, int shift
     else if (deep) hipLaunchKernelGGL(gemm_bf16_tn3_kernel<false>, grid, dim3(G3T), 0, stream, g);
     else if (avec) hipLaunchKernelGGL(gemm_bf16_tn_kernel<true>, grid, dim3(256), 0, stream, g);
     else hipLaunchKernelGGL(gemm_bf16_tn_kernel<false>, grid, dim3(256), 0, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("gemm_bf16_tn launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    if (int rc = launch_check("gemm_bf16_tn")) return rc;
     if (split > 1) return reduce_or_defer(deferred, scratch, c, (long)(M + g.bias_row) * N, split, accumulate, stream, "splitk_reduce");
     return FOV_OK;
 }
@@ -620,9 +619,7 @@ int gemm_bf16_nt(const float* a, long lda, const float* b, long ldb, float* c, i
     GemmNT g = {};
     g.a = a; g.b = b; g.c = c; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3((N + GT - 1) / GT, (M + GT - 1) / GT), dim3(256), 0, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("gemm_bf16_nt launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("gemm_bf16_nt");
 }
 
 }  // namespace fov

@@ -529,9 +529,7 @@ static int launch_bwd16_t(Bwd16Params& p, int act, hipStream_t stream) {
     const int pad_max = env_knobs().xcd_pad_max;   // members per group at most
     p.xcd_pad = (!no_pad && XG <= pad_max && p.num_groups < 8 && device_cu_count() >= 8 * XG) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(p.xcd_pad ? 8 * XG : p.num_groups * XG), dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("16-unit BPTT launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("16-unit BPTT");
 }
 
 // status word + granule buffers live at `xch_ws` (kStatusBytes + kXchBytes)
@@ -593,9 +591,7 @@ int launch_bwd16_pair(const float* R2, const float* K2, const float* reserve2, c
     if (int rc_ = xch_account(u.status, u.epoch_span, stream)) return rc_;
     void (*kern)(Bwd16Pair) = act == FOV_ACT_HARD_SIGMOID ? lstm_bwd16_pair_kernel<FOV_ACT_HARD_SIGMOID> : lstm_bwd16_pair_kernel<FOV_ACT_SIGMOID>;
     hipLaunchKernelGGL(kern, dim3(8 * 16), dim3(256), 0, stream, pp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("two-layer BPTT launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("two-layer BPTT");
 }
 
 }  // namespace fov

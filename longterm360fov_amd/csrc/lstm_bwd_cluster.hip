@@ -338,9 +338,7 @@ static int launch_bwd_h(const BwdParams& p, int act, hipStream_t stream) {
                                                           : lstm_bwd_cluster_kernel<H, FOV_ACT_SIGMOID>;
     const dim3 grid((H > 64 ? xch_padded_groups(p.num_groups) : p.num_groups) * (H / 64)), block(256);
     hipLaunchKernelGGL(kern, grid, block, 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("bwd cluster launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("bwd cluster");
 }
 
 // status word + granule buffers live at `xch_ws` (kStatusBytes + bwd_cluster_xch_bytes)

@@ -1168,9 +1168,7 @@ static int launch_cluster_h(const LstmParams& p, int mode, hipStream_t stream) {
     q.xcd_pad = (H >= 128 && !env_knobs().no_xcd_pad && (q.num_groups & 7) != 0 && device_cu_count() >= padded * (H / 64)) ? 1 : 0;
     const dim3 grid((q.xcd_pad ? padded : q.num_groups) * (H / 64)), block(256);
     hipLaunchKernelGGL(kern, grid, block, lds, stream, q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("cluster launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("cluster");
 }
 
 template <int H>
@@ -1187,9 +1185,7 @@ static int launch_cluster_fused_h(const LstmParams& p, hipStream_t stream) {
     const int padded = (q.num_groups + 7) & ~7;
     q.xcd_pad = (H >= 128 && !no_pad && (q.num_groups & 7) != 0 && device_cu_count() >= padded * (H / 64)) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3((q.xcd_pad ? padded : q.num_groups) * (H / 64)), dim3(256), lds, stream, q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("fused cluster launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("fused cluster");
 }
 
 static int launch_cluster_fused(const LstmParams& p, hipStream_t stream) {

@@ -164,9 +164,7 @@ int launch_generic(const LstmParams& p, bool decode, hipStream_t stream) {
         if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
     }
     hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("generic launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("generic");
 }
 
 }  // namespace fov

@@ -312,9 +312,7 @@ int launch_layer_bf16(const LstmParams& p_in, hipStream_t stream) {
         : xvec ? (hs_ ? lstm_layer_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, true> : lstm_layer_bf16_kernel<FOV_ACT_SIGMOID, 8, true>)
                : (hs_ ? lstm_layer_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, false> : lstm_layer_bf16_kernel<FOV_ACT_SIGMOID, 8, false>);
     hipLaunchKernelGGL(kern, dim3(q_padded_groups(p.num_groups) * QG), dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("bf16 LSTM layer launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("bf16 LSTM layer");
 }
 
 }  // namespace fov

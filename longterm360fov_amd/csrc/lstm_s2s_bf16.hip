@@ -352,9 +352,7 @@ int launch_s2s_bf16(const LstmParams& p_in, hipStream_t stream) {
         : xvec ? (hs_ ? s2s_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, true> : s2s_bf16_kernel<FOV_ACT_SIGMOID, 8, true>)
                : (hs_ ? s2s_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, false> : s2s_bf16_kernel<FOV_ACT_SIGMOID, 8, false>);
     hipLaunchKernelGGL(kern, dim3(q_padded_groups(p.num_groups) * QG), dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("bf16 seq2seq decode launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("bf16 seq2seq decode");
 }
 
 bool dense_bf16_shape_ok(int In, int Out) { return In >= 1 && In <= QH && Out >= 1 && Out <= 16; }
@@ -362,9 +360,7 @@ bool dense_bf16_shape_ok(int In, int Out) { return In >= 1 && In <= QH && Out >=
 int launch_dense_bf16(const float* x, const float* W, const float* b, float* y, int N, int In, int Out, int act, hipStream_t stream) {
     if (N == 0) return FOV_OK;
     hipLaunchKernelGGL(dense_bf16_kernel, dim3((N + QBT - 1) / QBT), dim3(256), 0, stream, x, W, b, y, N, In, Out, act);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("bf16 dense launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("bf16 dense");
 }
 
 }  // namespace fov

@@ -401,9 +401,7 @@ int launch_stack2_bf16(const float* x, const float* K1, const float* R1, const f
     void (*kern)(Stack2Params) = act == FOV_ACT_HARD_SIGMOID ? lstm_stack2_bf16_kernel<FOV_ACT_HARD_SIGMOID>
                                                              : lstm_stack2_bf16_kernel<FOV_ACT_SIGMOID>;
     hipLaunchKernelGGL(kern, dim3(2 * q_padded_groups(p.num_groups) * QG), dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("bf16 two-layer launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("bf16 two-layer");
 }
 
 }  // namespace fov

@@ -420,9 +420,7 @@ static int launch_wide_t(LstmParams& p, hipStream_t stream) {
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(xch_padded_groups(p.num_groups) * WG), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("wide LSTM launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("wide LSTM");
 }
 
 // p.status / p.xch point into the caller's workspace (cluster_workspace_bytes(B, H): header + the fixed granule area)

@@ -1057,9 +1057,7 @@ int launch_wide16_t(LstmParams& p, hipStream_t stream) {
     const int pad_max = env_knobs().xcd_pad_max;   // members per group at most
     p.xcd_pad = (!no_pad && WG <= pad_max && p.num_groups < 8 && device_cu_count() >= 8 * WG) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(p.xcd_pad ? 8 * WG : p.num_groups * WG), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("wide16 LSTM launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("wide16 LSTM");
 }
 
 }  // namespace
@@ -1116,9 +1114,7 @@ int launch_wide16_pair(const LstmParams& a, const LstmParams& b, hipStream_t str
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(8 * WG), dim3(256), lds, stream, pp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("two-layer width-512 launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("two-layer width-512");
 }
 
 // Encoder + free-running decoder in one launch: widths 128 / 256, narrow inputs, at most eight outputs fed back, one tile per group
@@ -1145,9 +1141,7 @@ static int launch_wide16_s2s_t(LstmParams& p, hipStream_t stream) {
     const bool no_pad = env_knobs().no_xcd_pad != 0;
     p.xcd_pad = (!no_pad && WG <= env_knobs().xcd_pad_max && p.num_groups < 8 && device_cu_count() >= 8 * WG) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(p.xcd_pad ? 8 * WG : p.num_groups * WG), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("seq2seq decode (wide16) launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("seq2seq decode (wide16)");
 }
 
 int launch_wide16_s2s(const LstmParams& p_in, hipStream_t stream) {

@@ -524,8 +524,7 @@ size_t mix_decoder_workspace_bytes(int B) {
 int mix_decoder_prepack(const float* K2, void* workspace, hipStream_t stream) {
     float* k2p = (float*)((char*)workspace + kStatusBytes + kXchBytes);
     hipLaunchKernelGGL(mix_decoder_pack_k2_kernel, dim3(MH * 4 * MH / 256), dim3(256), 0, stream, K2, k2p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_decoder_prepack launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    if (int rc = launch_check("mix_decoder_prepack")) return rc;
     prepack_mark(workspace, K2);
     return FOV_OK;
 }
@@ -552,9 +551,7 @@ int mix_decoder_launch(MixDecParams p, const float* K2, int act, int train, void
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(xch_padded_groups(p.num_groups) * MG), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_decoder launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("mix_decoder");
 }
 
 #ifdef FOV_STAMPS

@@ -537,8 +537,7 @@ size_t mix_decoder_bwd_workspace_bytes(int B) {
 int mix_decoder_bwd_prepack(const float* K2, void* workspace, hipStream_t stream) {
     float* k2p = (float*)((char*)workspace + kStatusBytes + kXchBytes);
     hipLaunchKernelGGL(mix_decoder_bwd_pack_k2_kernel, dim3(BH * 4 * BH / 256), dim3(256), 0, stream, K2, k2p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_decoder_bwd_prepack launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    if (int rc = launch_check("mix_decoder_bwd_prepack")) return rc;
     prepack_mark(workspace, K2);
     return FOV_OK;
 }
@@ -563,9 +562,7 @@ int mix_decoder_bwd_launch(MixDecBwdParams p, const float* K2, int act, void* wo
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(xch_padded_groups(p.num_groups) * BG), dim3(256), lds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mix_decoder_bwd launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("mix_decoder_bwd");
 }
 
 #ifdef FOV_STAMPS

@@ -735,12 +735,6 @@ bool mlp_dims_ok(int B, int L, const int* dims) {
     return true;
 }
 
-int mh_check(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
-}
-
 }  // namespace
 
 }  // namespace fov
@@ -776,7 +770,7 @@ int fov_mlp_head_fwd(const float* x, const float* const* W, const float* const* 
     int rc = ensure_dynamic_lds((const void*)mlp_head_fwd_kernel, lds, MH_NT);
     if (rc) return rc;
     hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3((unsigned)((B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
-    return mh_check("mlp head forward");
+    return launch_check("mlp head forward");
 }
 
 size_t fov_mlp_head_bwd_workspace_bytes(int B, int L, const int* dims) {
@@ -818,7 +812,7 @@ int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* 
         int rc = ensure_dynamic_lds((const void*)mlp_head_bwd_chain_kernel, lds, MH_NT);
         if (rc) return rc;
         hipLaunchKernelGGL(mlp_head_bwd_chain_kernel, dim3((unsigned)((B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
-        rc = mh_check("mlp head backward chain");
+        rc = launch_check("mlp head backward chain");
         if (rc) return rc;
     }
     int blk[MH_MAXL + 1] = {0, 0, 0, 0, 0};
@@ -830,7 +824,7 @@ int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* 
         if (rc) return rc;
     }
     hipLaunchKernelGGL(mlp_head_wgrad_kernel, dim3((unsigned)blk[L]), dim3(256), 0, (hipStream_t)stream, p, blk[1], blk[2], blk[3]);
-    return mh_check("mlp head weight gradients");
+    return launch_check("mlp head weight gradients");
 }
 
 int fov_gmm3d_loss_grad(const float* params, const float* y, int64_t ldy, float* loss, float* dpre, int B, int n_mix, int n_pts,
@@ -850,7 +844,7 @@ int fov_gmm3d_loss_grad(const float* params, const float* y, int64_t ldy, float*
     if (rc) return rc;
     hipLaunchKernelGGL(gmm3d_loss_grad_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, params, y, (long)ldy, ticket, part, loss,
                        dpre, n_mix, n_pts, tc, scale, weight_by_pi ? 1 : 0);
-    return mh_check("gmm3d loss");
+    return launch_check("gmm3d loss");
 }
 
 int fov_gmm3d_sample(const float* params, const float* u, const float* z, float* out, int64_t ldo, int B, int n_mix, int n_pts,
@@ -859,7 +853,7 @@ int fov_gmm3d_sample(const float* params, const float* u, const float* z, float*
     if (!params || !u || !z || !out || B < 0) { set_error("fov_gmm3d_sample: invalid argument"); return FOV_ERR_INVALID; }
     if (n_mix < 1 || n_mix > GM_MAXMIX || n_pts < 1 || ldo < 3 * (int64_t)n_pts) { set_error("fov_gmm3d_sample: n_mix <= 32, ldo >= 3 n_pts"); return FOV_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(gmm3d_sample_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, params, u, z, out, (long)ldo, n_mix, n_pts);
-    return mh_check("gmm3d sample");
+    return launch_check("gmm3d sample");
 }
 
 }  // extern "C"

@@ -132,9 +132,7 @@ int fov_onehot_maps(const float* xyz, int64_t xyz_seq_stride, int64_t xyz_step_s
         hipLaunchKernelGGL(onehot_maps_kernel<32>, grid, block, 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(onehot_maps_kernel<30>, grid, block, 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("onehot_maps launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("onehot_maps");
 }
 
 int fov_onehot_status(int* status, fov_stream_t stream) {

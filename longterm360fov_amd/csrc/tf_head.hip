@@ -206,9 +206,7 @@ int fov_tf_head_fwd(const float* h, const float* mu_W1, const float* mu_b1, cons
     p.a1 = a1; p.mu = mu; p.a3 = a3; p.var = var; p.B = B; p.H = H; p.M = M; p.O = O;
     const size_t lds = sizeof(float) * ((size_t)TH_ROWS * H + TH_KQ * TH_ROWS * 64 + TH_ROWS * 64);
     hipLaunchKernelGGL(tf_head_fwd_kernel, dim3((unsigned)((B + TH_ROWS - 1) / TH_ROWS)), dim3(256), lds, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("tf head forward launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("tf head forward");
 }
 
 int fov_tf_head_bwd(const float* h, const float* mu_W1, const float* mu_W2, const float* var_W1, const float* var_W2, const float* a1,
@@ -242,9 +240,7 @@ int fov_tf_head_bwd(const float* h, const float* mu_W1, const float* mu_W2, cons
         if (int rc = defer_touch(grads[i], sizes[i], (hipStream_t)stream)) return rc;
     const int blocksA = (H + 3) / 4, blocksB = ((H + 255) / 256) * ((B + 7) / 8);
     hipLaunchKernelGGL(tf_head_bwd_kernel, dim3((unsigned)(blocksA + blocksB + 1)), dim3(256), 0, (hipStream_t)stream, p, blocksA, blocksB);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("tf head backward launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("tf head backward");
 }
 
 }  // extern "C"

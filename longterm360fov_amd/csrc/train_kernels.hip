@@ -804,9 +804,7 @@ __global__ void guard_flag_kernel(const unsigned* g0, const unsigned* g1, const 
 }
 int guard_flag(const unsigned* const* guards, float* out, hipStream_t stream) {
     hipLaunchKernelGGL(guard_flag_kernel, dim3(1), dim3(1), 0, stream, guards[0], guards[1], guards[2], out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("guard_flag launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("guard_flag");
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -1314,9 +1312,7 @@ __global__ __launch_bounds__(256) void rmsprop_tf_kernel(float* __restrict__ p, 
 // ---------------------------------------------------------------------------------------
 static int check_launch(const char* what) {
     if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] launched: %s\n", what);   // FOV_DBG_TRACE=1 (with HIP_LAUNCH_BLOCKING=1: the last line names the launch BEFORE a faulting one)
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check(what);
 }
 
 // C (+)= A.B.  Few output tiles and a long K -> split-K: slices write partial tiles into

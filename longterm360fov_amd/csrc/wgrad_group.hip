@@ -541,9 +541,7 @@ int wgrad_group_layers(int L, const float* const* x, const int* F, const float* 
     if (int rc = touch_outputs(g, stream)) return rc;
     if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] wgrad_group: %d problems, %d workgroups\n", g.count, blocks);
     hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("wgrad_group launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("wgrad_group");
 }
 
 
@@ -596,9 +594,7 @@ int wgrad_rows_layers(int L, const float* const* x, const int* F, const int* T, 
     const dim3 grid((unsigned)blocks), blk(256);
     if (MT == 2) hipLaunchKernelGGL((wgrad_rows_kernel<2, 10>), grid, blk, 0, stream, g);
     else hipLaunchKernelGGL((wgrad_rows_kernel<1, 5>), grid, blk, 0, stream, g);      // (batches of 10: H = 256 11.1 -> 14.2 us)
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("wgrad_rows launch: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
-    return FOV_OK;
+    return launch_check("wgrad_rows");
 }
 
 }  // namespace fov

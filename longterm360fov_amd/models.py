@@ -287,6 +287,22 @@ class KerasModelSurface:
         import torch
         return torch.from_numpy(_as_f32(a)).to(self.device)
 
+    def _predict_chunks(self, arrays, batch_size, run, empty):
+        """run(*chunks) over `batch_size` rows of `arrays` at a time (None: all rows in one call), each result copied to the
+        host, the results concatenated along the rows.  arrays: host arrays (a chunk is uploaded), device tensors (sliced) or
+        None (handed on); run returns one device tensor, or a tuple of them when `empty` is a list; empty: the shape a result has
+        after its leading N (one per output if a list) - what a call with no rows returns, as (0,) + shape."""
+        n = arrays[0].shape[0]
+        bs = n if not batch_size else int(batch_size)
+        several = isinstance(empty, list)
+        outs = []
+        for lo in range(0, n, max(bs, 1)):
+            o = run(*[a if a is None else a[lo:lo + bs] if hasattr(a, "is_cuda") else self._to_device(a[lo:lo + bs]) for a in arrays])
+            outs.append([t.cpu().numpy() for t in (o if several else (o,))])
+        res = [np.concatenate(col, axis=0) for col in zip(*outs)] if outs else \
+            [np.zeros((0,) + tuple(shape), np.float32) for shape in (empty if several else [empty])]
+        return res if several else res[0]
+
     # ---- training surface ----
     def compile(self, optimizer="Adam", loss="mean_squared_error", metrics=None):
         """Keras `compile`.  Accepted: optimizer 'Adam' | 'RMSprop' (Keras defaults), loss 'mean_squared_error' | 'mse'
@@ -427,15 +443,11 @@ class Seq2SeqLSTM(KerasModelSurface):
         enc, dec_in = x
         enc, dec_in = _as_f32(enc), _as_f32(dec_in)
         ops, dw = self._ops(), self._device_weights()
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            o = ops.seq2seq_teacher_forced(self._dev(enc[lo:lo + bs]), self._dev(dec_in[lo:lo + bs]), dw,
-                                           act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype)
-            outs.append(o.cpu().numpy())
+        y = self._predict_chunks([enc, dec_in], batch_size, lambda e, d: ops.seq2seq_teacher_forced(
+            e, d, dw, act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype),
+            (dec_in.shape[1], self.num_decoder_tokens))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, dec_in.shape[1], self.num_decoder_tokens), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -453,15 +465,11 @@ class Seq2SeqLSTM(KerasModelSurface):
                 first_decoder_input = get_gt_target_xyz(input_seq[:, -1:, :].astype(np.float64))
         first_decoder_input = _as_f32(first_decoder_input)
         ops, dw = self._ops(), self._device_weights()
-        n = input_seq.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            o = ops.seq2seq_decode(self._dev(input_seq[lo:lo + bs]), self._dev(first_decoder_input[lo:lo + bs]), dw,
-                                   T_out, act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype)
-            outs.append(o.cpu().numpy())
+        y = self._predict_chunks([input_seq, first_decoder_input], batch_size, lambda e, d: ops.seq2seq_decode(
+            e, d, dw, T_out, act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype),
+            (T_out, self.num_decoder_tokens))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, self.num_decoder_tokens), np.float32)
+        return y
 
     def _encoder_predict(self, input_seq):
         """encoder_model.predict(input_seq) -> [state_h, state_c]   (FoV_seq2seq.py:137,156)."""
@@ -582,9 +590,6 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
         T_out, O, H, F = self.predict_step, self.num_decoder_tokens, self.latent_dim, self.num_encoder_tokens
         plain = not (self.add_residual_link or self.enc_last_out_as_dec_in or self.dense_activation != "tanh" or
                      self.has_reconstruct_loss or (self.embed_frame_state_enc2dec and not self.decoder_no_init_state))
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs, recs = [], []
 
         def dense(v, W, b, dact=None):
             dact = dact or self.dense_activation
@@ -601,30 +606,26 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
                     xin = ops.act_bwd(r, r, base=xin, activation=None)     # y_t = Dense(h_t) + residual
                 o[:, t] = xin
             return o
-        for lo in range(0, n, max(bs, 1)):
-            e = self._dev(enc[lo:lo + bs])
+
+        def run(e, d0):
             if plain:     # ONE fused call; a zero-length encoder input is the zero initial state of :98-99
-                o = ops.seq2seq_decode(e[:, :0] if self.decoder_no_init_state else e, self._dev(dec0[lo:lo + bs]), dw, T_out,
-                                       act=act, impl=self.impl, workspace=self._ws)
-                outs.append(o.cpu().numpy())
-                continue
+                return ops.seq2seq_decode(e[:, :0] if self.decoder_no_init_state else e, d0, dw, T_out, act=act, impl=self.impl,
+                                          workspace=self._ws)
             B = e.shape[0]
             _, h_enc, c_enc = ops.lstm_seq(e, dw["enc_K"], dw["enc_R"], dw["enc_b"], act=act, impl=self.impl, return_sequences=False,
                                            workspace=self._ws)
             sh, sc = h_enc, c_enc
             if self.embed_frame_state_enc2dec:
                 sh, sc = dense(h_enc, dw["emb1_W"], dw["emb1_b"], "tanh"), dense(c_enc, dw["emb2_W"], dw["emb2_b"], "tanh")
-            xin = dense(h_enc, dw["dense_W"], dw["dense_b"]) if self.enc_last_out_as_dec_in else self._dev(dec0[lo:lo + bs]).reshape(B, O)
+            xin = dense(h_enc, dw["dense_W"], dw["dense_b"]) if self.enc_last_out_as_dec_in else d0.reshape(B, O)
             h, c = (torch.zeros_like(sh), torch.zeros_like(sc)) if self.decoder_no_init_state else (sh, sc)
             r = dense(xin, dw["res_W"], dw["res_b"]) if self.add_residual_link else None
-            outs.append(unroll("dec", "dense", xin, h, c, r, None, O).cpu().numpy())
-            if self.has_reconstruct_loss:
-                xr = dense(h_enc, dw["recd_W"], dw["recd_b"], "tanh")
-                recs.append(unroll("rec", "recd", xr, sh, sc, None, "tanh", F).cpu().numpy())
+            y = unroll("dec", "dense", xin, h, c, r, None, O)
+            if not self.has_reconstruct_loss:
+                return y
+            return y, unroll("rec", "recd", dense(h_enc, dw["recd_W"], dw["recd_b"], "tanh"), sh, sc, None, "tanh", F)
+        y = self._predict_chunks([enc, dec0], batch_size, run, [(T_out, O), (T_out, F)] if self.has_reconstruct_loss else (T_out, O))
         self._ws.check()
-        y = np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, O), np.float32)
-        if self.has_reconstruct_loss:
-            return [y, np.concatenate(recs, axis=0) if recs else np.zeros((0, T_out, F), np.float32)]
         return y
 
     predict_on_batch = predict
@@ -700,21 +701,18 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
 
     def predict(self, x, batch_size=None, verbose=0):
         """[encoder_input (N,T_in,F), decoder_input (N,T_out,O)] -> (N,T_out,O), teacher-forced graph (:332)."""
-        import torch
         enc, dec_in = _as_f32(x[0]), _as_f32(x[1])
         ops, dw = self._device()
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            states = self._encode(ops, dw, torch.from_numpy(enc[lo:lo + bs]).to(self.device))
-            inp = torch.from_numpy(dec_in[lo:lo + bs]).to(self.device)
+
+        def run(e, inp):
+            states = self._encode(ops, dw, e)
             for l in range(self.L):
                 inp, _, _ = ops.lstm_seq(inp, dw["dec%d_K" % l], dw["dec%d_R" % l], dw["dec%d_b" % l], states[l][0], states[l][1],
                                          act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
-            outs.append(ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh").cpu().numpy())
+            return ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
+        y = self._predict_chunks([enc, dec_in], batch_size, run, (dec_in.shape[1], self.O))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, dec_in.shape[1], self.O), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -725,13 +723,11 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
         enc, d0 = _as_f32(input_seq), _as_f32(first_decoder_input)
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         ops, dw = self._device()
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            states = self._encode(ops, dw, torch.from_numpy(enc[lo:lo + bs]).to(self.device))
+
+        def run(e, xin):
+            states = self._encode(ops, dw, e)
             B = states[0][0].shape[0]
-            xin = torch.from_numpy(d0[lo:lo + bs]).to(self.device).reshape(B, 1, self.O)
+            xin = xin.reshape(B, 1, self.O)
             y = torch.empty((B, T_out, self.O), dtype=torch.float32, device=self.device)
             for t in range(T_out):
                 inp = xin
@@ -741,9 +737,10 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
                     states[l] = (h, c)
                 xin = ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
                 y[:, t] = xin[:, 0]
-            outs.append(y.cpu().numpy())
+            return y
+        y = self._predict_chunks([enc, d0], batch_size, run, (T_out, self.O))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, self.O), np.float32)
+        return y
 
     def _make_trainer(self, optimizer):
         from .training import StackedSeq2SeqTrainer
@@ -828,18 +825,14 @@ class OthersContextSeq2Seq(KerasModelSurface):
         dw, act, H, O = self._device_weights(), self.recurrent_activation, self.H, self.O
         T_out = oth.shape[1]
         W_h = dw["dense_W"][dw["dense_W"].shape[0] - H:].contiguous()
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            d = lambda a: torch.from_numpy(a[lo:lo + bs]).to(self.device)
-            e = d(enc)
+
+        def run(e, o, xin):
             B = e.shape[0]
-            ctx_proj = self._context(ops, dw, d(oth))
+            ctx_proj = self._context(ops, dw, o)
             hs1, h1, c1 = ops.lstm_seq(e, dw["enc1_K"], dw["enc1_R"], dw["enc1_b"], act=act, impl=self.impl, workspace=self._ws)
             _, h2, c2 = ops.lstm_seq(hs1, dw["enc2_K"], dw["enc2_R"], dw["enc2_b"], act=act, impl=self.impl, return_sequences=False,
                                      workspace=self._ws)
-            xin = d(dec0).reshape(B, 1, O)
+            xin = xin.reshape(B, 1, O)
             y = torch.empty((B, T_out, O), dtype=torch.float32, device=self.device)
             for t in range(T_out):
                 _, h1, c1 = ops.lstm_seq(xin, dw["dec1_K"], dw["dec1_R"], dw["dec1_b"], h1, c1, act=act, impl=self.impl,
@@ -850,9 +843,10 @@ class OthersContextSeq2Seq(KerasModelSurface):
                     ops.dense_add(h2, W_h, None, ctx_proj[:, t], activation="tanh")
                 y[:, t] = yt
                 xin = yt.view(B, 1, O)
-            outs.append(y.cpu().numpy())
+            return y
+        y = self._predict_chunks([enc, oth, dec0], batch_size, run, (T_out, O))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, O), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -912,27 +906,22 @@ class NoTeacherForcingOthersConvLSTM(KerasModelSurface):
                                            device=self.device)
 
     def predict(self, x, batch_size=None, verbose=0):
-        import torch
         from . import ops
         enc, oth, dec0 = (_as_f32(a) for a in x)
         tr = self._get_trainer()
         if self._dw is None:          # weights were set from outside since the trainer last saw them
             tr.load_weights_(self._w)
             self._dw = tr.w
-        n, T_out = enc.shape[0], oth.shape[1]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            d = lambda a: torch.from_numpy(a[lo:lo + bs]).to(self.device)
-            e = d(enc)
-            B = e.shape[0]
+        T_out = oth.shape[1]
+
+        def run(e, o, d0):
             _, hT, cT = ops.lstm_seq(e, tr.w["enc_K"], tr.w["enc_R"], tr.w["enc_b"], act=self.recurrent_activation, impl=self.impl,
                                      return_sequences=False, workspace=tr.ws)
-            S, _ = tr.branch_forward(d(oth), tape=False)
-            tp = tr.decode(d(dec0).reshape(B, self.O), hT, cT, S, T_out, tape=False)
-            outs.append(tp["XA"][1:].transpose(0, 1).cpu().numpy())
+            S, _ = tr.branch_forward(o, tape=False)
+            return tr.decode(d0.reshape(e.shape[0], self.O), hT, cT, S, T_out, tape=False)["XA"][1:].transpose(0, 1)
+        y = self._predict_chunks([enc, oth, dec0], batch_size, run, (T_out, self.O))
         tr.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, self.O), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -972,21 +961,20 @@ class KerasSingleLSTM(KerasModelSurface):
         from . import ops
         x = _as_f32(x)
         dw, act = self._device_weights(), self.recurrent_activation
-        n = x.shape[0]
-        bs = n if not batch_size else int(batch_size)
         P = self.predict_step
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            xd = torch.from_numpy(x[lo:lo + bs]).to(self.device)
+        lo = 0       # first row of the chunk: the caller's noise is (P-1, N, F), rows on its second axis
+
+        def run(xd):
+            nonlocal lo
             B = xd.shape[0]
             if self.unrolled and not self.sample_and_refeed:
                 xd = xd.expand(B, P, self.F).contiguous()          # the same second is shown to every step (:131-153)
             if not self.sample_and_refeed:
                 hs, _, _ = ops.lstm_seq(xd, dw["K"], dw["R"], dw["b"], act=act, impl=self.impl, workspace=self._ws)
-                outs.append(ops.dense(hs, dw["dense_W"], dw["dense_b"], activation="tanh").cpu().numpy())
-                continue
+                return ops.dense(hs, dw["dense_W"], dw["dense_b"], activation="tanh")
             nz = torch.randn((P - 1, B, self.F), dtype=torch.float32, device=self.device) if noise is None \
-                else torch.from_numpy(_as_f32(noise[:, lo:lo + bs])).to(self.device)
+                else self._to_device(noise[:, lo:lo + B])
+            lo += B
             y = torch.empty((B, P, self.O), dtype=torch.float32, device=self.device)
             xin, h, c = xd.reshape(B, 1, self.F), None, None
             for t in range(P):
@@ -996,10 +984,10 @@ class KerasSingleLSTM(KerasModelSurface):
                 y[:, t] = yt
                 if t < P - 1:
                     xin = ops.sample_refeed(yt[:, :3].contiguous(), yt[:, 3:].contiguous(), nz[t], std="var", planar=True).view(B, 1, self.F)
-            outs.append(y.cpu().numpy())
+            return y
+        y = self._predict_chunks([x], batch_size, run, (P if self.unrolled else x.shape[1], self.O))
         self._ws.check()
-        T = P if self.unrolled else x.shape[1]
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T, self.O), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -1190,18 +1178,11 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         return out.transpose(0, 1)
 
     def predict(self, x, batch_size=None, verbose=0):
-        import torch
         enc, others, dec0 = (_as_f32(a) for a in x)
         self._device_weights()
-        n = enc.shape[0]
-        T_out, O = others.shape[1], self.num_decoder_tokens
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            d = lambda a: torch.from_numpy(a[lo:lo + bs]).to(self.device)
-            outs.append(self.predict_device(d(enc), d(others), d(dec0)).cpu().numpy())
+        y = self._predict_chunks([enc, others, dec0], batch_size, self.predict_device, (others.shape[1], self.num_decoder_tokens))
         self._ws.check()
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out, O), np.float32)
+        return y
 
     predict_on_batch = predict
 
@@ -1404,26 +1385,21 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                                dropout_rate=self.dropout_rate, add_xyz_sum1=self.add_xyz_sum1, loss=self.loss or "mse",
                                dilation_rate=self.dilation_rate)
 
+    def _output_shape(self, T_out, H, W):
+        """What a prediction has after its leading N."""
+        return (T_out, 6) if self.head == "dense" else (T_out, H, W, self._w["head2_W"].shape[3])
+
     def predict(self, x, batch_size=None, predict_step=None, verbose=0):
-        import torch
-        from . import ops
         enc, dec0 = _as_f32(x[0]), _as_f32(x[1])
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            out = self.predict_device(torch.from_numpy(enc[lo:lo + bs]).to(self.device), torch.from_numpy(dec0[lo:lo + bs]).to(self.device), T_out)
-            outs.append(out.cpu().numpy())
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out), np.float32)
+        return self._predict_chunks([enc, dec0], batch_size, lambda e, d: self.predict_device(e, d, T_out),
+                                    self._output_shape(T_out, *enc.shape[2:4]))
 
-    def predict_device(self, xe, dec0, predict_step=None):
-        """predict on device-resident inputs: xe (B,T_in,H,W,C), dec0 (B,1,H,W,C) float32 tensors on self.device (C may already
-        carry the zero channels up to a multiple of 4, as ops.one_hot_maps(channels=32) writes them) -> the
-        prediction as a device tensor (B,T_out,H,W,C_out) / (B,T_out,6); no host transfer (what bench.py times)."""
+    def _device_weights(self):
+        """The weights on the device and what predict_device derives from them, once per set of weights (rebuilt whenever _dw is
+        dropped): the [K ; R] stacks, and the bf16 packs of the head's kernels (dtype) and of the stacks (cell_dtype)."""
         import torch
         from . import ops
-        T_out = cfg.predict_step if predict_step is None else int(predict_step)
         if self._dw is None:
             self._dw = {k: torch.from_numpy(v).to(self.device) for k, v in self._w.items()}
             for side in ("enc", "dec"):     # [K ; R] stacked along the input-channel axis: one convolution per cell step
@@ -1433,20 +1409,42 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                     if pad:   # zero weight rows for the zero channels the input map is padded with (16-byte pixel gather)
                         K = torch.cat([K, torch.zeros(K.shape[:2] + (pad, K.shape[3]), dtype=K.dtype, device=K.device)], 2)
                     self._dw["%s%d_KR" % (side, l)] = torch.cat([K, R], 2).contiguous()
-            if self.dtype == "bf16":        # the head's kernels as bf16 in fragment order: rebuilt whenever _dw is dropped
+            if self.dtype == "bf16":        # the head's kernels as bf16 in fragment order
                 for i in range(3):
                     self._dw["head%d_P" % i] = ops.conv2d_pack_bf16(self._dw["head%d_W" % i])
             if self.cell_dtype == "bf16":   # the cells' [K ; R] stacks likewise
-                for side in ("enc", "dec"):
-                    for l in range(3):
-                        self._dw["%s%d_P" % (side, l)] = ops.convlstm_cell_pack_bf16(self._dw["%s%d_KR" % (side, l)])
-        dw, act = self._dw, self.act
+                for name in [k[:-3] for k in self._dw if k.endswith("_KR")]:
+                    self._dw[name + "_P"] = ops.convlstm_cell_pack_bf16(self._dw[name + "_KR"])
+        return self._dw
+
+    def _cell_and_head(self, dw):
+        """The arithmetic cell_dtype / dilation_rate and head / dtype choose -> (cell(x, h, name, c, h_out): one ConvLSTM2D step
+        of layer `name`, head(feat): the prediction from the concatenated decoder outputs)."""
+        from . import ops
+        act = self.act
         if self.cell_dtype == "bf16":
             cell = lambda x, h, name, c, h_out: ops.convlstm_cell_bf16(x, h, dw[name + "_KR"], dw[name + "_b"], c, h_out, act,
                                                                        packed=dw[name + "_P"])
         else:
             cell = lambda x, h, name, c, h_out: ops.convlstm_cell(x, h, dw[name + "_KR"], dw[name + "_b"], c, h_out, act,
                                                                   dilation=self.dilation_rate)
+        if self.head == "dense":     # Flatten + Dense(6): cfg.predict_mean_var
+            return cell, lambda feat: ops.dense(feat.reshape(feat.shape[0], -1), dw["head0_W"], dw["head0_b"], activation=None)
+        if self.dtype == "bf16":
+            conv = lambda y, i, a: ops.conv2d_bf16(y, dw["head%d_W" % i], dw["head%d_b" % i], activation=a, packed=dw["head%d_P" % i])
+        else:
+            conv = lambda y, i, a: ops.conv2d(y, dw["head%d_W" % i], dw["head%d_b" % i], activation=a)
+        last = "relu" if self.head == "conv2d" else None
+        return cell, lambda feat: ops.softmax_lastdim(conv(conv(conv(feat, 0, "relu"), 1, "relu"), 2, last))
+
+    def predict_device(self, xe, dec0, predict_step=None):
+        """predict on device-resident inputs: xe (B,T_in,H,W,C), dec0 (B,1,H,W,C) float32 tensors on self.device (C may already
+        carry the zero channels up to a multiple of 4, as ops.one_hot_maps(channels=32) writes them) -> the
+        prediction as a device tensor (B,T_out,H,W,C_out) / (B,T_out,6); no host transfer (what bench.py times)."""
+        import torch
+        T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        dw = self._device_weights()
+        cell, head = self._cell_and_head(dw)
         filters = [dw["enc%d_R" % l].shape[2] for l in range(3)]
         cat = sum(filters)
         offs = [0, filters[0], filters[0] + filters[1]]
@@ -1478,8 +1476,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             seq = nxt
             states.append([h, c])
         # decoder: three cells per step, each h written straight into its slot of the concat map
-        dense_head = self.head == "dense"
-        out = e4(B, T_out, 6) if dense_head else e4(B, T_out, H, W, dw["head2_W"].shape[3])
+        out = e4(B, T_out, *self._output_shape(T_out, H, W)[1:])
         for t in range(T_out):
             feat = e4(B, H, W, cat)
             cur = inp
@@ -1488,25 +1485,10 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                 cell(cur, states[l][0], "dec%d" % l, states[l][1], hslot)
                 states[l][0] = hslot
                 cur = hslot
-            if dense_head:   # Flatten + Dense(6): cfg.predict_mean_var, output fed back as a 1x1x6 map
-                y = ops.dense(feat.reshape(B, H * W * cat), dw["head0_W"], dw["head0_b"], activation=None)
-                out[:, t] = y
-                if pad:
-                    inp[..., :C_in] = y.reshape(B, 1, 1, 6)
-                else:
-                    inp = y.reshape(B, 1, 1, 6)
-                continue
-            last = "relu" if self.head == "conv2d" else None
-            if self.dtype == "bf16":
-                y = ops.conv2d_bf16(feat, dw["head0_W"], dw["head0_b"], activation="relu", packed=dw["head0_P"])
-                y = ops.conv2d_bf16(y, dw["head1_W"], dw["head1_b"], activation="relu", packed=dw["head1_P"])
-                y = ops.conv2d_bf16(y, dw["head2_W"], dw["head2_b"], activation=last, packed=dw["head2_P"])
-            else:
-                y = ops.conv2d(feat, dw["head0_W"], dw["head0_b"], activation="relu")
-                y = ops.conv2d(y, dw["head1_W"], dw["head1_b"], activation="relu")
-                y = ops.conv2d(y, dw["head2_W"], dw["head2_b"], activation=last)
-            y = ops.softmax_lastdim(y)
+            y = head(feat)
             out[:, t] = y
+            if self.head == "dense":     # the six outputs fed back as a 1x1x6 map
+                y = y.reshape(B, 1, 1, 6)
             if pad:
                 inp[..., :C_in] = y
             else:
@@ -1546,14 +1528,8 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         self._check_onehot_model()
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         enc, dec = self._xyz_on_device(enc_xyz), self._xyz_on_device(dec_xyz)
-        n = enc.shape[0]
-        bs = n if not batch_size else int(batch_size)
-        outs = []
-        for lo in range(0, n, max(bs, 1)):
-            xe = ops.one_hot_maps(enc[lo:lo + bs], channels=32)
-            d0 = ops.one_hot_maps(dec[lo:lo + bs], channels=32)
-            outs.append(self.predict_device(xe, d0, T_out).cpu().numpy())
-        return np.concatenate(outs, axis=0) if outs else np.zeros((0, T_out), np.float32)
+        return self._predict_chunks([enc, dec], batch_size, lambda e, d: self.predict_device(
+            ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out), self._output_shape(T_out, 36, 18))
 
     def train_on_trajectories(self, enc_xyz, dec_xyz, target_xyz):
         """train_on_batch([enc maps, dec maps], target maps) with the three one-hot map sets built on the device from frame

@@ -1092,27 +1092,47 @@ def lstm_seq_zx(zx, R, b, h0=None, c0=None, act="sigmoid", impl="auto", return_s
 # ---------------------------------------------------------------------------------------------
 # ConvLSTM2D seq2seq (a8/a9): building blocks
 # ---------------------------------------------------------------------------------------------
+_CONV_ACT = {None: 0, "linear": 0, "relu": 2}    # the activation codes of the fov_conv2d_* entry points
+
+
+def _nhwc(t, what="NHWC with a uniform pixel stride"):
+    """(B, H, W, C, ldx, ldb) of an NHWC float32 map that may be a channel-slice / batch-strided view: only the pixel stride
+    ldx and the batch stride ldb may differ from dense (a batch of one has no batch stride to read)."""
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
+    B, H, W, C = t.shape
+    ldx = t.stride(2)
+    ldb = t.stride(0) if B > 1 else H * W * ldx
+    assert t.stride(1) == W * ldx and ldb >= H * W * ldx, what
+    return B, H, W, C, ldx, ldb
+
+
+def _conv2d(x, w, out):
+    """The checks conv2d and conv2d_bf16 share -> (geometry of x, shape of w, y)."""
+    g = _nhwc(x, "x must be NHWC with a uniform pixel stride")
+    kh, kw, Cw, N = _dev(w, "w").shape
+    assert Cw == g[3]
+    y = torch.empty(g[:3] + (N,), dtype=torch.float32, device=x.device) if out is None else out
+    return g, (N, kh, kw), y
+
+
 def conv2d(x, w, b=None, add=None, activation=None, out=None, in_channels=None, dilation=1):
     """y (B,H,W,N) = act(conv2d_same(x, w) + b + add).  x may be a channel slice view of a wider NHWC map
     (only the last-dim stride may differ from dense: pass the view, pixel stride is taken from it).
     dilation = Keras `dilation_rate` (taps `dilation` pixels apart, 'same' padding grown to match)."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(3) == 1
-    B, H, W, C = x.shape
-    ldx = x.stride(2)
-    ldb = x.stride(0) if B > 1 else H * W * ldx
-    assert x.stride(1) == W * ldx and ldb >= H * W * ldx, "x must be NHWC with a uniform pixel stride"
-    w = _dev(w, "w")
-    kh, kw, Cw, N = w.shape
-    assert Cw == C
-    y = torch.empty((B, H, W, N), dtype=torch.float32, device=x.device) if out is None else out
-    act = {None: 0, "linear": 0, "relu": 2}[activation]
-    if dilation != 1:
-        check(_lib.lib().fov_conv2d_dilated_fwd(x.data_ptr(), ldx, ldb, _ptr(w), _ptr(_dev(b, "b")), _ptr(add), _ptr(y), B, H, W,
-                                                C, N, kh, kw, int(dilation), act, _stream()))
-        return y
-    check(_lib.lib().fov_conv2d_fwd(x.data_ptr(), ldx, ldb, _ptr(w), _ptr(_dev(b, "b")), _ptr(add), _ptr(y), B, H, W, C, N,
-                                    kh, kw, act, _stream()))
+    (B, H, W, C, ldx, ldb), (N, kh, kw), y = _conv2d(x, w, out)
+    L = _lib.lib()
+    fwd, dil = (L.fov_conv2d_dilated_fwd, (int(dilation),)) if dilation != 1 else (L.fov_conv2d_fwd, ())
+    check(fwd(x.data_ptr(), ldx, ldb, _ptr(w), _ptr(_dev(b, "b")), _ptr(add), _ptr(y), B, H, W, C, N, kh, kw, *dil,
+              _CONV_ACT[activation], _stream()))
     return y
+
+
+def _pack_bf16(w, F_div, nbytes, pack):
+    """w (kh,kw,C,N) rounded to bf16 into a fresh device byte tensor by one of the library's pack entry points."""
+    kh, kw, C, N = w.shape
+    packed = torch.empty((int(nbytes(C, N // F_div, kh, kw)),), dtype=torch.uint8, device=w.device)
+    check(pack(_ptr(w), _ptr(packed), C, N // F_div, kh, kw, _stream()))
+    return packed
 
 
 def conv2d_pack_bf16(w):
@@ -1120,11 +1140,8 @@ def conv2d_pack_bf16(w):
     a device byte tensor of fov_conv2d_bf16_packed_bytes.  Pack once per set of weights; the layout is the library's own."""
     w = _dev(w, "w")
     assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous()
-    kh, kw, C, N = w.shape
     L = _lib.lib()
-    packed = torch.empty((int(L.fov_conv2d_bf16_packed_bytes(C, N, kh, kw)),), dtype=torch.uint8, device=w.device)
-    check(L.fov_conv2d_pack_bf16(_ptr(w), _ptr(packed), C, N, kh, kw, _stream()))
-    return packed
+    return _pack_bf16(w, 1, L.fov_conv2d_bf16_packed_bytes, L.fov_conv2d_pack_bf16)
 
 
 def conv2d_bf16(x, w, b=None, activation=None, out=None, packed=None):
@@ -1132,46 +1149,61 @@ def conv2d_bf16(x, w, b=None, activation=None, out=None, packed=None):
     accumulation, bias / relu / y in fp32 (inference of the ConvLSTM head).  x as in conv2d (channel-slice views allowed);
     w the fp32 (kh,kw,C,N) kernel - it gives the shape -, packed = conv2d_pack_bf16(w) when the caller keeps it (without
     it the call packs first)."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(3) == 1
-    B, H, W, C = x.shape
-    ldx = x.stride(2)
-    ldb = x.stride(0) if B > 1 else H * W * ldx
-    assert x.stride(1) == W * ldx and ldb >= H * W * ldx, "x must be NHWC with a uniform pixel stride"
-    w = _dev(w, "w")
-    kh, kw, Cw, N = w.shape
-    assert Cw == C
+    (B, H, W, C, ldx, ldb), (N, kh, kw), y = _conv2d(x, w, out)
     L = _lib.lib()
     if packed is None:
         packed = conv2d_pack_bf16(w)
     assert packed.is_cuda and packed.dtype == torch.uint8 and packed.numel() == L.fov_conv2d_bf16_packed_bytes(C, N, kh, kw)
-    y = torch.empty((B, H, W, N), dtype=torch.float32, device=x.device) if out is None else out
-    act = {None: 0, "linear": 0, "relu": 2}[activation]
-    check(L.fov_conv2d_fwd_bf16(x.data_ptr(), ldx, ldb, _ptr(packed), _ptr(_dev(b, "b")), _ptr(y), B, H, W, C, N, kh, kw, act,
-                                _stream()))
+    check(L.fov_conv2d_fwd_bf16(x.data_ptr(), ldx, ldb, _ptr(packed), _ptr(_dev(b, "b")), _ptr(y), B, H, W, C, N, kh, kw,
+                                _CONV_ACT[activation], _stream()))
     return y
 
 
 def conv2d_cat(x1, x2, w, b=None, activation=None, out=None):
     """y = act(conv2d_same([x1 | x2], w) + b): convolution over the channel concatenation of two NHWC maps (each may
     be a channel-slice / batch-strided view) without materialising it; w (kh,kw,C1+C2,N)."""
-    def geom(x):
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.stride(3) == 1
-        B, H, W, C = x.shape
-        ldx = x.stride(2)
-        ldb = x.stride(0) if B > 1 else H * W * ldx
-        assert x.stride(1) == W * ldx and ldb >= H * W * ldx, "NHWC with a uniform pixel stride"
-        return B, H, W, C, ldx, ldb
-    B, H, W, C1, ldx1, ldb1 = geom(x1)
-    B2, H2, W2, C2, ldx2, ldb2 = geom(x2)
+    B, H, W, C1, ldx1, ldb1 = _nhwc(x1)
+    B2, H2, W2, C2, ldx2, ldb2 = _nhwc(x2)
     assert (B, H, W) == (B2, H2, W2)
     w = _dev(w, "w")
     kh, kw, Cw, N = w.shape
     assert Cw == C1 + C2
     y = torch.empty((B, H, W, N), dtype=torch.float32, device=x1.device) if out is None else out
-    act = {None: 0, "linear": 0, "relu": 2}[activation]
     check(_lib.lib().fov_conv2d_fwd2(x1.data_ptr(), ldx1, ldb1, C1, x2.data_ptr(), ldx2, ldb2, C2, _ptr(w), _ptr(_dev(b, "b")),
-                                     None, _ptr(y), B, H, W, N, kh, kw, act, _stream()))
+                                     None, _ptr(y), B, H, W, N, kh, kw, _CONV_ACT[activation], _stream()))
     return y
+
+
+def _convlstm_cell(fwd, weights, x, h_prev, w, b, c_prev, h_out, act, c_new, gates, *dilation):
+    """The body convlstm_cell and convlstm_cell_bf16 share: every check, the c_new default and the launch through the
+    entry point `fwd`.  weights(Cw, F, kh, kw) -> the tensor `fwd` reads [K ; R] from, called once the shapes hold."""
+    B, H, W, C, ldx, ldb = _nhwc(x)
+    w = _dev(w, "w")
+    kh, kw, Cw, N = w.shape
+    F = N // 4
+    assert N == 4 * F
+    ldx2 = ldb2 = 0
+    if h_prev is not None:
+        B2, H2, W2, F2, ldx2, ldb2 = _nhwc(h_prev)
+        assert (B2, H2, W2, F2) == (B, H, W, F) and Cw == C + F
+    else:
+        assert Cw == C
+    wdev = weights(Cw, F, kh, kw)
+    c_prev = _dev(c_prev, "c_prev")
+    if c_new is None:
+        c_new = c_prev if c_prev is not None else torch.empty((B, H, W, F), dtype=torch.float32, device=x.device)
+    c_new = _dev(c_new, "c_new")
+    assert c_new.shape == (B, H, W, F) and (c_prev is None or c_prev.shape == c_new.shape)
+    assert h_out.is_cuda and h_out.dtype == torch.float32 and h_out.stride(-1) == 1 and h_out.shape == c_new.shape
+    assert h_out.stride(1) == W * h_out.stride(2) and (B == 1 or h_out.stride(0) == H * W * h_out.stride(2)), "h_out: uniform pixel stride"
+    if gates is not None:
+        gates = _dev(gates, "gates")
+        assert gates.shape == (B, H, W, N)
+    _sync_env()
+    check(fwd(x.data_ptr(), ldx, ldb, C, h_prev.data_ptr() if h_prev is not None else None, ldx2, ldb2, wdev.data_ptr(), _ptr(_dev(b, "b")),
+              _ptr(c_prev), _ptr(c_new), h_out.data_ptr(), h_out.stride(-2), _ptr(gates), B, H, W, F, kh, kw, *dilation,
+              act_code(act), _stream()))
+    return h_out, c_new
 
 
 def convlstm_cell(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new=None, gates=None, dilation=1):
@@ -1180,45 +1212,9 @@ def convlstm_cell(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new=None
     state; c_new defaults to updating c_prev in place; h_out may be a channel-slice view and must not be h_prev; gates
     (B,H,W,4F) receives the activated i,f,g,o when given (training tape).  dilation spreads the taps over x only, as Keras's
     ConvLSTM2D does (its recurrent convolution is never dilated)."""
-    def geom(t):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
-        B, H, W, C = t.shape
-        ldx = t.stride(2)
-        ldb = t.stride(0) if B > 1 else H * W * ldx
-        assert t.stride(1) == W * ldx and ldb >= H * W * ldx, "NHWC with a uniform pixel stride"
-        return B, H, W, C, ldx, ldb
-    B, H, W, C, ldx, ldb = geom(x)
-    w = _dev(w, "w")
-    kh, kw, Cw, N = w.shape
-    F = N // 4
-    assert N == 4 * F
-    ldx2 = ldb2 = 0
-    if h_prev is not None:
-        B2, H2, W2, F2, ldx2, ldb2 = geom(h_prev)
-        assert (B2, H2, W2, F2) == (B, H, W, F) and Cw == C + F
-    else:
-        assert Cw == C
-    c_prev = _dev(c_prev, "c_prev")
-    if c_new is None:
-        c_new = c_prev if c_prev is not None else torch.empty((B, H, W, F), dtype=torch.float32, device=x.device)
-    c_new = _dev(c_new, "c_new")
-    assert c_new.shape == (B, H, W, F) and (c_prev is None or c_prev.shape == c_new.shape)
-    assert h_out.is_cuda and h_out.dtype == torch.float32 and h_out.stride(-1) == 1 and h_out.shape == c_new.shape
-    assert h_out.stride(1) == W * h_out.stride(2) and (B == 1 or h_out.stride(0) == H * W * h_out.stride(2)), "h_out: uniform pixel stride"
-    if gates is not None:
-        gates = _dev(gates, "gates")
-        assert gates.shape == (B, H, W, N)
-    _sync_env()
-    if dilation != 1:
-        check(_lib.lib().fov_convlstm_cell_dilated_fwd(x.data_ptr(), ldx, ldb, C, h_prev.data_ptr() if h_prev is not None else None,
-                                                       ldx2, ldb2, _ptr(w), _ptr(_dev(b, "b")), _ptr(c_prev), _ptr(c_new),
-                                                       h_out.data_ptr(), h_out.stride(-2), _ptr(gates), B, H, W, F, kh, kw,
-                                                       int(dilation), act_code(act), _stream()))
-        return h_out, c_new
-    check(_lib.lib().fov_convlstm_cell_fwd(x.data_ptr(), ldx, ldb, C, h_prev.data_ptr() if h_prev is not None else None, ldx2, ldb2,
-                                           _ptr(w), _ptr(_dev(b, "b")), _ptr(c_prev), _ptr(c_new), h_out.data_ptr(),
-                                           h_out.stride(-2), _ptr(gates), B, H, W, F, kh, kw, act_code(act), _stream()))
-    return h_out, c_new
+    L = _lib.lib()
+    fwd, dil = (L.fov_convlstm_cell_dilated_fwd, (int(dilation),)) if dilation != 1 else (L.fov_convlstm_cell_fwd, ())
+    return _convlstm_cell(fwd, lambda *shape: w, x, h_prev, w, b, c_prev, h_out, act, c_new, gates, *dil)
 
 
 def convlstm_cell_pack_bf16(w):
@@ -1227,11 +1223,8 @@ def convlstm_cell_pack_bf16(w):
     fov_convlstm_cell_bf16_packed_bytes.  Pack once per set of weights; the layout is the library's own."""
     w = _dev(w, "w")
     assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous() and w.shape[3] % 4 == 0
-    kh, kw, Ctot, N = w.shape
     L = _lib.lib()
-    packed = torch.empty((int(L.fov_convlstm_cell_bf16_packed_bytes(Ctot, N // 4, kh, kw)),), dtype=torch.uint8, device=w.device)
-    check(L.fov_convlstm_cell_pack_bf16(_ptr(w), _ptr(packed), Ctot, N // 4, kh, kw, _stream()))
-    return packed
+    return _pack_bf16(w, 4, L.fov_convlstm_cell_bf16_packed_bytes, L.fov_convlstm_cell_pack_bf16)
 
 
 def convlstm_cell_bf16(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new=None, gates=None, packed=None):
@@ -1239,43 +1232,13 @@ def convlstm_cell_bf16(x, h_prev, w, b, c_prev, h_out, act="hard_sigmoid", c_new
     accumulation; bias, gates, cell update and everything stored in fp32 (inference of the ConvLSTM cells) -> (h_out, c_new).
     The arguments of convlstm_cell (no dilation); w the fp32 (kh,kw,C+F,4F) stack - it gives the shape -, packed =
     convlstm_cell_pack_bf16(w) when the caller keeps it (without it the call packs first)."""
-    def geom(t):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
-        B, H, W, C = t.shape
-        ldx = t.stride(2)
-        ldb = t.stride(0) if B > 1 else H * W * ldx
-        assert t.stride(1) == W * ldx and ldb >= H * W * ldx, "NHWC with a uniform pixel stride"
-        return B, H, W, C, ldx, ldb
-    B, H, W, C, ldx, ldb = geom(x)
-    w = _dev(w, "w")
-    kh, kw, Cw, N = w.shape
-    F = N // 4
-    assert N == 4 * F
-    ldx2 = ldb2 = 0
-    if h_prev is not None:
-        B2, H2, W2, F2, ldx2, ldb2 = geom(h_prev)
-        assert (B2, H2, W2, F2) == (B, H, W, F) and Cw == C + F
-    else:
-        assert Cw == C
     L = _lib.lib()
-    if packed is None:
-        packed = convlstm_cell_pack_bf16(w)
-    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.numel() == L.fov_convlstm_cell_bf16_packed_bytes(Cw, F, kh, kw)
-    c_prev = _dev(c_prev, "c_prev")
-    if c_new is None:
-        c_new = c_prev if c_prev is not None else torch.empty((B, H, W, F), dtype=torch.float32, device=x.device)
-    c_new = _dev(c_new, "c_new")
-    assert c_new.shape == (B, H, W, F) and (c_prev is None or c_prev.shape == c_new.shape)
-    assert h_out.is_cuda and h_out.dtype == torch.float32 and h_out.stride(-1) == 1 and h_out.shape == c_new.shape
-    assert h_out.stride(1) == W * h_out.stride(2) and (B == 1 or h_out.stride(0) == H * W * h_out.stride(2)), "h_out: uniform pixel stride"
-    if gates is not None:
-        gates = _dev(gates, "gates")
-        assert gates.shape == (B, H, W, N)
-    _sync_env()
-    check(L.fov_convlstm_cell_fwd_bf16(x.data_ptr(), ldx, ldb, C, h_prev.data_ptr() if h_prev is not None else None, ldx2, ldb2,
-                                       _ptr(packed), _ptr(_dev(b, "b")), _ptr(c_prev), _ptr(c_new), h_out.data_ptr(),
-                                       h_out.stride(-2), _ptr(gates), B, H, W, F, kh, kw, act_code(act), _stream()))
-    return h_out, c_new
+
+    def weights(*shape):
+        p = convlstm_cell_pack_bf16(w) if packed is None else packed
+        assert p.is_cuda and p.dtype == torch.uint8 and p.numel() == L.fov_convlstm_cell_bf16_packed_bytes(*shape)
+        return p
+    return _convlstm_cell(L.fov_convlstm_cell_fwd_bf16, weights, x, h_prev, w, b, c_prev, h_out, act, c_new, gates)
 
 
 def convlstm_gates(z, c, h_out, act="hard_sigmoid"):

@@ -1545,14 +1545,7 @@ class ConvLSTMTrainer(FlatParamTrainer):
 
         wt4 = {k: ops.conv2d_weight_transpose(v) for k, v in tp["k4"].items()}
         dense_head = self.head == "dense"
-        tgt = target.transpose(0, 1).contiguous()
-        if self.loss == "categorical_crossentropy":      # convlstm_heatmap.py:192
-            dP, loss = ops.categorical_crossentropy_grad(P, tgt, scratch=sc)
-        else:
-            dP, loss = ops.mse_dense_grad(P, tgt, None, scratch=sc)
-        if self.add_xyz_sum1:      # costfunc._mse, cost.py:23-28: + 0.5 * MSE(1, ux^2 + uy^2 + uz^2)
-            reg = ops.xyz_sum1_grad(P, dP, scratch=sc)
-            loss = ops.act_bwd(reg, reg, base=loss, activation=None)
+        dP, loss = self._loss(P, target.transpose(0, 1).contiguous())
         wt = {k: ops.conv2d_weight_transpose(w[k]) for k in self.order if k.endswith(("_K", "_R")) or
               (k.endswith("_W") and not dense_head)}
         nh = self.n_head
@@ -1646,17 +1639,20 @@ class ConvLSTMTrainer(FlatParamTrainer):
         loss = self._weigh(loss, grad_weight)
         return loss, P.transpose(0, 1)
 
-    def eval_loss(self, enc, dec0, target):
-        P, _ = self._forward(enc, dec0, target.shape[1])
-        tgt = target.transpose(0, 1).contiguous()
-        if self.loss == "categorical_crossentropy":
+    def _loss(self, P, tgt):
+        """Time-major prediction and target -> (dP = d loss / d P, loss (1,))."""
+        if self.loss == "categorical_crossentropy":      # convlstm_heatmap.py:192
             dP, loss = ops.categorical_crossentropy_grad(P, tgt, scratch=self.scratch)
         else:
             dP, loss = ops.mse_dense_grad(P, tgt, None, scratch=self.scratch)
-        if self.add_xyz_sum1:
+        if self.add_xyz_sum1:      # costfunc._mse, cost.py:23-28: + 0.5 * MSE(1, ux^2 + uy^2 + uz^2)
             reg = ops.xyz_sum1_grad(P, dP, scratch=self.scratch)
             loss = ops.act_bwd(reg, reg, base=loss, activation=None)
-        return loss
+        return dP, loss
+
+    def eval_loss(self, enc, dec0, target):
+        P, _ = self._forward(enc, dec0, target.shape[1])
+        return self._loss(P, target.transpose(0, 1).contiguous())[1]
 
 
 class TFLSTMTrainer(FlatParamTrainer):
