@@ -633,7 +633,7 @@ int fov_rmsprop_step_guarded(float* params, const float* grads, float* accum, in
  * between _begin and _end calls _flush before.  Writers covered: fov_lstm_seq_bwd(_bf16), fov_lstm_seq_wgrad,
  * fov_lstm_seq_wgrad_pair, fov_lstm_stack2_bwd, fov_dense_bwd(_bf16), fov_wgrad_fused, fov_colsum, fov_mix_head_wgrad,
  * fov_mse_dense_grad_db / _w (db), fov_dense_mse_head, fov_mlp_head_bwd, fov_tf_head_bwd, fov_conv2d_wgrad,
- * fov_conv2d_dilated_wgrad, in every kernel form and in their empty-shape zeroing; readers covered (they
+ * fov_conv2d_dilated_wgrad, fov_conv2d_wgrad_bf16, in every kernel form and in their empty-shape zeroing; readers covered (they
  * flush over the gradients they read): fov_adam_step(_guarded), fov_rmsprop_step(_guarded), fov_rmsprop_tf_step(_guarded).
  * A region is KEYED BY ITS GRADIENT BUFFER: each caller (trainer, thread, stream, device) opens its own with _begin and names
  * it again by grad_base (any address inside the buffer) in _flush / _end; regions of different buffers share nothing - their
@@ -763,6 +763,25 @@ size_t fov_conv2d_wgrad_workspace_bytes(int C, int N, int kh, int kw);
 int fov_conv2d_wgrad(const float* x, int64_t x_pixel_stride, const float* dy, float* dw, int B, int H, int W,
                      int C, int N, int kh, int kw, int accumulate, void* workspace, size_t workspace_bytes,
                      fov_stream_t stream);
+
+/* fov_conv2d_wgrad with bf16 matrix-core operands - training of the Conv2D / Conv1D prediction head
+ * (convlstm_seq2seq.py:176-181,231-238 under model.fit).  Arithmetic contract:
+ *     dw[i][j][c][n] (+)= sum over the B*H*W pixels p of  bf16(x[p + tap(i,j)][c]) * bf16(dy[p][n])
+ * both operands rounded to bf16 round-to-nearest-even, products accumulated in fp32 in an order the kernel chooses.
+ * Unlike fov_conv2d_wgrad the tuned form multiplies the zero padding in: a non-finite x[.][c] makes every tap of channel c
+ * non-finite, and a non-finite dy[.][n] every tap of output n, where the exact sum would skip the terms outside the image.  dw fp32 in the Keras (kh,kw,C,N) layout.  'same' zero padding,
+ * stride 1, odd kh, kw, dilation 1.  x: batch-dense NHWC with pixel stride x_pixel_stride >= C; dy (B*H*W, N) with rows
+ * dy_row_stride >= N floats apart (N for a dense dy; a trainer that keeps dy in a channel-padded buffer passes the view).
+ * accumulate as in fov_conv2d_wgrad; the empty batch writes zeros (accumulate = 0) or leaves dw alone.  Any split is
+ * deterministic (partial slices in the workspace - or in the arena of an open deferred region that holds dw -, fixed-order
+ * reduce); results are bit-identical inside and outside a region.  workspace >= fov_conv2d_wgrad_bf16_workspace_bytes
+ * (FOV_ERR_WORKSPACE otherwise).  x and dy may be larger than 2 GiB as a whole (the trainer's one product over all decoder steps
+ * is): the maps are cut into slices of at most 2 GiB each; FOV_ERR_UNSUPPORTED only where one map alone exceeds 2 GiB or the
+ * workspace cannot hold that many slices. */
+size_t fov_conv2d_wgrad_bf16_workspace_bytes(int C, int N, int kh, int kw);
+int fov_conv2d_wgrad_bf16(const float* x, int64_t x_pixel_stride, const float* dy, int64_t dy_row_stride, float* dw, int B, int H,
+                          int W, int C, int N, int kh, int kw, int accumulate, void* workspace, size_t workspace_bytes,
+                          fov_stream_t stream);
 
 /* The same three with a dilation (Keras `dilation_rate`; cfg.dilation_rate of mycode/config.py:105 reaches the six ConvLSTM2D
  * layers of mycode/convlstm_seq2seq.py:100-126,146-165): tap (i, j) reads the pixel (i - kh/2, j - kw/2) * dilation away, 'same'

@@ -131,6 +131,8 @@ SIGNATURES = {
     "fov_convlstm_gates_bwd": (_I, [_P, ctypes.c_int64] + [_P] * 5 + [ctypes.c_int64, _I, _I, _P]),
     "fov_conv2d_wgrad_workspace_bytes": (_SZ, [_I] * 4),
     "fov_conv2d_wgrad": (_I, [_P, ctypes.c_int64, _P, _P] + [_I] * 8 + [_P, _SZ, _P]),
+    "fov_conv2d_wgrad_bf16_workspace_bytes": (_SZ, [_I] * 4),
+    "fov_conv2d_wgrad_bf16": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P] + [_I] * 8 + [_P, _SZ, _P]),
     "fov_conv2d_weight_transpose": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "fov_softmax_lastdim_bwd": (_I, [_P] * 3 + [ctypes.c_int64, _I, _P]),
     "fov_colsum": (_I, [_P, _P, ctypes.c_int64, _I, _I, _P, _SZ, _P]),

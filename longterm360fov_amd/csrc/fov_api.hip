@@ -455,6 +455,7 @@ void env_reload() {
     g_env.gemm_bf16_shallow = getenv("FOV_GEMM_BF16_SHALLOW") ? 1 : 0;
     g_env.no_wgrad_group = getenv("FOV_NO_WGRAD_GROUP") ? 1 : 0;
     g_env.no_wgrad_lines = getenv("FOV_NO_WGRAD_LINES") ? 1 : 0;
+    g_env.no_wgrad_bf16_tiles = env_flag("FOV_NO_WGRAD_BF16_TILES");
     g_env.no_wide16_trio = getenv("FOV_NO_WIDE16_TRIO") ? 1 : 0;
     g_env.dbg_trace = getenv("FOV_DBG_TRACE") ? 1 : 0;
     const char* gb = getenv("FOV_GEMM_BF16_SPLIT");
@@ -1721,6 +1722,24 @@ int fov_conv2d_wgrad(const float* x, int64_t x_pixel_stride, const float* dy, fl
     if (workspace && (((uintptr_t)workspace) & 15)) { set_error("workspace must be 16-byte aligned"); return FOV_ERR_WORKSPACE; }
     return conv2d_wgrad(x, (long)x_pixel_stride, dy, dw, B, H, W, C, N, kh, kw, accumulate, (float*)workspace,
                         workspace ? workspace_bytes / sizeof(float) : 0, (hipStream_t)stream);
+}
+
+size_t fov_conv2d_wgrad_bf16_workspace_bytes(int C, int N, int kh, int kw) {
+    if (C <= 0 || N <= 0 || kh <= 0 || kw <= 0) return 256;
+    return sizeof(float) * conv2d_wgrad_bf16_workspace_floats(C, N, kh, kw);
+}
+
+int fov_conv2d_wgrad_bf16(const float* x, int64_t x_pixel_stride, const float* dy, int64_t dy_row_stride, float* dw, int B, int H,
+                          int W, int C, int N, int kh, int kw, int accumulate, void* workspace, size_t workspace_bytes,
+                          fov_stream_t stream) {
+    if (B < 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || kh <= 0 || kw <= 0 || (kh & 1) == 0 || (kw & 1) == 0 ||
+        x_pixel_stride < C || dy_row_stride < N || !dw || (B > 0 && (!x || !dy))) {
+        set_error("fov_conv2d_wgrad_bf16: invalid argument (odd kernel sizes only)");
+        return FOV_ERR_INVALID;
+    }
+    if (int rc = check_ws(workspace, workspace_bytes, fov_conv2d_wgrad_bf16_workspace_bytes(C, N, kh, kw))) return rc;
+    return conv2d_wgrad_bf16(x, (long)x_pixel_stride, dy, (long)dy_row_stride, dw, B, H, W, C, N, kh, kw, accumulate,
+                             (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 int fov_conv2d_dilated_wgrad(const float* x, int64_t x_pixel_stride, const float* dy, float* dw, int B, int H, int W, int C, int N,

@@ -88,6 +88,7 @@ struct EnvKnobs {
     int no_bwd16_narrow; // FOV_NO_BWD16_NARROW=1: widths 128 / 256 keep the 2- / 4- / 8-workgroup BPTT kernels at small batches
     int bwd16_groups32;  // FOV_BWD16_GROUPS=32: width-512 BPTT on thirty-two workgroups per tile up to eight tiles (default: sixteen)
     int no_stack2;       // FOV_NO_STACK2=1: two stacked width-512 layers as two launches (fov_lstm_stack2_supported -> 0)
+    int no_wgrad_bf16_tiles;   // FOV_NO_WGRAD_BF16_TILES=1: the bf16 Conv2D weight gradient on its plain kernel (tests; conv_wgrad_bf16.hip)
 };
 const EnvKnobs& env_knobs();
 void env_reload();
@@ -163,6 +164,10 @@ int conv_wgrad_lines(const float* x, long ldx, const float* dz, float* dw, int B
 size_t conv2d_wgrad_workspace_floats(int C, int N, int kh, int kw);
 int conv2d_wgrad(const float* x, long ldx, const float* dz, float* dw, int B, int H, int W, int C, int N, int kh, int kw,
                  int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream, int dil = 1);
+// the same product with bf16 matrix-core operands (conv_wgrad_bf16.hip): dy rows ldy floats apart; scratch >= the workspace floats
+size_t conv2d_wgrad_bf16_workspace_floats(int C, int N, int kh, int kw);
+int conv2d_wgrad_bf16(const float* x, long ldx, const float* dy, long ldy, float* dw, int B, int H, int W, int C, int N, int kh, int kw,
+                      int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream);
 int convlstm_gates_train(const float* z, const float* c_prev, float* c_new, float* h, long ldh, float* gates, long rows, int F,
                          int act, hipStream_t stream);
 int convlstm_gates_bwd(const float* dh, long lddh, float* dc, const float* gates, const float* c_prev, const float* c_new,

@@ -1327,7 +1327,12 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                     Flatten + Dense(6, linear), output (N,T_out,6) fed back as the next 1x1x6 input map
     dtype 'bf16' (heads 'conv2d' / 'conv1d', inference only): the three head convolutions run with bf16 matrix-core operands
     and fp32 accumulation (ops.conv2d_bf16) on weights packed once per set of weights; the ConvLSTM cells, the softmax, all
-    stored tensors and the weights the model holds stay fp32.  Train an fp32 model and hand its get_weights() to a bf16 one.
+    stored tensors and the weights the model holds stay fp32.  Train an fp32 model and hand its get_weights() to a bf16 one,
+    or opt into bf16 training of the head:
+    train_dtype None (default: every call behaves as it did before the keyword existed) | 'f32' | 'bf16'.  'bf16' needs
+    dtype='bf16' (and 'f32' dtype='f32': one arithmetic for fit's val_loss, eval_loss and predict) and a convolutional head;
+    the trainer then runs the head's forward, data gradient and weight gradient with bf16 operands (ConvLSTMTrainer
+    head_dtype='bf16'), everything else in fp32.
     cell_dtype 'bf16' (every head, inference only, dilation_rate 1; independent of dtype): the six ConvLSTM2D layers run with
     bf16 matrix-core operands and fp32 accumulation (ops.convlstm_cell_bf16) on [K ; R] stacks packed once per set of weights;
     gates, cell update, h, c and every other consumer of h stay fp32.
@@ -1341,7 +1346,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
     _default_optimizer = "rmsprop"      # convlstm_seq2seq.py:287
 
     def __init__(self, weights, head="conv2d", recurrent_activation="hard_sigmoid", device="cuda", dropout_rate=0.0,
-                 add_xyz_sum1=None, dilation_rate=None, dtype="f32", cell_dtype="f32"):
+                 add_xyz_sum1=None, dilation_rate=None, dtype="f32", cell_dtype="f32", train_dtype=None):
         from .training import convlstm_weight_order
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
@@ -1349,7 +1354,14 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             raise ValueError("cell_dtype must be 'f32' or 'bf16'")
         if dtype == "bf16" and head == "dense":
             raise ValueError("dtype='bf16' needs a convolutional head ('conv2d' / 'conv1d'): the 'dense' head is one small Dense")
-        self.dtype, self.cell_dtype = dtype, cell_dtype
+        if train_dtype not in (None, "f32", "bf16"):
+            raise ValueError("train_dtype must be None, 'f32' or 'bf16'")
+        if train_dtype == "bf16" and head == "dense":
+            raise ValueError("train_dtype='bf16' needs a convolutional head ('conv2d' / 'conv1d'): the 'dense' head is one small Dense")
+        if train_dtype is not None and train_dtype != dtype:
+            raise ValueError("train_dtype=%r needs dtype=%r: the head trains in the arithmetic predict runs, so that val_loss, "
+                             "eval_loss and predict agree" % (train_dtype, train_dtype))
+        self.dtype, self.cell_dtype, self.train_dtype = dtype, cell_dtype, train_dtype
         self.add_xyz_sum1 = bool(cfg.add_xyz_sum1 if add_xyz_sum1 is None else add_xyz_sum1)
         # cfg.dilation_rate (config.py:105) -> the six ConvLSTM2D layers' input convolutions (:102,110,120,148,155,162)
         self.dilation_rate = int(cfg.dilation_rate if dilation_rate is None else dilation_rate)
@@ -1374,7 +1386,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         self._trainer = None
 
     def _make_trainer(self, optimizer):
-        if self.dtype == "bf16":
+        if self.dtype == "bf16" and self.train_dtype != "bf16":
             raise NotImplementedError("ConvLSTMSeq2Seq(dtype='bf16') is inference only: train a dtype='f32' model and hand its "
                                       "get_weights() to a bf16 one")
         if self.cell_dtype == "bf16":
@@ -1383,7 +1395,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         from .training import ConvLSTMTrainer
         return ConvLSTMTrainer(self._w, head=self.head, act=self.act, optimizer=optimizer, lr=self._lr, device=self.device,
                                dropout_rate=self.dropout_rate, add_xyz_sum1=self.add_xyz_sum1, loss=self.loss or "mse",
-                               dilation_rate=self.dilation_rate)
+                               dilation_rate=self.dilation_rate, **({"head_dtype": "bf16"} if self.train_dtype == "bf16" else {}))
 
     def _output_shape(self, T_out, H, W):
         """What a prediction has after its leading N."""

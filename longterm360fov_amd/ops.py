@@ -52,7 +52,7 @@ def _stream():
 
 _ENV_KNOBS = ("FOV_FORCE_SAFE_EXCHANGE", "FOV_TWO_LAUNCHES", "FOV_DBG_RESIDENT_LIMIT", "FOV_NO_CELL_PATCH", "FOV_NO_CONV_PATCH", "FOV_NO_WIDE16", "FOV_BWD_STEPPED",
               "FOV_NO_WGRAD_FUSION", "FOV_NO_DX_FUSION", "FOV_BWD_GROUPS4", "FOV_GEMM_BF16_NOREMAP", "FOV_GEMM_BF16_SPLIT", "FOV_GEMM_BF16_SHALLOW", "FOV_NO_WGRAD_GROUP", "FOV_NO_WIDE16_TRIO", "FOV_DBG_TRACE", "FOV_GEMM_VARIANT",
-              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES")
+              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES")
 _env_seen = None
 # os.environ.get costs 0.7 us per key (encode, lookup, decode): 9 us for the knob list, paid at every workspace / scratch
 # fetch - 0.15 ms of a 0.3 ms training step at batch 32.  The mapping underneath (bytes -> bytes on POSIX) answers the
@@ -1287,9 +1287,9 @@ def convlstm_gates_bwd(dh, dc, gates, c_prev, c_new, act="hard_sigmoid", dz=None
     return dz
 
 
-def conv2d_wgrad(x, dy, kh, kw, dw=None, accumulate=False, scratch=None, dilation=1):
-    """dw (kh,kw,C,N) (+)= weight gradient of y = conv2d_same(x, w).  x: batch-dense NHWC (leading dims are
-    flattened into the batch; the last dim may be a channel slice of a wider map); dy (..., N) dense."""
+def _conv2d_wgrad(x, dy, kh, kw, dw, scratch, workspace_bytes, dense_dy=True):
+    """The checks conv2d_wgrad and conv2d_wgrad_bf16 share -> (B, H, W, C, N, ldx, ldy, dy, dw, workspace).  dense_dy = False
+    admits a dy whose rows are a channel slice of a wider buffer (uniform row stride)."""
     assert x.is_cuda and x.dtype == torch.float32 and x.stride(-1) == 1
     H, W, C = x.shape[-3:]
     ldx = x.stride(-2)
@@ -1298,19 +1298,57 @@ def conv2d_wgrad(x, dy, kh, kw, dw=None, accumulate=False, scratch=None, dilatio
     for i in range(x.dim() - 3, -1, -1):
         assert x.shape[i] == 1 or x.stride(i) == expect, "x must be batch-dense NHWC"
         expect *= x.shape[i]
-    dy = _dev(dy, "dy")
     N = dy.shape[-1]
+    if dense_dy:
+        dy = _dev(dy, "dy")
+        ldy = N
+    else:
+        assert dy.is_cuda and dy.dtype == torch.float32 and dy.stride(-1) == 1
+        ldy = expect = dy.stride(-2) if dy.dim() > 1 else N
+        for i in range(dy.dim() - 2, -1, -1):
+            assert dy.shape[i] == 1 or dy.stride(i) == expect, "dy must have a uniform row stride"
+            expect *= dy.shape[i]
     assert dy.numel() == B * H * W * N
     dw = torch.empty((kh, kw, C, N), dtype=torch.float32, device=x.device) if dw is None else dw
+    buf = (scratch or _default_scratch).get(workspace_bytes(C, N, kh, kw), x.device)
+    return B, H, W, C, N, ldx, ldy, dy, dw, buf
+
+
+def conv2d_wgrad(x, dy, kh, kw, dw=None, accumulate=False, scratch=None, dilation=1):
+    """dw (kh,kw,C,N) (+)= weight gradient of y = conv2d_same(x, w).  x: batch-dense NHWC (leading dims are
+    flattened into the batch; the last dim may be a channel slice of a wider map); dy (..., N) dense."""
     L = _lib.lib()
-    buf = (scratch or _default_scratch).get(L.fov_conv2d_wgrad_workspace_bytes(C, N, kh, kw), x.device)
-    if dilation != 1:
-        check(L.fov_conv2d_dilated_wgrad(x.data_ptr(), ldx, _ptr(dy), _ptr(dw), B, H, W, C, N, kh, kw, int(dilation),
-                                         1 if accumulate else 0, buf.data_ptr(), buf.numel(), _stream()))
-        return dw
-    check(L.fov_conv2d_wgrad(x.data_ptr(), ldx, _ptr(dy), _ptr(dw), B, H, W, C, N, kh, kw, 1 if accumulate else 0,
-                             buf.data_ptr(), buf.numel(), _stream()))
+    B, H, W, C, N, ldx, _, dy, dw, buf = _conv2d_wgrad(x, dy, kh, kw, dw, scratch, L.fov_conv2d_wgrad_workspace_bytes)
+    wgrad, dil = (L.fov_conv2d_dilated_wgrad, (int(dilation),)) if dilation != 1 else (L.fov_conv2d_wgrad, ())
+    check(wgrad(x.data_ptr(), ldx, _ptr(dy), _ptr(dw), B, H, W, C, N, kh, kw, *dil, 1 if accumulate else 0, buf.data_ptr(),
+                buf.numel(), _stream()))
     return dw
+
+
+def conv2d_wgrad_bf16(x, dy, kh, kw, dw=None, accumulate=False, scratch=None):
+    """conv2d_wgrad with bf16 matrix-core operands: dw (kh,kw,C,N) (+)= sum over the pixels of bf16(x[pixel + tap]) *
+    bf16(dy[pixel]), fp32 accumulation, dw fp32 (training of the ConvLSTM head).  x as in conv2d_wgrad; dy (..., N) may be
+    the leading-channel view of a wider buffer (uniform row stride).  No dilated form."""
+    L = _lib.lib()
+    B, H, W, C, N, ldx, ldy, dy, dw, buf = _conv2d_wgrad(x, dy, kh, kw, dw, scratch, L.fov_conv2d_wgrad_bf16_workspace_bytes,
+                                                         dense_dy=False)
+    check(L.fov_conv2d_wgrad_bf16(x.data_ptr(), ldx, dy.data_ptr(), ldy, _ptr(dw), B, H, W, C, N, kh, kw, 1 if accumulate else 0,
+                                  buf.data_ptr(), buf.numel(), _stream()))
+    return dw
+
+
+def conv2d_bwd_data_pack_bf16(w, pad_in=0):
+    """The kernel of the data gradient of y = conv2d_same(x, w), packed for conv2d_bf16: w (kh,kw,C,N) is flipped and
+    transposed into a scratch tensor (kh,kw,N + pad_in,C) - pad_in zero rows for a dy the caller keeps channel-padded - and
+    rounded by conv2d_pack_bf16.  -> (wt, packed): dx = conv2d_bf16(dy, wt, packed=packed)."""
+    w = _dev(w, "w")
+    kh, kw, C, N = w.shape
+    if pad_in:
+        wt = torch.zeros((kh, kw, N + pad_in, C), dtype=torch.float32, device=w.device)
+        wt[:, :, :N].copy_(conv2d_weight_transpose(w))
+    else:
+        wt = conv2d_weight_transpose(w)
+    return wt, conv2d_pack_bf16(wt)
 
 
 def conv2d_weight_transpose(w, out=None):

@@ -1404,10 +1404,24 @@ class ConvLSTMTrainer(FlatParamTrainer):
     dilation_rate (cfg.dilation_rate, convlstm_seq2seq.py:102,110,120,148,155,162): Keras's ConvLSTM2DCell passes it to the
     input convolution only (`input_conv(..., dilation_rate=self.dilation_rate)`; `recurrent_conv` has none), so K's taps are
     spread, R's are not; the head's Conv2D layers are not dilated.  Backward: dx through the dilated convolution with the
-    transposed K, dK through the dilated weight gradient."""
+    transposed K, dK through the dilated weight gradient.
+
+    head_dtype 'bf16' (heads 'conv2d' / 'conv1d'): the three products of every head layer - forward (ops.conv2d_bf16), data
+    gradient (ops.conv2d_bf16 on the flipped, transposed kernel) and weight gradient (ops.conv2d_wgrad_bf16) - take both
+    operands rounded to bf16 and accumulate in fp32.  Cells, gates, softmax and relu backward, losses, bias gradients, tapes,
+    master weights, optimizer and the flat gradient buffer stay fp32.  The packed kernels are rebuilt from the fp32 master
+    weights in every _forward (forward packs) and forward_backward (transposed packs): nothing to invalidate after an
+    optimizer step or set_weights.  The last layer's dy (30 channels at the heat maps) is kept in a buffer padded to a multiple
+    of 4 channels where that lifts its data gradient onto the map-resident forward kernel (>= 32 channels): zero pad channels,
+    zero rows in the transposed kernel; weight and bias gradient read the unpadded view."""
 
     def __init__(self, weights, head="conv2d", act="hard_sigmoid", optimizer="rmsprop", lr=1e-3, device="cuda",
-                 dropout_rate=0.0, seed=0, add_xyz_sum1=False, loss="mse", dilation_rate=1):
+                 dropout_rate=0.0, seed=0, add_xyz_sum1=False, loss="mse", dilation_rate=1, head_dtype="f32"):
+        if head_dtype not in ("f32", "bf16"):
+            raise ValueError("head_dtype must be 'f32' or 'bf16'")
+        if head_dtype == "bf16" and head == "dense":
+            raise ValueError("head_dtype='bf16' needs a convolutional head ('conv2d' / 'conv1d'): the 'dense' head is one small Dense")
+        self.head_dtype = head_dtype
         if not 0.0 <= dropout_rate < 1.0:
             raise ValueError("dropout_rate must be in [0, 1)")
         if int(dilation_rate) < 1:
@@ -1492,6 +1506,11 @@ class ConvLSTMTrainer(FlatParamTrainer):
         cin = [C] + F[:2]
         dx4 = [e(T_out, B, H, W, 4 * cin[l]) for l in range(3)] if masks is not None else None
         kr = [torch.cat([k4["dec%d_K" % l] if masks is not None else w["dec%d_K" % l], w["dec%d_R" % l]], 2) for l in range(3)]
+        if self.head_dtype == "bf16":   # the head's kernels rounded from the master weights of THIS step
+            hp = [ops.conv2d_pack_bf16(w["head%d_W" % i]) for i in range(self.n_head)]
+            head_conv = lambda y, i, a, out: ops.conv2d_bf16(y, w["head%d_W" % i], w["head%d_b" % i], activation=a, out=out, packed=hp[i])
+        else:
+            head_conv = lambda y, i, a, out: ops.conv2d(y, w["head%d_W" % i], w["head%d_b" % i], activation=a, out=out)
         for t in range(T_out):
             cur = inp[t]
             for l in range(3):
@@ -1510,7 +1529,7 @@ class ConvLSTMTrainer(FlatParamTrainer):
                 y = feat[t]
                 for i in range(self.n_head):
                     a = "relu" if i < self.n_head - 1 else last_act
-                    y = ops.conv2d(y, w["head%d_W" % i], w["head%d_b" % i], activation=a, out=ys[i][t])
+                    y = head_conv(y, i, a, ys[i][t])
                 ops.softmax_lastdim(y, out=P[t])
             if t + 1 < T_out:
                 assert P[t].numel() == inp[t + 1].numel(), "the head's output is fed back as the next decoder input"
@@ -1546,10 +1565,24 @@ class ConvLSTMTrainer(FlatParamTrainer):
         wt4 = {k: ops.conv2d_weight_transpose(v) for k, v in tp["k4"].items()}
         dense_head = self.head == "dense"
         dP, loss = self._loss(P, target.transpose(0, 1).contiguous())
+        bf16_head = self.head_dtype == "bf16"
         wt = {k: ops.conv2d_weight_transpose(w[k]) for k in self.order if k.endswith(("_K", "_R")) or
-              (k.endswith("_W") and not dense_head)}
+              (k.endswith("_W") and not dense_head and not bf16_head)}
         nh = self.n_head
         dys = [torch.empty_like(y) for y in tp["ys"]]                    # d(pre-activation) of every head layer
+        if bf16_head:
+            # the last layer's dy in a channel-padded buffer when that puts its data gradient on the map-resident kernel
+            n_last = dys[nh - 1].shape[-1]
+            pad = (-n_last) % 4 if n_last + (-n_last) % 4 >= 32 else 0
+            if pad:
+                dlast = torch.zeros(dys[nh - 1].shape[:-1] + (n_last + pad,), dtype=torch.float32, device=enc.device)
+                dtmp = torch.empty_like(dys[nh - 1][0])
+                dys[nh - 1] = dlast[..., :n_last]
+            wtp = [ops.conv2d_bwd_data_pack_bf16(w["head%d_W" % i], pad if i == nh - 1 else 0) for i in range(nh)]
+            head_dx = lambda d, i, out=None: ops.conv2d_bf16(d, wtp[i][0], out=out, packed=wtp[i][1])
+        else:
+            pad = 0
+            head_dx = lambda d, i, out=None: ops.conv2d(d, wt["head%d_W" % i], out=out)
         dzs = [torch.empty_like(x) for x in tp["dg"]]                    # decoder dz, all steps
         zeros = lambda l: torch.zeros((B, H, W, F[l]), dtype=torch.float32, device=enc.device)
         dh_rec, dc = [zeros(l) for l in range(3)], [zeros(l) for l in range(3)]
@@ -1562,13 +1595,16 @@ class ConvLSTMTrainer(FlatParamTrainer):
                 dfeat, _, _ = ops.dense_bwd(feat[t].reshape(B, -1), w["head0_W"], dP[t], need_dW=False, need_db=False, scratch=sc)
                 dfeat = dfeat.reshape(B, H, W, -1)
             else:
-                d = ops.softmax_lastdim_bwd(dp, P[t], out=dys[nh - 1][t])
+                d = ops.softmax_lastdim_bwd(dp, P[t], out=dtmp if pad else dys[nh - 1][t])
                 if tp["last_act"] == "relu":
                     ops.act_bwd(d, tp["ys"][nh - 1][t], activation="relu", out=d)
+                if pad:                                                  # into the padded buffer; its pad channels stay zero
+                    dys[nh - 1][t].copy_(d)
+                    d = dlast[t]
                 for i in range(nh - 1, 0, -1):                           # head layers, data gradient only
-                    d = ops.conv2d(d, wt["head%d_W" % i], out=dys[i - 1][t])
+                    d = head_dx(d, i, dys[i - 1][t])
                     ops.act_bwd(d, tp["ys"][i - 1][t], activation="relu", out=d)
-                dfeat = ops.conv2d(d, wt["head0_W"])
+                dfeat = head_dx(d, 0)
             dx_up = None
             for l in range(2, -1, -1):
                 dh = dfeat[..., offs[l]:offs[l] + F[l]] + dh_rec[l]
@@ -1592,8 +1628,14 @@ class ConvLSTMTrainer(FlatParamTrainer):
             ops.dense_bwd(feat.reshape(T_out * B, -1), w["head0_W"], dP.reshape(T_out * B, -1), dW=g["head0_W"], db=g["head0_b"],
                           need_dx=False, scratch=sc)
         for i in range(0 if dense_head else nh):
-            ops.conv2d_wgrad(x_in, dys[i], *w["head%d_W" % i].shape[:2], dw=g["head%d_W" % i], scratch=sc)
-            ops.colsum(dys[i], out=g["head%d_b" % i], scratch=sc)
+            if bf16_head:
+                ops.conv2d_wgrad_bf16(x_in, dys[i], *w["head%d_W" % i].shape[:2], dw=g["head%d_W" % i], scratch=sc)
+            else:
+                ops.conv2d_wgrad(x_in, dys[i], *w["head%d_W" % i].shape[:2], dw=g["head%d_W" % i], scratch=sc)
+            if pad and i == nh - 1:     # column sums of the padded buffer; the pad columns sum to zero and are dropped
+                g["head%d_b" % i].copy_(ops.colsum(dlast, scratch=sc)[:dys[i].shape[-1]])
+            else:
+                ops.colsum(dys[i], out=g["head%d_b" % i], scratch=sc)
             x_in = tp["ys"][i]
         # decoder cells
         for l in range(3):
