@@ -16,6 +16,7 @@
 // 32-lane half touches contiguous: with a row stride of 72 dwords every transposed read is bank-conflict-free.
 // Both kernels are HBM/L2-bound at the sizes of this path (a 5120 x 256 x 1024 product is 2.7 GFLOP = 1 us of bf16
 // matrix time against 26 MB of fp32 operands).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "bf16_common.h"
@@ -593,6 +594,9 @@ int gemm_bf16_tn_fused(const float* a1, long lda1, long a1_so, int M1, int shift
     g.grid_m = (M + GT - 1) / GT;
     g.xcd_remap = (split >= 8 && !env_knobs().gemm_bf16_noremap) ? 1 : 0;
     const dim3 grid = g.xcd_remap ? dim3((unsigned)(8 * ((split + 7) / 8) * g.grid_n * g.grid_m)) : dim3(g.grid_n, g.grid_m, split);
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] gemm_bf16_tn next: M=%d N=%d RO=%d RI=%d form=%s avec=%d split=%d rows_per_split=%ld remap=%d a2=%d shifts=%d/%d bias=%d add_c=%d\n",
+                M, N, RO, RI, deep ? "deep" : "shallow", (int)avec, split, rps, g.xcd_remap, a2 ? 1 : 0, shift1 ? 1 : 0, shift2 ? 1 : 0, g.bias_row, g.add_c);
     if (deep && avec) hipLaunchKernelGGL(gemm_bf16_tn3_kernel<true>, grid, dim3(G3T), 0, stream, g);
     else if (deep) hipLaunchKernelGGL(gemm_bf16_tn3_kernel<false>, grid, dim3(G3T), 0, stream, g);
     else if (avec) hipLaunchKernelGGL(gemm_bf16_tn_kernel<true>, grid, dim3(256), 0, stream, g);

@@ -1551,6 +1551,7 @@ static int skinny_tn(const float* S, long ss, int ns, const float* Wd, long ldw,
     const dim3 grid(colblocks, (unsigned)chunks);
     bool deferred = false;
     if (float* arena = defer_alloc(out, n, (size_t)chunks * n, stream)) { scratch = arena; deferred = true; }
+    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] skinny_tn next: ns=%d nw=%d rows=%ld vec=%d chunks=%ld\n", ns, nw, rows, (int)vec, chunks);
 #define FOV_SKINNY(NSV)                                                                                                       \
     case NSV:                                                                                                                 \
         if (vec) hipLaunchKernelGGL((skinny_tn_kernel<NSV, 4>), grid, dim3(256), 0, stream, S, ss, Wd, ldw, scratch, rows, nw, \
