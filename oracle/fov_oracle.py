@@ -621,6 +621,242 @@ def rmsprop_step(p, g, a, lr=1e-3, rho=0.9, eps=1e-7):
 
 
 # --------------------------------------------------------------------------------------
+# Loss / optimizer / pointwise references of tests/test_gpu_loss_optim_edges.py.  Every one is fp64 arithmetic ON THE
+# fp32-ROUNDED inputs and hyper-parameters (r32): the kernels form 1.f - beta in fp32, and 1 - float32(0.999) is 1.3e-5 away
+# from 1 - 0.999.  Next to each result comes the sum of the |terms| that make up each element, the weight of the
+# per-element bound  |err| <= c * 2^-24 * weight  (a max|ref| scale would hide an error in an ordinary element).
+# --------------------------------------------------------------------------------------
+U24 = 2.0 ** -24
+
+
+def r32(x):
+    """The fp64 value of x after rounding to fp32 (what a kernel's float argument holds)."""
+    return float(np.float32(x))
+
+
+def _d(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def adam_lr_t(t, lr=1e-3, beta1=0.9, beta2=0.999):
+    """The step size the library hands its Adam kernels: double arithmetic on the float arguments, rounded to float."""
+    return r32(r32(lr) * np.sqrt(1.0 - r32(beta2) ** t) / (1.0 - r32(beta1) ** t))
+
+
+def adam_step_f32args(p, g, m, v, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, exact_betas=False):
+    """One Adam step in fp64 from fp32 state with fp32-rounded hyper-parameters -> (p, m, v) and the weights of their bounds
+    (p: |p| + |update|, m / v: their |terms|, upd: |update|, upd_m: what an error of m of one weight does to the update).
+    exact_betas: the plain fp64 hyper-parameters instead (the reference the tests must be able to tell apart)."""
+    p, g, m, v = _d(p), _d(g), _d(m), _d(v)
+    if exact_betas:
+        b1, b2, e = beta1, beta2, eps
+        lr_t = lr * np.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
+    else:
+        b1, b2, e, lr_t = r32(beta1), r32(beta2), r32(eps), adam_lr_t(t, lr, beta1, beta2)
+    mn = b1 * m + (1 - b1) * g
+    vn = b2 * v + (1 - b2) * g * g
+    den = np.sqrt(vn) + e
+    upd = lr_t * mn / den
+    wm = np.abs(b1 * m) + np.abs((1 - b1) * g)
+    return (p - upd, mn, vn), {"p": np.abs(p) + np.abs(upd), "m": wm, "v": vn, "upd": np.abs(upd), "upd_m": lr_t * wm / den}
+
+
+def rmsprop_step_f32args(p, g, a, lr=1e-3, rho=0.9, eps=1e-7):
+    """Keras RMSprop, as adam_step_f32args -> (p, a), weights p / a / upd."""
+    p, g, a = _d(p), _d(g), _d(a)
+    lr, rho, eps = r32(lr), r32(rho), r32(eps)
+    an = rho * a + (1 - rho) * g * g
+    upd = lr * g / (np.sqrt(an) + eps)
+    return (p - upd, an), {"p": np.abs(p) + np.abs(upd), "a": an, "upd": np.abs(upd)}
+
+
+def rmsprop_tf_step(p, g, ms, lr, decay=0.9, eps=1e-10, clip=0.0):
+    """tf.train.RMSPropOptimizer (TF 1.x, momentum 0, not centered) after clip_by_value(g, -clip, clip) (clip 0: none):
+    ms = decay*ms + (1-decay) g^2;  p -= lr * g / sqrt(ms + eps) - eps INSIDE the root -> (p, ms), weights p / a / upd."""
+    p, g, ms = _d(p), _d(g), _d(ms)
+    lr, decay, eps, clip = r32(lr), r32(decay), r32(eps), r32(clip)
+    if clip > 0:
+        g = np.clip(g, -clip, clip)
+    msn = decay * ms + (1 - decay) * g * g
+    upd = lr * g / np.sqrt(msn + eps)
+    return (p - upd, msn), {"p": np.abs(p) + np.abs(upd), "a": msn, "upd": np.abs(upd)}
+
+
+def gauss_nll(mu, var, y, fps, scale, clip_mask=True):
+    """cost.py:190-229: l = log(var_a + 1e-20) + (y - mu_a)^2 / (var_a + 1e-20) per sequence, second, frame and axis, clipped to
+    [-10, 10]; loss = scale * mean_b sum l; the clip passes no gradient outside (-10, 10).  mu, var (B,3), y (B,T_y,3*fps)
+    interleaved x,y,z -> (loss, dmu, dvar), (w_dmu, w_dvar), l.  clip_mask=False: the gradient WITHOUT the clip's mask."""
+    mu, var, y = _d(mu), _d(var), _d(y)
+    B = y.shape[0]
+    ye = y.reshape(B, -1, 3)
+    v = (var + r32(1e-20))[:, None, :]
+    d = ye - mu[:, None, :]
+    l = np.log(v) + d * d / v
+    s = r32(scale)
+    loss = s * np.clip(l, -10, 10).sum() / max(B, 1)
+    k = ((l > -10) & (l < 10)) if clip_mask else np.ones(l.shape, bool)
+    gm, gv1, gv2 = -2 * d / v * k, (1 / v) * k, d * d / (v * v) * k
+    f = s / max(B, 1)
+    return (loss, f * gm.sum(1), f * (gv1 - gv2).sum(1)), (f * np.abs(gm).sum(1), f * (gv1 + gv2).sum(1)), l
+
+
+# (B, T_y, fps) of the Gaussian NLL cases: per = 3, one trip of the 256-element loop, a second trip with a partial wave, a third,
+# more than 256 block partials, both at once; (n_pix, C) of the cross-entropy cases (70 000 rows: 274 block partials)
+NLL_EDGE_SHAPES = ((1, 1, 1), (5, 1, 30), (7, 3, 30), (3, 6, 30), (257, 1, 2), (300, 3, 30))
+CCE_EDGE_SHAPES = ((1, 1), (255, 30), (257, 30), (700, 64), (70000, 3))
+
+
+def nll_edge_inputs(seed, B, Ty, fps):
+    """Inputs of gauss_nll with all three populations present: l below -10 (var 1e-7..1e-5, |y - mu| about 1e-3), l above 10
+    (outliers of +-3 on var in [0.05, 1]) and the interior; no element within 1e-3 of a clip bound (those are drawn again)
+    -> (mu, var, y) fp32 and the number of elements that were drawn again."""
+    rng = np.random.default_rng(seed)
+    per = Ty * fps * 3
+    mu = rng.uniform(-1, 1, (B, 3)).astype(np.float32)
+    low = (np.arange(B * 3).reshape(B, 3) % 5) == 1
+    var = np.where(low, 10.0 ** rng.uniform(-7, -5, (B, 3)), rng.uniform(0.05, 1.0, (B, 3))).astype(np.float32)
+    a = np.arange(per) % 3
+    m_e, v_e, low_e = mu[:, a].astype(np.float64), var[:, a].astype(np.float64), low[:, a]
+
+    def draw():
+        n = rng.standard_normal((B, per))
+        d = np.where(low_e, 1e-3 * n, 0.3 * np.sqrt(v_e) * n)
+        out = ~low_e & (rng.random((B, per)) < 0.17)
+        return (m_e + np.where(out, np.where(rng.random((B, per)) < 0.5, 3.0, -3.0), d)).astype(np.float32)
+
+    y = draw()
+    again = 0
+    for _ in range(20):
+        l = gauss_nll(mu, var, y.reshape(B, Ty, 3 * fps), fps, 1.0)[2].reshape(B, per)
+        bad = np.abs(np.abs(l) - 10) < 1e-3
+        if not bad.any():
+            break
+        again += int(bad.sum())
+        y = np.where(bad, draw(), y)
+    return mu, var, y.reshape(B, Ty, 3 * fps), again
+
+
+def nll_populations(mu, var, y, fps):
+    """Shares of the elements of gauss_nll below -10, above 10 and inside, and the least distance of |l| from 10."""
+    l = gauss_nll(mu, var, y, fps, 1.0)[2]
+    return float((l <= -10).mean()), float((l >= 10).mean()), float(((l > -10) & (l < 10)).mean()), float(np.abs(np.abs(l) - 10).min())
+
+
+def mse_dense(y, target, activation, weight=1.0, time_major=False, transpose_target=True):
+    """Keras mean_squared_error behind Dense(tanh | linear): loss = w mean (y - t)^2, dpre = 2 w (y - t) / n * act'(y) ->
+    (loss, dpre), w_dpre.  time_major: y (T,B,O) against a target (B,T,O) (transpose_target=False leaves it as it lies)."""
+    y, t = _d(y), _d(target)
+    if time_major and transpose_target:
+        t = t.transpose(1, 0, 2)
+    t = t.reshape(y.shape)
+    n = max(y.size, 1)
+    sc = r32(r32(weight) / np.float32(n))
+    d = y - t
+    da = 1 - y * y if activation == "tanh" else np.ones_like(y)
+    wa = 1 + y * y if activation == "tanh" else np.ones_like(y)
+    return ((d * d).sum() * sc, 2 * d * sc * da), 2 * np.abs(d) * sc * wa
+
+
+def categorical_crossentropy(p, t, eps=1e-7):
+    """Keras-2.2 categorical_crossentropy on probabilities, TensorFlow backend: q = p / sum_c p, q' = clip(q, eps, 1 - eps) with
+    eps and 1 - eps rounded to fp32 (1 - 2^-23), l = -sum_c t_c log q'_c, loss = mean over rows; the clip passes no gradient
+    outside (eps, 1 - eps) -> (loss, dp), w_dp, q."""
+    p, t = _d(p), _d(t)
+    C = p.shape[-1]
+    p2, t2 = p.reshape(-1, C), t.reshape(-1, C)
+    n = max(p2.shape[0], 1)
+    lo, hi = r32(eps), float(np.float32(1) - np.float32(eps))
+    S = p2.sum(-1, keepdims=True)
+    q = p2 / S
+    qc = np.clip(q, lo, hi)
+    loss = -(t2 * np.log(qc)).sum() / n
+    g = np.where((q > lo) & (q < hi), -t2 / qc, 0.0)
+    dot = (g * q).sum(-1, keepdims=True)
+    w = (np.abs(g) + np.abs(g * q).sum(-1, keepdims=True)) / S / n
+    return (loss, ((g - dot) / S / n).reshape(p.shape)), w.reshape(p.shape), q.reshape(p.shape)
+
+
+def cce_edge_inputs(seed, n_pix, C):
+    """Rows for categorical_crossentropy: unnormalised (each scaled by uniform(0.5, 2)); every 5th row has 1e-9 under its target
+    class (lower clip), every 11th is exactly one-hot (q = 1, upper clip), every 7th has a soft target -> (p, t) fp32 and the
+    mask of the exactly one-hot rows."""
+    rng = np.random.default_rng(seed)
+    p = rng.random((n_pix, C)) + 0.01
+    p /= p.sum(-1, keepdims=True)
+    sc = rng.uniform(0.5, 2.0, (n_pix, 1))
+    cls = rng.integers(0, C, n_pix)
+    r = np.arange(n_pix)
+    t = np.zeros((n_pix, C))
+    t[r, cls] = 1.0
+    soft = rng.random((n_pix, C)) + 0.05
+    t = np.where((r % 7 == 3)[:, None], soft / soft.sum(-1, keepdims=True), t)
+    tiny = r % 5 == 1
+    p[r[tiny], cls[tiny]] = 1e-9
+    onehot = (r % 11 == 2) | (C == 1)
+    p[onehot] = 0.0
+    p[r[onehot], cls[onehot]] = 1.0
+    t[onehot] = 0.0
+    t[r[onehot], cls[onehot]] = 1.0
+    return (p * sc).astype(np.float32), t.astype(np.float32), onehot
+
+
+def cce_near_clip_rows(p, onehot, eps=1e-7):
+    """Rows (other than the exactly one-hot ones) with a q within 2 ulp of a clip bound: fp32 and fp64 could mask them differently."""
+    q = categorical_crossentropy(p, np.zeros_like(p), eps)[2]
+    lo, hi = r32(eps), float(np.float32(1) - np.float32(eps))
+    near = (np.abs(q - lo) <= 2 * float(np.spacing(np.float32(lo)))) | (np.abs(q - hi) <= 2 * U24)
+    return near.any(-1) & ~onehot
+
+
+def xyz_sum1(p, dp0=None):
+    """cost.py:20-29 under cfg.add_xyz_sum1: r = ux^2 + uy^2 + uz^2 - 1 per row of C >= 3 channels, reg = 0.5 mean r^2,
+    d reg / d u_k = 2 r u_k / n added to dp0 (channels >= 3 untouched) -> (reg, dp), w_dp."""
+    p = _d(p)
+    C = p.shape[-1]
+    p2 = p.reshape(-1, C)
+    n = p2.shape[0]
+    ss = (p2[:, :3] ** 2).sum(-1, keepdims=True)
+    r = ss - 1
+    dp = np.zeros_like(p2) if dp0 is None else _d(dp0).reshape(-1, C).copy()
+    w = np.abs(dp)
+    g = 2 * r * p2[:, :3] / n
+    dp[:, :3] += g
+    w[:, :3] += 2 * (ss + 1) * np.abs(p2[:, :3]) / n
+    return (0.5 * (r * r).mean(), dp.reshape(p.shape)), w.reshape(p.shape)
+
+
+def _refeed_axis(n, planar):
+    fps = n // 3
+    return (np.arange(n) // fps) if planar else (np.arange(n) % 3)
+
+
+def sample_refeed(mu, var, noise, std="sqrt", planar=False):
+    """lstm.py:460-468 / lstm_keras.py:139-149: x = mu_a + sd(var_a) * noise, sd = sqrt(var) ('sqrt') or var itself ('var');
+    frames interleaved x,y,z or planar [x*fps | y*fps | z*fps] -> x (B,3*fps), w_x."""
+    mu, var, noise = _d(mu), _d(var), _d(noise)
+    a = _refeed_axis(noise.shape[1], planar)
+    sd = np.sqrt(var) if std == "sqrt" else var
+    t = sd[:, a] * noise
+    return mu[:, a] + t, np.abs(mu[:, a]) + np.abs(t)
+
+
+def sample_refeed_bwd(dx, var, noise, std="sqrt", planar=False, dmu0=None, dvar0=None):
+    """Gradient of sample_refeed: dmu_a = sum_frames dx, dvar_a = sum_frames dx * noise * sd'(var_a), sd' = 1 / (2 sqrt(var)) or 1,
+    added to dmu0 / dvar0 where given -> (dmu, dvar), (w_dmu, w_dvar)."""
+    dx, var, noise = _d(dx), _d(var), _d(noise)
+    a = _refeed_axis(noise.shape[1], planar)
+    sel = (a[None, :] == np.arange(3)[:, None]).astype(np.float64)      # (3, n)
+    sdp = 0.5 / np.sqrt(var) if std == "sqrt" else np.ones_like(var)
+    gm, wm = dx @ sel.T, np.abs(dx) @ sel.T
+    gv, wv = (dx * noise) @ sel.T * sdp, np.abs(dx * noise) @ sel.T * sdp
+    if dmu0 is not None:
+        gm, wm = gm + _d(dmu0), wm + np.abs(_d(dmu0))
+    if dvar0 is not None:
+        gv, wv = gv + _d(dvar0), wv + np.abs(_d(dvar0))
+    return (gm, gv), (wm, wv)
+
+
+# --------------------------------------------------------------------------------------
 # a10: tf.contrib.rnn.LSTMCell / MultiRNNCell / tf.nn.dynamic_rnn as used by mycode/lstm.py:218-240
 # (TensorFlow 1.x contrib, not in the repo; restated from its published definition: one fused
 # kernel W:(F+H,4H) applied to [x, h], gate column order i, j(=g), f, o, plain sigmoid,

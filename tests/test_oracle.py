@@ -856,3 +856,168 @@ def test_value_regime_model_cases_hold_their_shares_and_the_yardstick_condition(
         assert min((z > 100).sum(), (z < -100).sum(), (z > 200).sum(), (z < -200).sum()) >= 100, (shape, act)
         assert (p["x_edge"][-1] == 0).all() and (p["h_edge"][-1] == 0).all() and (p["c_edge"][-1] == 0).all()
         _cap("convlstm cell %s %s" % (shape, act), {k: O.regime_error(r32[k], r64[k], "f32") for k in ("h", "c", "gates")})
+
+
+# --------------------------------------------------------------------------------------
+# References of tests/test_gpu_loss_optim_edges.py: each against torch.autograd in fp64 (1e-10 relative), and the input
+# generators' population / near-clip conditions for every shape the GPU file uses (a bad seed shows here, without a GPU).
+# --------------------------------------------------------------------------------------
+def _t64(a, grad=False):
+    return torch.tensor(np.asarray(a, np.float64), requires_grad=grad)
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+@pytest.mark.parametrize("i", range(len(O.NLL_EDGE_SHAPES)))
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+def test_gauss_nll_reference_matches_autograd_and_populations(i, scale):
+    B, Ty, fps = O.NLL_EDGE_SHAPES[i]
+    mu, var, y, again = O.nll_edge_inputs(100 + i, B, Ty, fps)
+    (loss, dmu, dvar), (wm, wv), l = O.gauss_nll(mu, var, y, fps, scale)
+    tm, tv = _t64(mu, True), _t64(var, True)
+    ve = tv[:, None, :] + O.r32(1e-20)
+    lt = torch.log(ve) + (_t64(y).reshape(B, -1, 3) - tm[:, None, :]) ** 2 / ve
+    lr = O.r32(scale) * torch.clamp(lt, -10, 10).sum() / B
+    lr.backward()
+    assert abs(loss - lr.item()) <= 1e-10 * abs(lr.item())
+    assert _rel(dmu, tm.grad.numpy()) <= 1e-10 and _rel(dvar, tv.grad.numpy()) <= 1e-10
+    assert (wm >= np.abs(dmu)).all() and (wv >= np.abs(dvar) * (1 - 1e-12)).all()
+    lo, hi, mid, dist = O.nll_populations(mu, var, y, fps)
+    print("nll %s: low %.3f high %.3f interior %.3f, drawn again %d of %d, least distance from a clip %.2e" % ((B, Ty, fps), lo, hi, mid, again, l.size, dist))
+    assert dist >= 1e-3
+    if l.size >= 90:      # (three elements cannot hold 5 % + 5 % + 50 %)
+        assert lo >= 0.05 and hi >= 0.05 and mid >= 0.5 and again < 0.01 * l.size
+        # the case tests the mask: without it the gradients are far outside any rounding bound
+        (_, dmu_n, dvar_n), _, _ = O.gauss_nll(mu, var, y, fps, scale, clip_mask=False)
+        assert (np.abs(dvar_n - dvar) > 1e-3 * wv).any() and (np.abs(dmu_n - dmu) > 1e-3 * wm).any()
+
+
+def test_gauss_nll_dvar_spans_orders_of_magnitude():
+    """Why the GPU bound is per element: with tiny variances present |dvar| spans seven orders of magnitude."""
+    mu, var, y, _ = O.nll_edge_inputs(105, 300, 3, 30)
+    dvar = np.abs(O.gauss_nll(mu, var, y, 30, 1.0)[0][2])
+    assert dvar.max() / np.median(dvar) > 1e6
+
+
+@pytest.mark.parametrize("i", range(len(O.CCE_EDGE_SHAPES)))
+def test_categorical_crossentropy_reference_matches_autograd(i):
+    n_pix, C = O.CCE_EDGE_SHAPES[i]
+    p, t, onehot = O.cce_edge_inputs(200 + i, n_pix, C)
+    (loss, dp), w, q = O.categorical_crossentropy(p, t)
+    tp = _t64(p, True)
+    hi = float(np.float32(1) - np.float32(1e-7))
+    assert hi == 1 - 2.0 ** -23
+    lr = torch.mean(-(_t64(t) * torch.log(torch.clamp(tp / tp.sum(-1, keepdim=True), O.r32(1e-7), hi))).sum(-1))
+    lr.backward()
+    assert abs(loss - lr.item()) <= 1e-10 * abs(lr.item())
+    ref = tp.grad.numpy()
+    # torch's clamp passes the gradient AT a bound (q == 1 of the one-hot rows); Keras' clip_by_value does too, but there
+    # d q / d p is exactly zero (q = p / p), so both are zero
+    assert np.abs(dp - ref).max() <= 1e-10 * np.abs(ref).max() + 1e-300
+    assert (w >= np.abs(dp) * (1 - 1e-12)).all()
+    near = O.cce_near_clip_rows(p, onehot)
+    assert near.sum() <= 0.01 * n_pix and not near.any()
+    if n_pix >= 255:
+        r = np.arange(n_pix)
+        assert (np.abs(p.sum(-1) - 1) > 1e-3).mean() > 0.9                       # unnormalised
+        assert (dp[onehot] == 0).all() and onehot.mean() >= 0.05                 # upper clip
+        if C > 1:
+            tiny = (r % 5 == 1) & ~onehot & (r % 7 != 3)
+            assert tiny.mean() >= 0.05 and (dp[tiny] == 0).all()                 # lower clip under a one-hot target
+            assert ((t > 0).sum(-1) > 1).mean() >= 0.05                          # soft targets
+
+
+@pytest.mark.parametrize("C", [3, 6])
+def test_xyz_sum1_reference_matches_autograd(C):
+    rng = np.random.default_rng(31)
+    p = rng.standard_normal((257, C)).astype(np.float32)
+    dp0 = rng.standard_normal((257, C)).astype(np.float32)
+    (reg, dp), w = O.xyz_sum1(p, dp0)
+    tp = _t64(p, True)
+    rr = 0.5 * torch.mean((tp[:, 0] ** 2 + tp[:, 1] ** 2 + tp[:, 2] ** 2 - 1) ** 2)
+    rr.backward()
+    assert abs(reg - rr.item()) <= 1e-10 * rr.item()
+    assert _rel(dp - dp0, tp.grad.numpy()) <= 1e-10 and (dp[:, 3:] == dp0[:, 3:]).all()
+    assert (w >= np.abs(dp) * (1 - 1e-12)).all()
+
+
+@pytest.mark.parametrize("clip", [0.0, 1.0])
+def test_rmsprop_tf_reference_matches_autograd_form(clip):
+    """TF RMSProp as a gradient step of torch: p - lr * g_c / sqrt(ms' + eps), ms' from ONE (ms starts at one)."""
+    g = np.array([0.5, -3.0, 0.0, 1.0, -1.0, 1.0000001, 2e-3], np.float32)
+    p = np.linspace(-1, 1, g.size).astype(np.float32)
+    (pn, msn), w = O.rmsprop_tf_step(p, g, np.ones_like(p), lr=0.1, decay=0.9, eps=1e-10, clip=clip)
+    tg = _t64(g)
+    gc = torch.clamp(tg, -O.r32(clip), O.r32(clip)) if clip > 0 else tg
+    ms = O.r32(0.9) * 1.0 + (1 - O.r32(0.9)) * gc * gc
+    ref = _t64(p) - O.r32(0.1) * gc / torch.sqrt(ms + O.r32(1e-10))
+    assert _rel(pn, ref.numpy()) <= 1e-10 and _rel(msn, ms.numpy()) <= 1e-10
+    if clip > 0:
+        assert msn[1] == msn[3] == msn[4] == msn[5]      # below, at and above the clip: the same clipped magnitude
+
+
+@pytest.mark.parametrize("std", ["sqrt", "var"])
+@pytest.mark.parametrize("planar", [False, True])
+def test_sample_refeed_reference_matches_autograd(std, planar):
+    rng = np.random.default_rng(32)
+    B, fps = 5, 22
+    mu = rng.uniform(-1, 1, (B, 3)); var = rng.uniform(0.01, 1, (B, 3)); var[0, 0] = 1e-6
+    noise = rng.standard_normal((B, 3 * fps)); dx = rng.standard_normal((B, 3 * fps))
+    dmu0, dvar0 = rng.standard_normal((B, 3)), rng.standard_normal((B, 3))
+    tm, tv = _t64(mu, True), _t64(var, True)
+    sd = torch.sqrt(tv) if std == "sqrt" else tv
+    if planar:
+        x = torch.cat([tm[:, k:k + 1] + sd[:, k:k + 1] * _t64(noise)[:, k * fps:(k + 1) * fps] for k in range(3)], -1)
+    else:
+        x = (tm[:, None, :] + sd[:, None, :] * _t64(noise).reshape(B, fps, 3)).reshape(B, 3 * fps)
+    (x * _t64(dx)).sum().backward()
+    xr, wx = O.sample_refeed(mu, var, noise, std, planar)
+    assert _rel(xr, x.detach().numpy()) <= 1e-10 and (wx >= np.abs(xr)).all()
+    (gm, gv), _ = O.sample_refeed_bwd(dx, var, noise, std, planar)
+    assert _rel(gm, tm.grad.numpy()) <= 1e-10 and _rel(gv, tv.grad.numpy()) <= 1e-10
+    (gm2, gv2), (wm, wv) = O.sample_refeed_bwd(dx, var, noise, std, planar, dmu0, dvar0)
+    assert _rel(gm2, tm.grad.numpy() + dmu0) <= 1e-10 and _rel(gv2, tv.grad.numpy() + dvar0) <= 1e-10
+    assert (wm >= np.abs(gm2) * (1 - 1e-12)).all() and (wv >= np.abs(gv2) * (1 - 1e-12)).all()
+
+
+@pytest.mark.parametrize("act", ["tanh", "linear"])
+def test_mse_dense_reference_matches_autograd(act):
+    rng = np.random.default_rng(33)
+    T, B, Od = 3, 5, 6
+    y = np.tanh(rng.standard_normal((T, B, Od))).astype(np.float32)
+    tgt = rng.uniform(-1, 1, (B, T, Od)).astype(np.float32)
+    pre = _t64(np.arctanh(y.astype(np.float64)) if act == "tanh" else y, True)
+    yy = torch.tanh(pre) if act == "tanh" else pre
+    lr = O.r32(O.r32(0.37) / np.float32(y.size)) * ((yy - _t64(tgt).transpose(0, 1)) ** 2).sum()
+    lr.backward()
+    (loss, dpre), w = O.mse_dense(y, tgt, act, 0.37, time_major=True)
+    assert abs(loss - lr.item()) <= 1e-10 * lr.item() and _rel(dpre, pre.grad.numpy()) <= 1e-10
+    assert (w >= np.abs(dpre) * (1 - 1e-12)).all()
+    (_, wrong), _ = O.mse_dense(y, tgt, act, 0.37, time_major=True, transpose_target=False)
+    assert (np.abs(wrong - dpre) > 1e-3 * w).any()
+
+
+def test_adam_reference_with_fp32_rounded_arguments_is_the_fp32_step():
+    """One Adam step: the fp64 reference on fp32-ROUNDED betas / lr_t / eps agrees with an fp32 NumPy emulation of the kernel's
+    arithmetic to a few ulp of each element's terms; the same reference on the exact fp64 betas is 1.3e-5 (200 times 2^-24) away in v."""
+    rng = np.random.default_rng(34)
+    n = 4099
+    f = np.float32
+    p, g = rng.standard_normal(n).astype(f), rng.standard_normal(n).astype(f)
+    m, v = (0.1 * rng.standard_normal(n)).astype(f), (rng.random(n) * 0.01).astype(f)
+    assert abs((1 - O.r32(0.999)) / (1 - 0.999) - 1) > 1.2e-5
+    for t in (1, 2, 1000):
+        lr_t, b1, b2, eps = f(O.adam_lr_t(t)), f(0.9), f(0.999), f(1e-7)
+        mi = b1 * m + (f(1) - b1) * g
+        vi = b2 * v + (f(1) - b2) * g * g
+        pi = p - lr_t * mi / (np.sqrt(vi) + eps)
+        assert mi.dtype == vi.dtype == pi.dtype == f
+        (pr, mr, vr), w = O.adam_step_f32args(p, g, m, v, t)
+        em, ev, ep = np.abs(mi - mr) / w["m"], np.abs(vi - vr) / w["v"], np.abs(pi - pr) / w["p"]
+        print("adam t=%d: fp32 emulation vs fp64 on rounded arguments, in 2^-24 of the terms: m %.2f v %.2f p %.2f" % (t, em.max() / O.U24, ev.max() / O.U24, ep.max() / O.U24))
+        assert em.max() <= 4 * O.U24 and ev.max() <= 5 * O.U24 and ep.max() <= 8 * O.U24
+        (_, _, vx), _ = O.adam_step_f32args(p, g, m, v, t, exact_betas=True)
+        assert (np.abs(vi - vx) / w["v"]).max() > 20 * O.U24
