@@ -848,6 +848,25 @@ int fov_onehot_maps(const float* xyz, int64_t xyz_seq_stride, int64_t xyz_step_s
                     int* theta_out, int* phi_out, int* status, int N, int T, fov_stream_t stream);
 int fov_onehot_status(int* status, fov_stream_t stream);
 
+/* The heat-map model's predictions decoded on the device, the step the reference's test loop runs right after model.predict:
+ *   replaces: mycode/convlstm_seq2seq.py:537-542 and mycode/convlstm_heatmap.py:556-558,
+ *             max_ind = np.argmax(decoded_sentence.reshape(batch_size, cfg.predict_step, -1, fps), axis=-2)
+ * Map m is n_pix pixels of C channels, element (p, c) at maps + m*map_stride + p*pixel_stride + c (strides in floats,
+ * pixel_stride >= C: a 30-channel view of a 32-channel buffer, a channel slice).  index[m*out_stride + c] is the pixel
+ * number of channel c's maximum over the n_pix pixels, value[m*out_stride + c] (value may be NULL) that maximum bit for
+ * bit; out_stride >= C lets a caller write slot t of an (N, T_out, C) tensor from step t.  Exactly np.argmax: the lowest
+ * pixel number among equal maxima (compared by value, -0.0 == +0.0), a NaN counts as the maximum and the first NaN wins.
+ * Every map is read once, in 8-byte loads when C, both strides and the base allow them, else in 4-byte loads; same result.
+ * Domain: 1 <= C <= 64, 1 <= n_pix <= 2^20, n_maps >= 0 (0 launches nothing), else FOV_ERR_INVALID. */
+int fov_heatmap_argmax(const float* maps, int64_t map_stride, int64_t pixel_stride, int* index, float* value,
+                       int64_t out_stride, int64_t n_maps, int n_pix, int C, fov_stream_t stream);
+/* Pixel number -> frame centre, the inverse of fov_onehot_maps' binning (mycode/utility.py:522-544) for the 36 x 18 /
+ * 10-degree geometry: i in [0, 648), ti = i / 18, pi = i % 18, az = (ti + 0.5) * 10 deg, el = (pi + 0.5) * 10 deg - 90 deg,
+ * xyz[3i..3i+2] = (cos el cos az, cos el sin az, sin el), evaluated in fp64 and rounded to fp32; each centre bins back to
+ * its own (ti, pi).  index (n) int32 and xyz (n, 3) contiguous.  An index outside [0, 648) writes three zeros and ORs a bit
+ * into `status`, the word of fov_onehot_maps' protocol: the caller zeroes it once, fov_onehot_status reads and clears it. */
+int fov_heatmap_index_xyz(const int* index, float* xyz, int64_t n, int* status, fov_stream_t stream);
+
 /* Zero-fills a freshly allocated workspace (asynchronously on `stream`): required once before its first use by
  * a persistent-kernel entry point, and again whenever the buffer is re-allocated. */
 int fov_workspace_init(void* workspace, size_t workspace_bytes, fov_stream_t stream);

@@ -13,7 +13,7 @@ constexpr int OH_FRAMES = 30;            // frames per second: the map's channel
 constexpr int OH_H = 36, OH_W = 18;      // 360 / 10 longitude bins x 180 / 10 latitude bins, indexed [theta, phi]
 constexpr int OH_PIX = OH_H * OH_W;
 constexpr int OH_NT = 256;
-enum { OH_BAD_XYZ = 1, OH_BAD_INDEX = 2 };
+enum { OH_BAD_XYZ = 1, OH_BAD_INDEX = 2, OH_BAD_PIXEL = 4 };    // OH_BAD_PIXEL: heatmap_decode.hip's HD_BAD_PIXEL
 
 struct OnehotParams {
     const float* xyz;       // (N, T, 30, 3): frame-contiguous inside a step, strided steps / sequences (floats)
@@ -142,6 +142,10 @@ int fov_onehot_status(int* status, fov_stream_t stream) {
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e == hipSuccess && word) e = hipMemsetAsync(status, 0, sizeof(int), (hipStream_t)stream);
     if (e != hipSuccess) { set_error("fov_onehot_status: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
+    if (word & OH_BAD_PIXEL) {      // fov_heatmap_index_xyz shares the word's protocol
+        set_error("fov_heatmap_index_xyz: a pixel number lies outside [0, 648)");
+        return FOV_ERR_INVALID;
+    }
     if (word) {
         set_error("fov_onehot_maps: %s", (word & OH_BAD_XYZ) ? "a frame centre is NaN or infinite"
                                                                : "a bin index lies outside [0, 36) x [0, 18)");

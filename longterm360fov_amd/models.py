@@ -1407,6 +1407,16 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         return self._predict_chunks([enc, dec0], batch_size, lambda e, d: self.predict_device(e, d, T_out),
                                     self._output_shape(T_out, *enc.shape[2:4]))
 
+    def predict_index(self, x, batch_size=None, predict_step=None):
+        """np.argmax(predict(x).reshape(N, T_out, -1, C_out), axis=-2), the reference's decode of its predictions
+        (convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558), with the arg-max taken on the device: only the int64
+        (N, T_out, C_out) pixel numbers reach the host, not the maps."""
+        self._check_map_head()
+        enc, dec0 = _as_f32(x[0]), _as_f32(x[1])
+        T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        return self._predict_chunks([enc, dec0], batch_size, lambda e, d: self.predict_index_device(e, d, T_out),
+                                    (T_out, self._w["head2_W"].shape[3])).astype(np.int64)
+
     def _device_weights(self):
         """The weights on the device and what predict_device derives from them, once per set of weights (rebuilt whenever _dw is
         dropped): the [K ; R] stacks, and the bf16 packs of the head's kernels (dtype) and of the stacks (cell_dtype)."""
@@ -1455,6 +1465,43 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         prediction as a device tensor (B,T_out,H,W,C_out) / (B,T_out,6); no host transfer (what bench.py times)."""
         import torch
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        B, H, W = xe.shape[0], xe.shape[2], xe.shape[3]
+        out = torch.empty((B,) + self._output_shape(T_out, H, W), dtype=torch.float32, device=self.device)
+
+        def sink(t, y):
+            out[:, t] = y
+        self._run_steps(xe, dec0, T_out, sink)
+        return out
+
+    def predict_index_device(self, xe, dec0, predict_step=None, values=False):
+        """predict_device's steps with each step's maps decoded where they are made (ops.heatmap_argmax, the reference's
+        np.argmax(decoded.reshape(N, T_out, -1, C), axis=-2) of convlstm_seq2seq.py:537-542): -> int32 (B, T_out, C_out) pixel
+        numbers on the device, with values=True also the float32 maxima.  The (B, T_out, H, W, C_out) prediction is never
+        allocated.  Heads 'conv2d' / 'conv1d'; the 'dense' head has no maps (ValueError)."""
+        import torch
+        from . import ops
+        self._check_map_head()
+        T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        shape = (xe.shape[0], T_out, self._w["head2_W"].shape[3])
+        index = torch.empty(shape, dtype=torch.int32, device=self.device)
+        value = torch.empty(shape, dtype=torch.float32, device=self.device) if values else None
+
+        def sink(t, y):
+            if values:
+                value[:, t] = ops.heatmap_argmax(y, values=True, out=index[:, t])[1]
+            else:
+                ops.heatmap_argmax(y, out=index[:, t])
+        self._run_steps(xe, dec0, T_out, sink)
+        return (index, value) if values else index
+
+    def _check_map_head(self):
+        if self.head == "dense":
+            raise ValueError("the 'dense' head predicts six numbers a step, not heat maps: there is nothing to decode")
+
+    def _run_steps(self, xe, dec0, T_out, sink):
+        """The encoder and the T_out decoder steps of predict_device; sink(t, y) receives step t's prediction y ((B,H,W,C_out) /
+        (B,6)) before it is fed back."""
+        import torch
         dw = self._device_weights()
         cell, head = self._cell_and_head(dw)
         filters = [dw["enc%d_R" % l].shape[2] for l in range(3)]
@@ -1488,7 +1535,6 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             seq = nxt
             states.append([h, c])
         # decoder: three cells per step, each h written straight into its slot of the concat map
-        out = e4(B, T_out, *self._output_shape(T_out, H, W)[1:])
         for t in range(T_out):
             feat = e4(B, H, W, cat)
             cur = inp
@@ -1498,14 +1544,13 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
                 states[l][0] = hslot
                 cur = hslot
             y = head(feat)
-            out[:, t] = y
+            sink(t, y)
             if self.head == "dense":     # the six outputs fed back as a 1x1x6 map
                 y = y.reshape(B, 1, 1, 6)
             if pad:
                 inp[..., :C_in] = y
             else:
                 inp = y
-        return out
 
     predict_on_batch = predict
 
@@ -1530,18 +1575,57 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         tgt = ops.one_hot_maps(self._xyz_on_device(target_xyz), time_major=True).transpose(0, 1)
         return enc, dec, tgt
 
-    def predict_trajectories(self, enc_xyz, dec_xyz, batch_size=None, predict_step=None):
+    def predict_trajectories(self, enc_xyz, dec_xyz, batch_size=None, predict_step=None, output="maps"):
         """predict([one-hot encoder maps, one-hot decoder seed]) from frame centres (convlstm_seq2seq.py:356-374 feeds the
         maps of utility._create_one_hot): enc_xyz (N, T_in, 30, 3) or (N, T_in, 1, 30, 3), dec_xyz (N, 1, 30, 3) - the second
         whose map is one_hot_future_input[:, 0] - as NumPy arrays or device tensors.  Only xyz crosses PCIe; the 32-channel
         maps predict_device runs on are written on the device.  -> NumPy (N, T_out, 36, 18, 30), what predict returns for the
-        host-built maps."""
+        host-built maps.
+        output 'index': the maps decoded on the device as predict_index does -> int64 (N, T_out, 30) pixel numbers; 'xyz':
+        those pixels' bin centres -> float32 (N, T_out, 30, 3), the layout of the xyz this method takes.  Neither allocates
+        nor copies the maps."""
         from . import ops
+        if output not in ("maps", "index", "xyz"):
+            raise ValueError("output must be 'maps', 'index' or 'xyz', got %r" % (output,))
         self._check_onehot_model()
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         enc, dec = self._xyz_on_device(enc_xyz), self._xyz_on_device(dec_xyz)
-        return self._predict_chunks([enc, dec], batch_size, lambda e, d: self.predict_device(
-            ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out), self._output_shape(T_out, 36, 18))
+        if output == "maps":
+            return self._predict_chunks([enc, dec], batch_size, lambda e, d: self.predict_device(
+                ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out), self._output_shape(T_out, 36, 18))
+        index = lambda e, d: self.predict_index_device(ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out)
+        if output == "index":
+            return self._predict_chunks([enc, dec], batch_size, index, (T_out, 30)).astype(np.int64)
+        return self._predict_chunks([enc, dec], batch_size, lambda e, d: ops.heatmap_index_xyz(index(e, d)), (T_out, 30, 3))
+
+    def evaluate_trajectories(self, enc_xyz, dec_xyz, target_xyz, batch_size=None, predict_step=None, span_deg=120.0,
+                              gt_span_deg=120.0):
+        """Predict from frame centres and score against the frames that followed, target_xyz (N, T_out, 30, 3), without the
+        maps or the pixel numbers leaving the device -> {'index_accuracy': the share of frames whose predicted pixel (the
+        reference's max_ind) is the pixel ops.theta_phi_index puts the target frame in, 'hit_rate': float32 (N, T_out), the
+        mean over a second's 30 frames of ops.fov_hit_rate(predicted bin centre, target centre)}.  The kernels leave one
+        number a frame; torch sums those on the device and the two results are copied out."""
+        import torch
+        from . import ops
+        self._check_onehot_model()
+        T_out = cfg.predict_step if predict_step is None else int(predict_step)
+        enc, dec, tgt = (self._xyz_on_device(a) for a in (enc_xyz, dec_xyz, target_xyz))
+        if tgt.dim() == 5:
+            tgt = tgt[:, :, 0]
+        if tuple(tgt.shape[1:]) != (T_out, 30, 3) or tgt.shape[0] != enc.shape[0]:
+            raise ValueError("target_xyz of shape %s: expected (%d, %d, 30, 3)" % (tuple(tgt.shape), enc.shape[0], T_out))
+        n = enc.shape[0]
+        bs = n if not batch_size else int(batch_size)
+        equal = torch.zeros((), dtype=torch.int64, device=self.device)
+        rates = []
+        for lo in range(0, n, max(bs, 1)):
+            e, d, g = enc[lo:lo + bs], dec[lo:lo + bs], tgt[lo:lo + bs].contiguous()
+            index = self.predict_index_device(ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out)
+            ti, pi = ops.theta_phi_index(g)
+            equal += (index == ti * 18 + pi).sum()
+            rates.append(ops.fov_hit_rate(ops.heatmap_index_xyz(index), g, span_deg, gt_span_deg).mean(-1))
+        return {"index_accuracy": float(equal.item()) / max(n * T_out * 30, 1),
+                "hit_rate": torch.cat(rates).cpu().numpy() if rates else np.zeros((0, T_out), np.float32)}
 
     def train_on_trajectories(self, enc_xyz, dec_xyz, target_xyz):
         """train_on_batch([enc maps, dec maps], target maps) with the three one-hot map sets built on the device from frame

@@ -1486,3 +1486,78 @@ def one_hot_maps(src, channels=30, out=None, time_major=False, bin_size=10):
     seq_stride, step_stride = (slab, N * slab) if time_major else (T * slab, slab)
     _onehot_launch(src, out, seq_stride, step_stride, channels, None)
     return out
+
+
+HEATMAP_ARGMAX_THREADS = 512    # heatmap_decode.hip's HD_NT: a pass of the kernel is THREADS // lanes-per-pixel pixels
+
+
+def heatmap_argmax_pass_pixels(C, vector=None):
+    """Pixels one workgroup of fov_heatmap_argmax takes per pass: a thread owns two channels in the 8-byte form (vector=True;
+    None: what an aligned call on C channels gets) and one in the scalar form."""
+    vector = C % 2 == 0 if vector is None else vector
+    return HEATMAP_ARGMAX_THREADS // (C // 2 if vector else C)
+
+
+def _uniform_stride(shape, strides, dense, what):
+    """The one stride that addresses dims `shape` as a single flattened dim (size-1 dims carry none) -> stride, or `dense` when
+    there is at most one element.  ValueError when the dims do not collapse: nothing is copied silently."""
+    dims = [(n, s) for n, s in zip(shape, strides) if n != 1]
+    for (n0, s0), (n1, s1) in zip(dims, dims[1:]):
+        if s0 != n1 * s1:
+            raise ValueError("%s: the leading dims %s with strides %s do not collapse to one stride" % (what, tuple(shape), tuple(strides)))
+    return dims[-1][1] if dims else dense
+
+
+def heatmap_argmax(maps, values=False, out=None):
+    """Per-channel arg-max over the pixels of every map, the reference's decode step
+    np.argmax(decoded.reshape(N, T, -1, C), axis=-2) (mycode/convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558), on
+    the device.  maps: float32 (..., H, W, C) on the GPU; the last three dims are one map with unit channel stride and a
+    uniform pixel stride (a channel slice or a 30-of-32 view is fine), the leading dims must collapse to one map stride,
+    else ValueError.  -> int32 (..., C) pixel numbers h * W + w, exactly np.argmax's (first of equal maxima, first NaN wins);
+    with values=True also the float32 maxima, bit for bit.  out: an int32 (..., C) view to write into, unit last stride and
+    one row stride (slot t of an (N, T, C) tensor)."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float32 and maps.dim() >= 3):
+        raise TypeError("maps must be a float32 (..., H, W, C) tensor on the GPU")
+    lead, (H, W, C) = tuple(maps.shape[:-3]), maps.shape[-3:]
+    if H * W == 0 or C == 0:
+        raise ValueError("maps of shape %s: an empty map has no maximum" % (tuple(maps.shape),))
+    if C > 1 and maps.stride(-1) != 1:
+        raise ValueError("maps: the channels of a pixel must be contiguous")
+    ps = _uniform_stride((H, W), maps.stride()[-3:-1], C, "maps (pixels)")
+    if ps < C:
+        raise ValueError("maps: pixel stride %d is below the %d channels" % (ps, C))
+    n_maps = 1
+    for d in lead:
+        n_maps *= d
+    ms = _uniform_stride(lead, maps.stride()[:-3], H * W * ps, "maps") if n_maps else 0
+    if ms < 0:
+        raise ValueError("maps: negative map stride")
+    if out is None:
+        out = torch.empty(lead + (C,), dtype=torch.int32, device=maps.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == lead + (C,)
+              and (C == 1 or out.stride(-1) == 1)):
+        raise ValueError("out must be an int32 %s view on the GPU with unit last stride" % (lead + (C,),))
+    os_ = _uniform_stride(lead, out.stride()[:-1], C, "out") if n_maps else C
+    if os_ < C:
+        raise ValueError("out: row stride %d is below the %d channels" % (os_, C))
+    val = torch.empty_strided(out.shape, out.stride(), dtype=torch.float32, device=maps.device) if values else None
+    check(_lib.lib().fov_heatmap_argmax(maps.data_ptr(), ms, ps, out.data_ptr(), _ptr(val), os_, n_maps, H * W, C, _stream()))
+    return (out, val) if values else out
+
+
+def heatmap_index_xyz(index):
+    """Pixel numbers of the 36 x 18 map -> their bins' centres as unit vectors, the inverse of theta_phi_index's binning
+    (pixel = theta_index * 18 + phi_index).  index: contiguous int32 (...) on the GPU -> float32 (..., 3), the layout of the
+    xyz one_hot_maps takes when index is (N, T, 30).  ValueError on a pixel number outside [0, 648) (the call synchronises
+    the stream to read the status word)."""
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.is_contiguous()):
+        raise TypeError("index must be a contiguous int32 tensor on the GPU")
+    xyz = torch.empty(tuple(index.shape) + (3,), dtype=torch.float32, device=index.device)
+    status = torch.zeros(1, dtype=torch.int32, device=index.device)
+    L = _lib.lib()
+    check(L.fov_heatmap_index_xyz(index.data_ptr(), xyz.data_ptr(), index.numel(), status.data_ptr(), _stream()))
+    code = L.fov_onehot_status(status.data_ptr(), _stream())
+    if code == _lib.ERR_INVALID:
+        raise ValueError(L.fov_last_error().decode("utf-8", "replace"))
+    check(code)
+    return xyz

@@ -13,6 +13,9 @@ reference's functions):
     theta_phi_index_for_onehot / create_one_hot
                              mycode/utility.py:522-571 (the ConvLSTM heat-map inputs; pinned by tests/golden/onehot.npz;
                              ops.theta_phi_index / ops.one_hot_maps build the same on the device)
+    heatmap_argmax           mycode/convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558 (the test loops' max_ind;
+                             ops.heatmap_argmax computes the same on the device); bin_centre_xyz is the way back from a
+                             pixel number to a frame centre
 """
 import numpy as np
 
@@ -196,6 +199,28 @@ def create_one_hot(theta_index, phi_index, bin_size=10, vector=False):
     if vector:
         one_hot = one_hot.reshape(ti.shape + (-1,))
     return one_hot
+
+
+def heatmap_argmax(decoded):
+    """The pixel number of every channel's maximum, int64 (N, T, C): the line the reference's test loop runs on
+    model.predict's (N, T, H, W, C) maps (mycode/convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558) before it
+    pickles the result.  ops.heatmap_argmax computes the same on the device."""
+    d = np.asarray(decoded)
+    return np.argmax(d.reshape(d.shape[0], d.shape[1], -1, d.shape[-1]), axis=-2)
+
+
+def bin_centre_xyz(index, bin_size=10):
+    """Centres of the one-hot bins as unit vectors, float64 (..., 3): pixel number index = theta_index * 18 + phi_index of
+    theta_phi_index_for_onehot's geometry -> az = (theta_index + 0.5) * bin_size, el = (phi_index + 0.5) * bin_size - 90
+    degrees, (cos el cos az, cos el sin az, sin el).  Every centre bins back to its own indices.  An index outside the map
+    raises ValueError.  ops.heatmap_index_xyz computes the same on the device."""
+    i = np.asarray(index)
+    H, W = 360 // bin_size, 180 // bin_size
+    if ((i < 0) | (i >= H * W)).any():
+        raise ValueError("bin_centre_xyz: index outside [0, %d)" % (H * W))
+    az = np.deg2rad((i // W + 0.5) * bin_size)
+    el = np.deg2rad((i % W + 0.5) * bin_size - 90.0)
+    return np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=-1)
 
 
 def get_shuffle_index(data_length, rng=None):
