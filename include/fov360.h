@@ -867,6 +867,28 @@ int fov_heatmap_argmax(const float* maps, int64_t map_stride, int64_t pixel_stri
  * into `status`, the word of fov_onehot_maps' protocol: the caller zeroes it once, fov_onehot_status reads and clears it. */
 int fov_heatmap_index_xyz(const int* index, float* xyz, int64_t n, int* status, fov_stream_t stream);
 
+/* The 'accuracy' metric of Keras 2.1-2.2's model.compile(metrics=['accuracy']), counted on the device:
+ *   replaces: the `acc` / `val_acc` that fit, fit_generator and evaluate report for the models compiled at
+ *             mycode/given_others_gt_mean_var_seq2seq.py:308, FoV_seq2seq_mu_var.py:248, Fov_seq2seq_2layers.py:335,
+ *             3layers.py:302, lstm_keras.py:87,247,392 and convlstm_heatmap.py:281 (keras/engine/training.py chooses
+ *             categorical_accuracy, K.argmax(y_true, -1) == K.argmax(y_pred, -1), for an output of C > 1 channels and
+ *             binary_accuracy, y_true == K.round(y_pred), for C == 1).
+ * Row (i0, i1, r), 0 <= i0 < n0, 0 <= i1 < n1, 0 <= r < rows, of either operand starts at i0*s0 + i1*s1 + r*row_stride
+ * floats; its C channels are contiguous, row_stride >= C (a 30-of-32-channel view works as it lies), outer strides >= 0.
+ * A time-major prediction (T, B, H*W, C) meets a batch-major target (B, T, H*W, C) by swapping s0 and s1, not by a copy.
+ * *matches (device memory, 8-byte aligned) receives the number of matching rows, or has it added when accumulate != 0; an
+ * empty shape writes 0 or leaves it alone.  The count is an exact integer, the same in every run (integer atomics only).
+ * C > 1: a row matches when both arg-maxes agree; arg-max takes the lowest index among equal maxima (-0.0 == +0.0) and
+ * the first NaN of a row as its maximum (np.argmax, the rule of fov_heatmap_argmax; TensorFlow leaves both unspecified).
+ * C == 1: an element matches when target == rint(pred), half to even (0.5 -> 0, 1.5 -> 2); a NaN matches nothing.
+ * Forms: C <= 8 a thread per row; 8 < C a group of 4 ... 64 lanes per row, each on 2 channels by 8-byte loads when both
+ * bases are 8-byte aligned and all six strides are even, else on 1 channel by 4-byte loads (same result); C beyond a
+ * group's reach (128 / 64 channels) loops.  Domain: C >= 1, n0 * n1 * rows <= 2^40, else FOV_ERR_INVALID. */
+int fov_categorical_accuracy(const float* pred, int64_t pred_s0, int64_t pred_s1, int64_t pred_row_stride,
+                             const float* target, int64_t tgt_s0, int64_t tgt_s1, int64_t tgt_row_stride,
+                             int64_t n0, int64_t n1, int64_t rows, int C,
+                             int64_t* matches, int accumulate, fov_stream_t stream);
+
 /* Zero-fills a freshly allocated workspace (asynchronously on `stream`): required once before its first use by
  * a persistent-kernel entry point, and again whenever the buffer is re-allocated. */
 int fov_workspace_init(void* workspace, size_t workspace_bytes, fov_stream_t stream);

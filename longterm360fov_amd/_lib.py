@@ -144,6 +144,7 @@ SIGNATURES = {
     "fov_onehot_status": (_I, [_P, _P]),
     "fov_heatmap_argmax": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_int64, _I, _I, _P]),
     "fov_heatmap_index_xyz": (_I, [_P, _P, ctypes.c_int64, _P, _P]),
+    "fov_categorical_accuracy": (_I, [_P] + [ctypes.c_int64] * 3 + [_P] + [ctypes.c_int64] * 3 + [ctypes.c_int64] * 3 + [_I, _P, _I, _P]),
     "fov_workspace_init": (_I, [_P, _SZ, _P]),
     "fov_check_status": (_I, [_P, _SZ, _P]),
     "fov_workspace_force_safe": (_I, [_P, _SZ, _I, _P]),

@@ -85,11 +85,53 @@ def pad_cols(a, Hp):
     return out
 
 
+class _EpochMeter:
+    """What one pass over batches logs - the batch-size-weighted loss and, when the model was compiled with the accuracy metric,
+    matches / rows - summed on the device and read once at the end: no host synchronisation per batch.  The loss is an fp64
+    sum of the trainers' fp32 (1,) losses (they lie in buffers the NEXT step overwrites: the add is queued before it), the
+    matches an int64 sum of what trainer.eval_metrics returns; a training pass leaves matches out, its count is the trainer's
+    own accumulator (FlatParamTrainer.acc_matches)."""
+
+    def __init__(self, device, accuracy):
+        import torch
+        self.loss_sum, self.n = torch.zeros(1, dtype=torch.float64, device=device), 0
+        self.match_sum, self.rows = (torch.zeros(1, dtype=torch.int64, device=device) if accuracy else None), 0
+
+    def add(self, loss, n, matches=None, rows=0):
+        self.loss_sum.add_(loss.reshape(1), alpha=float(n))      # (fp32 into the fp64 sum: one launch)
+        self.n += n
+        self.rows += rows
+        if matches is not None:
+            self.match_sum.add_(matches.reshape(1))
+
+    def loss(self):
+        return float(self.loss_sum.item()) / max(self.n, 1)
+
+    def acc(self, counter=None):
+        """matches / rows; counter: the device int64 that holds this pass's matches instead of the meter's own sum."""
+        counter = self.match_sum if counter is None else counter
+        return int(counter.item()) / max(self.rows, 1)
+
+
+def _train_acc(trainer, meter):
+    """The epoch's training accuracy from the trainer's accumulator: under torch.distributed every rank counted its shards,
+    ONE all-reduce per epoch sums them (the rows are the global batches', known on the host)."""
+    import torch
+    from . import parallel
+    counter = trainer.acc_matches
+    if counter is None:      # an epoch of no steps
+        return 0.0
+    if parallel.dp_active():
+        torch.distributed.all_reduce(counter, op=torch.distributed.ReduceOp.SUM)
+    return meter.acc(counter)
+
+
 def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, shuffle, callbacks, initial_epoch,
                validation_data):
     """Keras `Model.fit` loop shared by the model objects: the LAST `validation_split` fraction is held out
     BEFORE shuffling, train indices are permuted every epoch (np.random), the last partial batch is used,
-    callbacks see {'loss','val_loss','lr'}.  Under torch.distributed every rank takes its contiguous shard
+    callbacks see {'loss','val_loss','lr'} and, compiled with metrics=['accuracy'], {'acc','val_acc'} (Keras 2.1-2.2's
+    keys).  Under torch.distributed every rank takes its contiguous shard
     of each global batch (one gradient all-reduce per step inside trainer.train_step)."""
     import torch
     from . import parallel
@@ -136,7 +178,11 @@ def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, 
             epoch_arrays = [t.index_select(0, idx_dev) for t in dev_arrays]
         # the epoch's loss sum stays on the device (fp64): no host synchronisation per step, so the launches of step k + 1 are
         # queued while step k runs (the returned loss tensor is overwritten by the NEXT step: the add is queued before it)
-        tot_t, cnt = torch.zeros(1, dtype=torch.float64, device=model.device), 0
+        # ... and so do the matches of the accuracy metric, in the trainer's own accumulator: two more reads per epoch, none per step
+        acc_on = bool(trainer.count_accuracy)
+        meter = _EpochMeter(model.device, False)
+        if acc_on and trainer.acc_matches is not None:
+            trainer.acc_matches.zero_()      # (train_on_batch counts into it too)
         step = trainer.train_step
         for lo in range(0, n_train, batch_size):
             gidx = idx[lo:lo + batch_size]
@@ -152,28 +198,27 @@ def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, 
             else:
                 batch = [t[lo + a:lo + b] for t in dev_arrays]   # idx is the identity: contiguous rows, no copy
             loss = step(*batch, n_global=len(gidx))
-            tot_t.add_(loss.reshape(1), alpha=float(len(gidx)))      # (fp32 into the fp64 sum: one launch)
-            cnt += len(gidx)
-        tot = float(tot_t.item())
-        logs = {"loss": tot / max(cnt, 1), "lr": trainer.lr}
+            meter.add(loss, len(gidx), rows=trainer.metric_rows((len(gidx),) + tgt.shape[1:]) if acc_on else 0)
+        logs = {"loss": meter.loss(), "lr": trainer.lr}
+        if acc_on:
+            logs["acc"] = _train_acc(trainer, meter)
         if val is not None and len(val[1]):
-            vt, vc = 0.0, 0
             if val_dev is None and sum(a.nbytes for a in val[0]) + val[1].nbytes <= limit:
                 val_dev = [d(a) for a in val[0]] + [d(val[1])]      # uploaded once per fit()
-            vt_t = torch.zeros(1, dtype=torch.float64, device=model.device)
+            vmeter = _EpochMeter(model.device, acc_on)
             for lo in range(0, len(val[1]), max(batch_size, 1)):
                 sl = slice(lo, lo + batch_size)
                 k = len(val[1][sl])
                 vb = [t[sl] for t in val_dev] if val_dev is not None else [d(arr[sl]) for arr in val[0]] + [d(val[1][sl])]
-                vt_t.add_(trainer.eval_loss(*vb).reshape(1), alpha=float(k))
-                vc += k
-            vt = float(vt_t.item())
-            logs["val_loss"] = vt / vc
-        trainer.check()      # a persistent kernel that gave up poisons its workspace and the optimizer skips the update
-        model._w = trainer.weights_numpy()
-        model._dw = None
-        for cb in cbs:
-            cb.on_epoch_end(epoch, logs)
+                if acc_on:
+                    vloss, vmatches = trainer.eval_metrics(*vb)
+                    vmeter.add(vloss, k, vmatches, trainer.metric_rows((k,) + val[1].shape[1:]))
+                else:
+                    vmeter.add(trainer.eval_loss(*vb), k)
+            logs["val_loss"] = vmeter.loss()
+            if acc_on:
+                logs["val_acc"] = vmeter.acc()
+        model._finish_epoch(trainer, cbs, epoch, logs)
         if model.stop_training:
             break
     for cb in cbs:
@@ -196,6 +241,7 @@ class KerasModelSurface:
         self._dw = self._ws = self._trainer = None       # device copies / workspace (lazy), trainer (lazy)
         self.optimizer = self.loss = None
         self.metrics = []
+        self._accuracy = False
         self._lr = 1e-3
         self.stop_training = False
 
@@ -306,13 +352,23 @@ class KerasModelSurface:
     # ---- training surface ----
     def compile(self, optimizer="Adam", loss="mean_squared_error", metrics=None):
         """Keras `compile`.  Accepted: optimizer 'Adam' | 'RMSprop' (Keras defaults), loss 'mean_squared_error' | 'mse'
-        (FoV_seq2seq.py:103, given_others...py:308, convlstm_seq2seq.py:287)."""
+        (FoV_seq2seq.py:103, given_others...py:308, convlstm_seq2seq.py:287); metrics: 'accuracy' | 'acc' (given_others...py:308,
+        convlstm_heatmap.py:281) makes fit / fit_generator log `acc` and `val_acc` and evaluate return [loss, acc] (Keras
+        2.1-2.2's names), counted on the device by the trainer; any other name is kept in self.metrics and ignored."""
         opt = optimizer if isinstance(optimizer, str) else getattr(optimizer, "name", str(optimizer))
         if opt.lower() not in ("adam", "rmsprop"):
             raise ValueError("unsupported optimizer %r" % (optimizer,))
         if str(getattr(loss, "__name__", loss)).lower().lstrip("_") not in ("mean_squared_error", "mse"):
             raise ValueError("unsupported loss %r" % (loss,))
         self.optimizer, self.loss, self.metrics = opt.lower(), "mse", list(metrics or [])
+        self._accuracy = any(isinstance(m, str) and m.lower() in ("accuracy", "acc") for m in self.metrics)
+        if self._trainer is not None:
+            self._trainer.count_accuracy = self._accuracy
+
+    @property
+    def metrics_names(self):
+        """Keras's `metrics_names`: what evaluate / test_on_batch return, in order."""
+        return ["loss", "acc"] if self._accuracy else ["loss"]
 
     @property
     def lr(self):
@@ -333,6 +389,8 @@ class KerasModelSurface:
         if self._trainer is None:
             self._trainer = self._make_trainer(self.optimizer or self._default_optimizer)
             self._trainer.lr = self._lr
+            if self._accuracy:      # (off is the trainers' default: a model compiled without the metric sets nothing)
+                self._trainer.count_accuracy = True
         return self._trainer
 
     def _fit_inputs(self, x):
@@ -350,6 +408,8 @@ class KerasModelSurface:
                           callbacks, initial_epoch, validation_data)
 
     def train_on_batch(self, x, y, **kw):
+        """Keras `train_on_batch`.  Returns the loss as a float also when the accuracy metric is compiled (Keras would return
+        [loss, acc])."""
         tr = self._get_trainer()
         loss = tr.train_step(*[self._to_device(a) for a in self._fit_inputs(x)], self._to_device(y),
                              **{k: (None if v is None else self._to_device(v)) for k, v in kw.items()})
@@ -358,6 +418,110 @@ class KerasModelSurface:
         self._w = tr.weights_numpy()
         self._dw = None
         return value
+
+    def _fit_target(self, y):
+        """The target as the one array the trainer takes."""
+        return y
+
+    def _finish_epoch(self, tr, cbs, epoch, logs):
+        tr.check()      # a persistent kernel that gave up poisons its workspace and the optimizer skips the update
+        self._w = tr.weights_numpy()
+        self._dw = None
+        for cb in cbs:
+            cb.on_epoch_end(epoch, logs)
+
+    def _host_batches(self, batches):
+        """(x, y) as a caller hands them -> (input list, one target array) as the trainer takes them."""
+        for xb, yb in batches:
+            yield self._fit_inputs(xb), _as_f32(self._fit_target(yb))
+
+    def _evaluate_batches(self, batches, what):
+        """Loss (and accuracy) over an iterable of host batches (input list, target array) in the trainer's form (_host_batches),
+        batch-size-weighted -> float, or [loss, acc] when the accuracy metric is compiled (model.metrics_names).  No update;
+        sums stay on the device until the end.  Nothing of `batches` is drawn before the compile check."""
+        if self.optimizer is None:
+            raise RuntimeError("call compile() before %s()" % what)
+        tr = self._get_trainer()
+        meter = _EpochMeter(self.device, self._accuracy)
+        for xb, yb in batches:
+            dev = [self._to_device(a) for a in xb] + [self._to_device(yb)]
+            if self._accuracy:
+                loss, matches = tr.eval_metrics(*dev)
+                meter.add(loss, len(yb), matches, tr.metric_rows(yb.shape))
+            else:
+                meter.add(tr.eval_loss(*dev), len(yb))
+        tr.check()
+        return [meter.loss(), meter.acc()] if self._accuracy else meter.loss()
+
+    def evaluate(self, x, y, batch_size=32, verbose=0):
+        """Keras `Model.evaluate`: the loss over (x, y) in chunks of `batch_size` rows, batch-size-weighted -> float, or
+        [loss, acc] for a model compiled with metrics=['accuracy'] (given_others...py:308, convlstm_heatmap.py:281)."""
+        def chunks():      # converted once, here: _evaluate_batches takes the batches as the trainer takes them
+            xs, yt = self._fit_inputs(x), _as_f32(self._fit_target(y))
+            bs = max(int(batch_size or len(yt)), 1)
+            for lo in range(0, len(yt), bs):
+                yield [a[lo:lo + bs] for a in xs], yt[lo:lo + bs]
+        return self._evaluate_batches(chunks(), "evaluate")
+
+    def test_on_batch(self, x, y):
+        """Keras `test_on_batch`: evaluate on (x, y) as ONE batch."""
+        return self._evaluate_batches(self._host_batches([(x, y)]), "test_on_batch")
+
+    def evaluate_generator(self, generator, steps):
+        """Keras `evaluate_generator`: evaluate over `steps` batches (x, y) drawn from the generator."""
+        return self._evaluate_batches(self._host_batches(next(generator) for _ in range(steps)), "evaluate_generator")
+
+    def fit_generator(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None,
+                      callbacks=None, use_multiprocessing=False, shuffle=True, initial_epoch=0, verbose=0):
+        """Keras `fit_generator` (given_others...py:494-498, convlstm_heatmap.py:415-418): `steps_per_epoch` batches per epoch
+        from a generator yielding (model inputs, target) - ([enc, others, dec_in], target) for the mixing model, ([enc, dec0],
+        target) for the ConvLSTM one; validation_data may be a generator (validation_steps batches).  Logs as fit's: loss,
+        val_loss, lr and, compiled with metrics=['accuracy'], acc and val_acc.  Every process draws its own batches: there is
+        no sharding of a generator."""
+        from .callbacks import History
+        if self.optimizer is None:
+            raise RuntimeError("call compile() before fit_generator()")
+        tr = self._get_trainer()
+        acc_on = self._accuracy
+        hist = History()
+        cbs = [hist] + list(callbacks or [])
+        for cb in cbs:
+            cb.set_model(self)
+            cb.on_train_begin()
+        self.stop_training = False
+
+        def device_batch(xb, yb):
+            yb = _as_f32(self._fit_target(yb))
+            return [self._to_device(a) for a in self._fit_inputs(xb)] + [self._to_device(yb)], yb.shape
+
+        for epoch in range(initial_epoch, epochs):
+            meter = _EpochMeter(self.device, False)      # no host synchronisation per step (_keras_fit)
+            if acc_on and tr.acc_matches is not None:
+                tr.acc_matches.zero_()
+            for _ in range(steps_per_epoch):
+                batch, shape = device_batch(*next(generator))
+                meter.add(tr.train_step(*batch), shape[0], rows=tr.metric_rows(shape) if acc_on else 0)
+            logs = {"loss": meter.loss(), "lr": tr.lr}
+            if acc_on:
+                logs["acc"] = meter.acc(tr.acc_matches) if tr.acc_matches is not None else 0.0
+            if validation_data is not None and validation_steps:
+                vmeter = _EpochMeter(self.device, acc_on)
+                for _ in range(validation_steps):
+                    batch, shape = device_batch(*next(validation_data))
+                    if acc_on:
+                        vloss, vmatches = tr.eval_metrics(*batch)
+                        vmeter.add(vloss, shape[0], vmatches, tr.metric_rows(shape))
+                    else:
+                        vmeter.add(tr.eval_loss(*batch), shape[0])
+                logs["val_loss"] = vmeter.loss()
+                if acc_on:
+                    logs["val_acc"] = vmeter.acc()
+            self._finish_epoch(tr, cbs, epoch, logs)
+            if self.stop_training:
+                break
+        for cb in cbs:
+            cb.on_train_end()
+        return hist
 
 
 class _SubModel:
@@ -1042,7 +1206,7 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         self._w = w
         self._init_surface(_MIX_ORDER, impl, device)
 
-    # ---- training surface: KerasModelSurface (given_others...py:308 compile, :500-506 fit) + fit_generator (:494-498) ----
+    # ---- training surface: KerasModelSurface (given_others...py:308 compile, :500-506 fit, :494-498 fit_generator) ----
     def _make_trainer(self, optimizer):
         from .training import OthersMixingTrainer, PaddedTrainer
         make = lambda w: OthersMixingTrainer(w, act=self.recurrent_activation, impl=self.impl, optimizer=optimizer, lr=self._lr,
@@ -1051,49 +1215,6 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         if Hp != self.latent_dim:      # the script's latent_dim = 32: the fused H = 256 kernels on zero-padded weights (exact)
             return PaddedTrainer(make, self._w, self.latent_dim, Hp, hidden_inputs=("enc2_K", "dec2_K"))
         return make(self._w)
-
-    def fit_generator(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None,
-                      callbacks=None, use_multiprocessing=False, shuffle=True, initial_epoch=0, verbose=0):
-        """Keras `fit_generator` (given_others...py:494-498): `steps_per_epoch` batches per epoch from a generator
-        yielding ([enc, others, dec_in], target); validation_data may be a generator (validation_steps batches)."""
-        import torch
-        from .callbacks import History
-        if self.optimizer is None:
-            raise RuntimeError("call compile() before fit_generator()")
-        tr = self._get_trainer()
-        d = lambda a: torch.from_numpy(_as_f32(a)).to(self.device)
-        hist = History()
-        cbs = [hist] + list(callbacks or [])
-        for cb in cbs:
-            cb.set_model(self)
-            cb.on_train_begin()
-        self.stop_training = False
-        for epoch in range(initial_epoch, epochs):
-            tot_t, cnt = torch.zeros(1, dtype=torch.float64, device=self.device), 0   # no host synchronisation per step (_keras_fit)
-            for _ in range(steps_per_epoch):
-                xb, yb = next(generator)
-                loss = tr.train_step(*[d(a) for a in xb], d(yb))
-                tot_t.add_(loss.reshape(1).double(), alpha=float(len(yb)))
-                cnt += len(yb)
-            tot = float(tot_t.item())
-            logs = {"loss": tot / max(cnt, 1), "lr": tr.lr}
-            if validation_data is not None and validation_steps:
-                vt, vc = 0.0, 0
-                for _ in range(validation_steps):
-                    xb, yb = next(validation_data)
-                    vt += float(tr.eval_loss(*[d(a) for a in xb], d(yb)).item()) * len(yb)
-                    vc += len(yb)
-                logs["val_loss"] = vt / max(vc, 1)
-            tr.check()
-            self._w = tr.weights_numpy()
-            self._dw = None
-            for cb in cbs:
-                cb.on_epoch_end(epoch, logs)
-            if self.stop_training:
-                break
-        for cb in cbs:
-            cb.on_train_end()
-        return hist
 
     def _run_width(self):
         """Width the inference kernels run at.  H < 256 (the script's latent_dim = 32): 256 with zero-padded weights,
@@ -1666,3 +1787,12 @@ class _TrajectoryTrainer:
 
     def eval_loss(self, enc_xyz, dec_xyz, target_xyz):
         return self._tr.eval_loss(*self._model._trajectory_maps(enc_xyz, dec_xyz, target_xyz))
+
+    def eval_metrics(self, enc_xyz, dec_xyz, target_xyz):
+        return self._tr.eval_metrics(*self._model._trajectory_maps(enc_xyz, dec_xyz, target_xyz))
+
+    def metric_rows(self, target_shape):
+        """target_xyz (n, T, 30, 3) or (n, T, 1, 30, 3) stands for n * T maps; a map's pixel rows are what ops.one_hot_maps
+        builds (ops.ONE_HOT_MAP_HW)."""
+        from . import ops
+        return int(target_shape[0]) * int(target_shape[1]) * ops.ONE_HOT_MAP_HW[0] * ops.ONE_HOT_MAP_HW[1]

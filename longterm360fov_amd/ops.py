@@ -1408,6 +1408,7 @@ def window_stacks(x, T, stride, collapse_user=True):
 
 
 ONEHOT_BIN_SIZE = 10    # the only bin size: it fixes the ConvLSTM model's 36 x 18 map geometry
+ONE_HOT_MAP_HW = (360 // ONEHOT_BIN_SIZE, 180 // ONEHOT_BIN_SIZE)    # (36, 18): the maps one_hot_maps writes
 
 
 def _onehot_check_bin(bin_size):
@@ -1475,7 +1476,7 @@ def one_hot_maps(src, channels=30, out=None, time_major=False, bin_size=10):
         raise ValueError("channels must be 30 or 32")
     lead = src.shape[:2] if isinstance(src, torch.Tensor) else src[0].shape[:2]
     N, T = int(lead[0]), int(lead[1])
-    shape = ((T, N) if time_major else (N, T)) + (36, 18, channels)
+    shape = ((T, N) if time_major else (N, T)) + ONE_HOT_MAP_HW + (channels,)
     dev = src.device if isinstance(src, torch.Tensor) else src[0].device
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -1561,3 +1562,60 @@ def heatmap_index_xyz(index):
         raise ValueError(L.fov_last_error().decode("utf-8", "replace"))
     check(code)
     return xyz
+
+
+def _accuracy_dims(pred, target):
+    """The rows of two tensors of one logical shape (..., C) as at most three joint dims (n0, n1, rows): size-1 dims carry no
+    stride, neighbours merge where BOTH tensors address them with one stride.  -> [(n, pred stride, target stride)] * 3, outer
+    dims of size 1 in front.  ValueError when more than two outer dims remain."""
+    C = pred.shape[-1]
+    dims = [(n, sp, st) for n, sp, st in zip(pred.shape[:-1], pred.stride()[:-1], target.stride()[:-1]) if n != 1]
+    merged = []
+    for n, sp, st in reversed(dims):         # innermost first
+        if merged and sp == merged[-1][0] * merged[-1][1] and st == merged[-1][0] * merged[-1][2]:
+            merged[-1] = (merged[-1][0] * n, merged[-1][1], merged[-1][2])
+        else:
+            merged.append((n, sp, st))
+    if len(merged) > 3:
+        raise ValueError("categorical_accuracy: shapes %s with strides %s and %s need %d row dims; the kernel addresses rows "
+                         "by two outer strides and a row stride" % (tuple(pred.shape), tuple(pred.stride()), tuple(target.stride()), len(merged)))
+    if not merged:
+        merged = [(1, C, C)]
+    return [(1, 0, 0)] * (3 - len(merged)) + merged[::-1]
+
+
+def categorical_accuracy(pred, target, out=None, accumulate=False):
+    """The number of rows on which `pred` and `target` agree under Keras 2.1-2.2's 'accuracy' metric
+    (model.compile(metrics=['accuracy']), given_others_gt_mean_var_seq2seq.py:308, convlstm_heatmap.py:281): C > 1
+    categorical_accuracy, argmax(target, -1) == argmax(pred, -1) (lowest index among equal maxima, the first NaN is the
+    maximum); C == 1 binary_accuracy, target == rint(pred) per element.  utility.categorical_accuracy is the NumPy mirror.
+    pred, target: float32 device tensors of one logical shape (..., C), each with unit last stride and a uniform row stride
+    over the innermost dims that collapse in both; at most two outer strides may differ between them (a time-major
+    prediction viewed batch-major against a batch-major target, a 30-of-32-channel view): nothing is copied, anything else
+    raises ValueError.  -> int64 (1,) device tensor: `out` when given (overwritten, or added to with accumulate=True)."""
+    for name, t in (("pred", pred), ("target", target)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 1):
+            raise ValueError("%s must be a float32 (..., C) tensor on the GPU" % name)
+    if pred.shape != target.shape:
+        raise ValueError("categorical_accuracy: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    C = pred.shape[-1]
+    if C == 0:
+        raise ValueError("categorical_accuracy: a row of no channels has no maximum")
+    if C > 1 and (pred.stride(-1) != 1 or target.stride(-1) != 1):
+        raise ValueError("categorical_accuracy: the channels of a row must be contiguous")
+    if out is None:
+        if accumulate:
+            raise ValueError("categorical_accuracy: accumulate=True needs the count to add to (out)")
+        out = torch.empty(1, dtype=torch.int64, device=pred.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.numel() == 1):
+        raise ValueError("out must be an int64 tensor of one element on the GPU")
+    if pred.numel() == 0:
+        (n0, p0, t0), (n1, p1, t1), (rows, prs, trs) = (0, 0, 0), (1, 0, 0), (1, C, C)
+    else:
+        (n0, p0, t0), (n1, p1, t1), (rows, prs, trs) = _accuracy_dims(pred, target)
+        if min(p0, t0, p1, t1) < 0 or min(prs, trs) < C:
+            raise ValueError("categorical_accuracy: rows overlap (row strides %d / %d below the %d channels) or a stride is negative"
+                             % (prs, trs, C))
+    check(_lib.lib().fov_categorical_accuracy(pred.data_ptr(), p0, p1, prs, target.data_ptr(), t0, t1, trs, n0, n1, rows, C,
+                                              out.data_ptr(), 1 if accumulate else 0, _stream()))
+    return out

@@ -178,7 +178,9 @@ class FlatParamTrainer:
         weight = self._begin_step(inputs[0].shape[0], n_global)
         deferring = self._defer_begin()
         try:
-            loss, _ = self.forward_backward(*inputs, grad_weight=weight, **kw)
+            loss, pred = self.forward_backward(*inputs, grad_weight=weight, **kw)
+            if self.count_accuracy:      # right here: the prediction lies in a buffer the next forward overwrites
+                self._count_matches(pred, inputs[-1], self._acc_counter("acc_matches", zero=True), accumulate=True)
         finally:
             if deferring:
                 ops.reduce_defer_end(self.grad)      # flushes: every gradient is final from here on
@@ -218,10 +220,47 @@ class FlatParamTrainer:
             self._dp_guard = None
         return loss
 
+    def _eval_forward(self, *inputs):
+        """-> (loss (1,), prediction) of one batch without an update: through the training forward (gradients are overwritten
+        by the next step) unless the trainer has a forward of its own for it."""
+        return self.forward_backward(*inputs)
+
     def eval_loss(self, *inputs):
-        """Validation loss through the training forward (gradients are overwritten by the next step)."""
-        loss, _ = self.forward_backward(*inputs)
-        return loss
+        """Validation loss (see _eval_forward)."""
+        return self._eval_forward(*inputs)[0]
+
+    # ---- the Keras 'accuracy' metric (model.compile(metrics=['accuracy'])): counted on the device, read once per epoch ----
+    # Off (the default), nothing of it exists: no buffer, no launch.  On (the model's compile sets it), train_step adds every
+    # step's matching rows into self.acc_matches, a device int64 (1,) that the fit loop reads and zeroes once per epoch.
+    count_accuracy = False
+    acc_matches = None
+    _eval_matches = None
+
+    def _acc_counter(self, name, zero=False):
+        buf = getattr(self, name)
+        if buf is None:
+            buf = (torch.zeros if zero else torch.empty)(1, dtype=torch.int64, device=self.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _metric_pair(self, pred, target):
+        """What of (prediction, target) the metric compares: same logical shape (..., C), views only."""
+        return pred, target
+
+    def metric_rows(self, target_shape):
+        """Rows the metric counts over for a target of this shape (known on the host): every (..., C) row - for C == 1
+        (Keras's binary_accuracy) that is every element."""
+        return int(np.prod(target_shape[:-1])) if int(target_shape[-1]) else 0
+
+    def _count_matches(self, pred, target, out, accumulate):
+        p, t = self._metric_pair(pred, target)
+        return ops.categorical_accuracy(p, t, out=out, accumulate=accumulate)
+
+    def eval_metrics(self, *inputs):
+        """-> (loss (1,), matches int64 (1,)) of one batch through eval_loss's forward: the rows on which prediction and target
+        agree under Keras's accuracy (ops.categorical_accuracy).  Both lie in buffers the NEXT call overwrites."""
+        loss, pred = self._eval_forward(*inputs)
+        return loss, self._count_matches(pred, inputs[-1], self._acc_counter("_eval_matches"), accumulate=False)
 
 
 def _pad_gates(a, H, Hp):
@@ -436,11 +475,11 @@ class Seq2SeqTrainer(FlatParamTrainer):
                          dR=g["enc_R"], db=g["enc_b"], act=act, dz=bufs["dz_enc"], scratch=self.bwd_scratch, dtype="bf16")
         return loss, y
 
-    def eval_loss(self, enc, dec_in, target):
+    def _eval_forward(self, enc, dec_in, target):
         y = ops.seq2seq_teacher_forced(enc, dec_in, self.w, act=self.act, impl=self.impl, workspace=self.ws,
                                        dtype=self.dtype)
         _, loss = ops.mse_dense_grad(y, target, None, scratch=self.scratch)
-        return loss
+        return loss, y
 
 
 def self_fed_weight_order(add_residual_link=False, embed_frame_state_enc2dec=False, has_reconstruct_loss=False):
@@ -482,6 +521,16 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
         self.embed, self.recons = bool(embed_frame_state_enc2dec), bool(has_reconstruct_loss)
         self._alloc(weights, self_fed_weight_order(self.residual, self.embed, self.recons), optimizer, lr, device)
         self.dact = dense_activation
+
+    def _metric_pair(self, pred, target):
+        """With the reconstruction decoder Keras logs one accuracy per output; `acc` here is the prediction output's: the
+        first O channels of the concatenated (B,T_out,O+F) pair, as they lie."""
+        O = self.w["dense_W"].shape[1]
+        return (pred[..., :O], target[..., :O]) if self.recons else (pred, target)
+
+    def metric_rows(self, target_shape):
+        O = self.w["dense_W"].shape[1]
+        return super().metric_rows(tuple(target_shape[:-1]) + (O,)) if self.recons else super().metric_rows(target_shape)
 
     def _dense(self, x, W, b, out=None, dact=None):
         dact = dact or self.dact
@@ -1692,9 +1741,9 @@ class ConvLSTMTrainer(FlatParamTrainer):
             loss = ops.act_bwd(reg, reg, base=loss, activation=None)
         return dP, loss
 
-    def eval_loss(self, enc, dec0, target):
+    def _eval_forward(self, enc, dec0, target):
         P, _ = self._forward(enc, dec0, target.shape[1])
-        return self._loss(P, target.transpose(0, 1).contiguous())[1]
+        return self._loss(P, target.transpose(0, 1).contiguous())[1], P.transpose(0, 1)
 
 
 class TFLSTMTrainer(FlatParamTrainer):

@@ -16,6 +16,8 @@ reference's functions):
     heatmap_argmax           mycode/convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558 (the test loops' max_ind;
                              ops.heatmap_argmax computes the same on the device); bin_centre_xyz is the way back from a
                              pixel number to a frame centre
+    categorical_accuracy     Keras 2.1-2.2 keras/metrics.py categorical_accuracy / binary_accuracy, the `acc` the scripts'
+                             compile(metrics=['accuracy']) logs (ops.categorical_accuracy counts the same on the device)
 """
 import numpy as np
 
@@ -221,6 +223,22 @@ def bin_centre_xyz(index, bin_size=10):
     az = np.deg2rad((i // W + 0.5) * bin_size)
     el = np.deg2rad((i % W + 0.5) * bin_size - 90.0)
     return np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=-1)
+
+
+def categorical_accuracy(pred, target):
+    """(matches, rows) of the 'accuracy' metric Keras 2.1-2.2 logs for model.compile(metrics=['accuracy'])
+    (given_others_gt_mean_var_seq2seq.py:308, convlstm_heatmap.py:281; keras/engine/training.py): for (..., C) arrays with
+    C > 1 categorical_accuracy, the rows with np.argmax(target, -1) == np.argmax(pred, -1) - the lowest index among equal
+    maxima, -0.0 == +0.0, the first NaN of a row is its maximum -; with C == 1 binary_accuracy, the elements with
+    target == np.rint(pred) (half to even).  acc = matches / rows.  ops.categorical_accuracy counts the same on the device."""
+    p, t = np.asarray(pred), np.asarray(target)
+    if p.shape != t.shape or p.ndim < 1 or p.shape[-1] == 0:
+        raise ValueError("categorical_accuracy: pred %s and target %s must share a shape (..., C), C >= 1" % (p.shape, t.shape))
+    if p.shape[-1] == 1:
+        return int(np.count_nonzero(t == np.rint(p))), int(p.size)
+    if p.size == 0:
+        return 0, 0
+    return int(np.count_nonzero(np.argmax(t, axis=-1) == np.argmax(p, axis=-1))), int(p.size // p.shape[-1])
 
 
 def get_shuffle_index(data_length, rng=None):
