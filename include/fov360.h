@@ -820,6 +820,29 @@ int64_t fov_window_count(int S, int T, int stride);
 int fov_window_stacks(const float* x, float* enc, float* fut, float* fut_in, int U, int S, int feat, int T,
                       int stride, int collapse_user, fov_stream_t stream);
 
+/* The seq2seq LSTM models' inputs gathered from tracks that stay on the device (wired in):
+ *   replaces: mycode/utility.py:264-305, 359-446, 483-517 (reshape2second_stacks, get_data, get_gt_target_xyz[_oth]),
+ *             mycode/given_others_gt_mean_var_seq2seq.py:675-695 and mycode/data_generator_including_saliency.py:93-182.
+ * secs (rows, 3*fps): every whole second of every (video, user) track, a track a contiguous run of rows; feat (rows, 6) =
+ * fov_meanvar_xyz(secs).  sample (n, 3) int32: [first row of the target's track, row of others_base, first second of the
+ * window]; others_base (n_pairs, n_others) int32: the first rows of the tracks in the others' slots of a (video, target)
+ * pair (NULL when n_others == 0).  Outputs, contiguous, any of them NULL (not written):
+ *   enc        (n, T_in, enc_width)       seconds start .. start+T_in-1 of the target: raw from secs when enc_width == 3*fps,
+ *                                         from feat when enc_width == 6; any other width of a non-NULL enc: FOV_ERR_INVALID
+ *   dec_in     (n, 6)                     feat of second start+T_in-1 (the decoder's seed: the encoder's last second)
+ *   target     (n, T_out, 6)              feat of the target at start+fut_offset+t
+ *   others     (n, T_out, n_others, 6)    feat at others_base[pair][j] + start+fut_offset+t
+ *   future_raw (n, T_out, 3*fps)          secs of the target at start+fut_offset+t
+ * Bit copies, no arithmetic; ONE launch per call, 8-byte accesses when every base is 8-byte aligned and 3*fps is even,
+ * else 4-byte ones (same result).  Nothing outside the tables is read: a sample is taken only if base >= 0, start >= 0 and
+ * base + start + max(T_in, fut_offset + T_out) <= rows, else all its outputs are zeros; an others slot also needs
+ * 0 <= pair < n_pairs and its own track's seconds inside [0, rows), else that slot is zeros.  That a track is as long as
+ * the samples say is the caller's business (rows of the next track would be copied).  n == 0: FOV_OK, no launch. */
+int fov_window_inputs(const float* secs, const float* feat, int64_t rows, int fps, const int32_t* sample, int64_t n,
+                      const int32_t* others_base, int64_t n_pairs, int n_others, int T_in, int T_out, int fut_offset,
+                      float* enc, int enc_width, float* dec_in, float* target, float* others, float* future_raw,
+                      fov_stream_t stream);
+
 /* FoV hit rate per predicted second, the evaluation step that consumes the path's output:
  * centres as unit xyz vectors -> (theta, phi) (mycode/dataIO.py:77-82), +-2pi seam fix
  * (baseline_knn_mean.py:78-85), area(pred box ^ gt box) / area(gt box) (:62-82).  Row strides in floats

@@ -138,6 +138,7 @@ SIGNATURES = {
     "fov_colsum": (_I, [_P, _P, ctypes.c_int64, _I, _I, _P, _SZ, _P]),
     "fov_window_count": (ctypes.c_int64, [_I, _I, _I]),
     "fov_window_stacks": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "fov_window_inputs": (_I, [_P, _P, ctypes.c_int64, _I, _P, ctypes.c_int64, _P, ctypes.c_int64] + [_I] * 4 + [_P, _I] + [_P] * 5),
     "fov_fov_hit_rate": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P]),
     "fov_onehot_maps": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _I, _P, _P, _P,
                              _I, _I, _P]),

@@ -126,26 +126,115 @@ def _train_acc(trainer, meter):
     return meter.acc(counter)
 
 
+class _ArrayFeed:
+    """The fit loop's batches cut from host arrays (fit, fit_trajectories): the model's inputs and the target, and what is
+    held out for validation."""
+
+    def __init__(self, model, inputs, y, validation_split, validation_data):
+        self.model = model
+        self.inputs = [_as_f32(a) for a in inputs]
+        self.tgt = _as_f32(y)
+        n = self.inputs[0].shape[0]
+        self.val = None
+        self.n_train = n
+        if validation_data is not None:
+            self.val = ([_as_f32(a) for a in validation_data[0]], _as_f32(validation_data[1]))
+        elif validation_split and 0.0 < validation_split < 1.0:
+            self.n_train = int(n * (1.0 - validation_split))
+            self.val = ([a[self.n_train:] for a in self.inputs], self.tgt[self.n_train:])
+        self.n_val = 0 if self.val is None else len(self.val[1])
+        self.target_shape = self.tgt.shape[1:]
+        self.val_target_shape = None if self.val is None else self.val[1].shape[1:]
+        # The training set lives on the device for the whole fit() when it fits (FOV_FIT_RESIDENT_BYTES, default 8 GiB of the
+        # 288): a batch is then a device gather by the epoch's permutation (or a plain slice without shuffling) instead of a
+        # NumPy fancy-index + three pageable uploads per step - at the reference's batch of 32 the host path was a quarter of
+        # the step (fit() 0.345 ms per step against 0.26 ms for the bare train_step, tools/fit_epoch_time.py).
+        self.limit = int(os.environ.get("FOV_FIT_RESIDENT_BYTES", str(8 << 30)))
+        self.val_dev = None
+        self.resident = sum(a.nbytes for a in self.inputs) + self.tgt.nbytes <= self.limit
+        self.dev_arrays = [self._d(a) for a in self.inputs] + [self._d(self.tgt)] if self.resident else None
+
+    def _d(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.model.device)
+
+    def begin_epoch(self, idx, shuffle):
+        import torch
+        self.shuffle = shuffle
+        self.idx_dev = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.model.device) \
+            if (self.resident and shuffle) else None
+        # ... and when twice the training set fits, the WHOLE epoch is gathered once (three launches per epoch): a batch is then
+        # a contiguous slice - at the reference's batch of 32 the three per-step gathers were 11 us of GPU time and as much host
+        # time again in a 0.13 ms step
+        self.epoch_arrays = None
+        if self.idx_dev is not None and 2 * (sum(a.nbytes for a in self.inputs) + self.tgt.nbytes) <= self.limit:
+            self.epoch_arrays = [t.index_select(0, self.idx_dev) for t in self.dev_arrays]
+
+    def train_batch(self, lo, hi, lidx):
+        """Rows lo .. hi-1 of the epoch's order, which are the rows `lidx` of the arrays -> device [*inputs, target]."""
+        if not self.resident:
+            return [self._d(arr[lidx]) for arr in self.inputs] + [self._d(self.tgt[lidx])]
+        if self.epoch_arrays is not None:
+            return [t[lo:hi] for t in self.epoch_arrays]
+        if self.shuffle:
+            sel = self.idx_dev[lo:hi]
+            return [t.index_select(0, sel) for t in self.dev_arrays]
+        return [t[lo:hi] for t in self.dev_arrays]   # idx is the identity: contiguous rows, no copy
+
+    def val_batch(self, lo, hi):
+        val = self.val
+        if self.val_dev is None and sum(a.nbytes for a in val[0]) + val[1].nbytes <= self.limit:
+            self.val_dev = [self._d(a) for a in val[0]] + [self._d(val[1])]      # uploaded once per fit()
+        sl = slice(lo, hi)
+        return [t[sl] for t in self.val_dev] if self.val_dev is not None else [self._d(arr[sl]) for arr in val[0]] + [self._d(val[1][sl])]
+
+
+class _DatasetFeed:
+    """The fit loop's batches gathered from a TrajectoryDataset (fit_dataset): each step's tensors are written by one
+    ops.window_inputs launch right before the step, from the epoch's permuted sample rows (three ints a window)."""
+
+    def __init__(self, model, train, val):
+        self.model, self.train, self.val = model, train, val
+        self.enc = model._dataset_check(train)
+        self.n_train = len(train)
+        self.n_val = 0 if val is None else len(val)
+        self.target_shape = self.val_target_shape = (train.T_out, 6)
+
+    def _batch(self, ds, sample):
+        b = ds._gather(sample, ds._names(False), self.enc)
+        return list(self.model._dataset_inputs(b)) + [b["target"]]
+
+    def begin_epoch(self, idx, shuffle):
+        import torch
+        rows = self.train._dev["sample"]
+        if shuffle:
+            rows = rows.index_select(0, torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(rows.device))
+        self.rows = rows
+
+    def train_batch(self, lo, hi, lidx):
+        return self._batch(self.train, self.rows[lo:hi])
+
+    def val_batch(self, lo, hi):
+        return self._batch(self.val, self.val._dev["sample"][lo:hi])
+
+
 def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, shuffle, callbacks, initial_epoch,
                validation_data):
+    """Keras `Model.fit` on host arrays: see _fit_loop for the semantics."""
+    return _fit_loop(model, trainer, _ArrayFeed(model, inputs, y, validation_split, validation_data), batch_size, epochs, shuffle,
+                     callbacks, initial_epoch)
+
+
+def _fit_loop(model, trainer, feed, batch_size, epochs, shuffle, callbacks, initial_epoch):
     """Keras `Model.fit` loop shared by the model objects: the LAST `validation_split` fraction is held out
-    BEFORE shuffling, train indices are permuted every epoch (np.random), the last partial batch is used,
+    BEFORE shuffling (by the feed), train indices are permuted every epoch (np.random), the last partial batch is used,
     callbacks see {'loss','val_loss','lr'} and, compiled with metrics=['accuracy'], {'acc','val_acc'} (Keras 2.1-2.2's
     keys).  Under torch.distributed every rank takes its contiguous shard
-    of each global batch (one gradient all-reduce per step inside trainer.train_step)."""
-    import torch
+    of each global batch (one gradient all-reduce per step inside trainer.train_step).  feed: where the batches come from,
+    host arrays (_ArrayFeed) or a device dataset (_DatasetFeed)."""
     from . import parallel
     from .callbacks import History
-    inputs = [_as_f32(a) for a in inputs]
-    tgt = _as_f32(y)
-    n = inputs[0].shape[0]
-    val = None
-    n_train = n
-    if validation_data is not None:
-        val = ([_as_f32(a) for a in validation_data[0]], _as_f32(validation_data[1]))
-    elif validation_split and 0.0 < validation_split < 1.0:
-        n_train = int(n * (1.0 - validation_split))
-        val = ([a[n_train:] for a in inputs], tgt[n_train:])
+    n_train = feed.n_train
     hist = History()
     cbs = [hist] + list(callbacks or [])
     for cb in cbs:
@@ -153,15 +242,6 @@ def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, 
         cb.on_train_begin()
     model.stop_training = False
     rank, world = parallel.world()
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(model.device)
-    # The training set lives on the device for the whole fit() when it fits (FOV_FIT_RESIDENT_BYTES, default 8 GiB of the
-    # 288): a batch is then a device gather by the epoch's permutation (or a plain slice without shuffling) instead of a
-    # NumPy fancy-index + three pageable uploads per step - at the reference's batch of 32 the host path was a quarter of
-    # the step (fit() 0.345 ms per step against 0.26 ms for the bare train_step, tools/fit_epoch_time.py).
-    limit = int(os.environ.get("FOV_FIT_RESIDENT_BYTES", str(8 << 30)))
-    val_dev = None
-    resident = sum(a.nbytes for a in inputs) + tgt.nbytes <= limit
-    dev_arrays = [d(a) for a in inputs] + [d(tgt)] if resident else None
     for epoch in range(initial_epoch, epochs):
         idx = np.arange(n_train)
         if shuffle:
@@ -169,13 +249,7 @@ def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, 
             # every rank must slice the SAME permutation: rank 0's is broadcast (the ranks' np.random states are
             # not synchronised), then each takes its contiguous shard of every global batch
             idx = parallel.broadcast_index(idx)
-        idx_dev = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(model.device) if (resident and shuffle) else None
-        # ... and when twice the training set fits, the WHOLE epoch is gathered once (three launches per epoch): a batch is then
-        # a contiguous slice - at the reference's batch of 32 the three per-step gathers were 11 us of GPU time and as much host
-        # time again in a 0.13 ms step
-        epoch_arrays = None
-        if idx_dev is not None and 2 * (sum(a.nbytes for a in inputs) + tgt.nbytes) <= limit:
-            epoch_arrays = [t.index_select(0, idx_dev) for t in dev_arrays]
+        feed.begin_epoch(idx, shuffle)
         # the epoch's loss sum stays on the device (fp64): no host synchronisation per step, so the launches of step k + 1 are
         # queued while step k runs (the returned loss tensor is overwritten by the NEXT step: the add is queued before it)
         # ... and so do the matches of the accuracy metric, in the trainer's own accumulator: two more reads per epoch, none per step
@@ -187,32 +261,20 @@ def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, 
         for lo in range(0, n_train, batch_size):
             gidx = idx[lo:lo + batch_size]
             a, b = parallel.shard_range(len(gidx), rank, world)
-            lidx = gidx[a:b]
-            if not resident:
-                batch = [d(arr[lidx]) for arr in inputs] + [d(tgt[lidx])]
-            elif epoch_arrays is not None:
-                batch = [t[lo + a:lo + b] for t in epoch_arrays]
-            elif shuffle:
-                sel = idx_dev[lo + a:lo + b]
-                batch = [t.index_select(0, sel) for t in dev_arrays]
-            else:
-                batch = [t[lo + a:lo + b] for t in dev_arrays]   # idx is the identity: contiguous rows, no copy
+            batch = feed.train_batch(lo + a, lo + b, gidx[a:b])
             loss = step(*batch, n_global=len(gidx))
-            meter.add(loss, len(gidx), rows=trainer.metric_rows((len(gidx),) + tgt.shape[1:]) if acc_on else 0)
+            meter.add(loss, len(gidx), rows=trainer.metric_rows((len(gidx),) + tuple(feed.target_shape)) if acc_on else 0)
         logs = {"loss": meter.loss(), "lr": trainer.lr}
         if acc_on:
             logs["acc"] = _train_acc(trainer, meter)
-        if val is not None and len(val[1]):
-            if val_dev is None and sum(a.nbytes for a in val[0]) + val[1].nbytes <= limit:
-                val_dev = [d(a) for a in val[0]] + [d(val[1])]      # uploaded once per fit()
+        if feed.n_val:
             vmeter = _EpochMeter(model.device, acc_on)
-            for lo in range(0, len(val[1]), max(batch_size, 1)):
-                sl = slice(lo, lo + batch_size)
-                k = len(val[1][sl])
-                vb = [t[sl] for t in val_dev] if val_dev is not None else [d(arr[sl]) for arr in val[0]] + [d(val[1][sl])]
+            for lo in range(0, feed.n_val, max(batch_size, 1)):
+                k = min(batch_size, feed.n_val - lo)
+                vb = feed.val_batch(lo, lo + k)
                 if acc_on:
                     vloss, vmatches = trainer.eval_metrics(*vb)
-                    vmeter.add(vloss, k, vmatches, trainer.metric_rows((k,) + val[1].shape[1:]))
+                    vmeter.add(vloss, k, vmatches, trainer.metric_rows((k,) + tuple(feed.val_target_shape)))
                 else:
                     vmeter.add(trainer.eval_loss(*vb), k)
             logs["val_loss"] = vmeter.loss()
@@ -471,6 +533,91 @@ class KerasModelSurface:
         """Keras `evaluate_generator`: evaluate over `steps` batches (x, y) drawn from the generator."""
         return self._evaluate_batches(self._host_batches(next(generator) for _ in range(steps)), "evaluate_generator")
 
+    # ---- fed from FoV tracks held on the device (trajectories.TrajectoryDataset): what the scripts do with utility.get_data's
+    # arrays (FoV_seq2seq.py:60-117, given_others...py:340-506, 675-695), without those arrays ----
+    _dataset_pick_user = None      # the pick_user a TrajectoryDataset must have been built with; None: no dataset methods
+
+    def _dataset_inputs(self, batch):
+        """The model's inputs, in predict's order, from a TrajectoryDataset batch (dict of device tensors)."""
+        raise NotImplementedError("%s takes no TrajectoryDataset" % type(self).__name__)
+
+    def _dataset_check(self, ds):
+        """-> the encoder form ('raw' | 'mean_var') this model reads from `ds`; ValueError if they do not fit."""
+        if self._dataset_pick_user is None:
+            raise NotImplementedError("%s takes no TrajectoryDataset" % type(self).__name__)
+        if ds._dev is None:
+            raise RuntimeError("this TrajectoryDataset was built with device=None: host tables only")
+        if bool(ds.pick_user) != self._dataset_pick_user:
+            raise ValueError("%s needs a TrajectoryDataset built with pick_user=%s" % (type(self).__name__, self._dataset_pick_user))
+        if self._dataset_pick_user and ds.num_user != self.num_user:
+            raise ValueError("the dataset has num_user=%d, the model %d" % (ds.num_user, self.num_user))
+        if self.num_decoder_tokens != 6:
+            raise ValueError("a TrajectoryDataset's targets are the 6 mean / variance numbers; the model predicts %d" % self.num_decoder_tokens)
+        if self.num_encoder_tokens == 6:
+            return "mean_var"
+        if self.num_encoder_tokens == 3 * ds.fps:
+            return "raw"
+        raise ValueError("encoder width %d is neither 6 nor the dataset's %d" % (self.num_encoder_tokens, 3 * ds.fps))
+
+    def _dataset_chunks(self, ds, batch_size, run, empty):
+        """run(batch dict) over `batch_size` windows of `ds` at a time through _predict_chunks: the chunks are slices of the
+        dataset's device sample table, each gathered right before its run."""
+        enc = self._dataset_check(ds)
+        names = ds._names(False)
+        return self._predict_chunks([ds._dev["sample"]], batch_size, lambda rows: run(ds._gather(rows, names, enc)), empty)
+
+    def predict_dataset(self, ds, batch_size=None):
+        """predict on every window of a TrajectoryDataset, `batch_size` windows per device call (None: all at once)
+        -> NumPy (N, T_out, 6); equal to predict on the arrays ds.batch hands out."""
+        self._device_weights()
+        y = self._dataset_chunks(ds, batch_size, lambda b: self.predict_device(*self._dataset_inputs(b)), (ds.T_out, 6))
+        self._ws.check()
+        return y
+
+    def evaluate_dataset(self, ds, batch_size=None, span_deg=120.0, gt_span_deg=120.0):
+        """-> {'loss': Keras's MSE as evaluate reports it (batch-size-weighted over the chunks; needs compile()),
+        'hit_rate': (T_out,) the mean over the sequences of 'hit_rate_per_sequence': float32 (N, T_out) =
+        ops.fov_hit_rate(prediction, target) per predicted second - the paper's curve}.  The loss is the trainer's
+        evaluation forward, the hit rates are those of predict_dataset's predictions (the inference kernels); predictions
+        and targets stay on the device, the sums too, and the three results are copied out at the end."""
+        import torch
+        from . import ops
+        if self.optimizer is None:
+            raise RuntimeError("call compile() before evaluate_dataset()")
+        tr = self._get_trainer()
+        self._device_weights()
+        meter = _EpochMeter(self.device, False)
+        total = torch.zeros(ds.T_out, dtype=torch.float64, device=self.device)
+
+        def run(b):
+            x = self._dataset_inputs(b)
+            tgt = b["target"]
+            meter.add(tr.eval_loss(*x, tgt), tgt.shape[0])
+            rate = ops.fov_hit_rate(self.predict_device(*x).contiguous(), tgt, span_deg, gt_span_deg)
+            total.add_(rate.sum(0, dtype=torch.float64))
+            return rate
+
+        rates = self._dataset_chunks(ds, batch_size, run, (ds.T_out,))
+        tr.check()
+        self._ws.check()
+        return {"loss": meter.loss(), "hit_rate": (total / max(len(ds), 1)).cpu().numpy(), "hit_rate_per_sequence": rates}
+
+    def fit_dataset(self, ds, batch_size=32, epochs=1, validation_split=0.0, validation_data=None, shuffle=True, callbacks=None,
+                    initial_epoch=0):
+        """fit on a TrajectoryDataset with the Keras semantics of _fit_loop - the last validation_split fraction of the
+        windows held out before shuffling (ds.split), or validation_data, another TrajectoryDataset - each step's tensors
+        gathered on the device right before the step.  Returns a History; equal to fit on the arrays ds.batch hands out."""
+        if self.optimizer is None:
+            raise RuntimeError("call compile() before fit_dataset()")
+        train, val = ds, validation_data
+        if val is not None:
+            self._dataset_check(val)
+        elif validation_split and 0.0 < validation_split < 1.0:
+            n_train = int(len(ds) * (1.0 - validation_split))
+            train, val = ds._view(0, n_train), ds._view(n_train, len(ds))
+        return _fit_loop(self, self._get_trainer(), _DatasetFeed(self, train, val), batch_size, epochs, shuffle, callbacks,
+                         initial_epoch)
+
     def fit_generator(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None,
                       callbacks=None, use_multiprocessing=False, shuffle=True, initial_epoch=0, verbose=0):
         """Keras `fit_generator` (given_others...py:494-498, convlstm_heatmap.py:415-418): `steps_per_epoch` batches per epoch
@@ -606,14 +753,25 @@ class Seq2SeqLSTM(KerasModelSurface):
         -> (N,T_out,F_dec).  `batch_size` chunks the device calls (None = all at once)."""
         enc, dec_in = x
         enc, dec_in = _as_f32(enc), _as_f32(dec_in)
-        ops, dw = self._ops(), self._device_weights()
-        y = self._predict_chunks([enc, dec_in], batch_size, lambda e, d: ops.seq2seq_teacher_forced(
-            e, d, dw, act=self.recurrent_activation, impl=self.impl, workspace=self._ws, dtype=self.dtype),
-            (dec_in.shape[1], self.num_decoder_tokens))
+        self._device_weights()
+        y = self._predict_chunks([enc, dec_in], batch_size, self.predict_device, (dec_in.shape[1], self.num_decoder_tokens))
         self._ws.check()
         return y
 
     predict_on_batch = predict
+
+    def predict_device(self, e, d):
+        """predict on device tensors: e (B,T_in,F_enc), d (B,T_out,F_dec) -> (B,T_out,F_dec) device tensor."""
+        return self._ops().seq2seq_teacher_forced(e, d, self._device_weights(), act=self.recurrent_activation, impl=self.impl,
+                                                  workspace=self._ws, dtype=self.dtype)
+
+    _dataset_pick_user = False
+
+    def _dataset_inputs(self, batch):
+        """[enc, decoder input]: the teacher-forced decoder reads get_gt_target_xyz(future_input) (FoV_seq2seq.py:77), the
+        future shifted right one second and seeded with the encoder's last - the batch's dec_in, then target[:, :-1]."""
+        import torch
+        return [batch["enc"], torch.cat((batch["dec_in"], batch["target"][:, :-1]), dim=1)]
 
     def decode_sequence(self, input_seq, first_decoder_input=None, predict_step=None, batch_size=None):
         """Autoregressive inference (FoV_seq2seq.py:154-178, any batch): encoder, then `predict_step`
@@ -722,6 +880,8 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
             self._w["recd_W"] = glorot_uniform(rng, H, F)
             self._w["recd_b"] = np.zeros(F, np.float32)
         self._order = self_fed_weight_order(self.add_residual_link, self.embed_frame_state_enc2dec, self.has_reconstruct_loss)
+
+    _dataset_pick_user = None      # (the dataset methods are the teacher-forced graph's: not built for this model)
 
     def _pad_extra(self, k, w, Hp):
         """The optional layers that carry the hidden width (FoV_seq2seq_no_teac_forc.py:47-59): the state embeddings
@@ -1182,6 +1342,10 @@ class OthersMixingSeq2Seq(KerasModelSurface):
     hoisted out of the loop as one GEMV batch."""
 
     fused_decoder = True   # H = 256: run the unrolled decoder as ONE launch (fov_mix_decoder_fwd); False = step-wise calls
+    _dataset_pick_user = True
+
+    def _dataset_inputs(self, batch):
+        return [batch["enc"], batch["others"], batch["dec_in"]]
 
     def __init__(self, num_encoder_tokens=None, num_decoder_tokens=6, latent_dim=32, num_user=34,
                  recurrent_activation=None, seed=None, impl="auto", device="cuda", dtype="f32"):

@@ -1407,6 +1407,44 @@ def window_stacks(x, T, stride, collapse_user=True):
     return tuple(outs)
 
 
+WINDOW_INPUT_NAMES = ("enc", "dec_in", "target", "others", "future_raw")
+
+
+def window_inputs(secs, feat, sample, others_base, T_in, T_out, fut_offset, enc_width=None,
+                  outputs=("enc", "dec_in", "target", "others")):
+    """The seq2seq LSTM models' inputs of the windows `sample` names, gathered in ONE launch from the dataset's two device
+    tables (fov_window_inputs): secs (rows, 3*fps) the raw seconds of every track, feat (rows, 6) = meanvar_xyz(secs),
+    sample (n, 3) int32 [target track's first row, row of others_base, first second], others_base (n_pairs, n_others)
+    int32 or None.  outputs: which of WINDOW_INPUT_NAMES to write; enc_width 3*fps (raw, the default) or 6.
+    -> dict name -> tensor: enc (n,T_in,enc_width), dec_in (n,6), target (n,T_out,6), others (n,T_out,n_others,6),
+    future_raw (n,T_out,3*fps).  A sample that points outside the tables gives zeros."""
+    secs, feat = _dev(secs, "secs"), _dev(feat, "feat")
+    rows, raw_w = secs.shape
+    if raw_w % 3 or tuple(feat.shape) != (rows, 6):
+        raise ValueError("secs must be (rows, 3*fps) and feat (rows, 6), got %s and %s" % (tuple(secs.shape), tuple(feat.shape)))
+
+    def _index(t, name, cols):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and
+                (cols is None or t.shape[1] == cols)):
+            raise TypeError("%s must be a contiguous int32 (n, %s) tensor on the GPU" % (name, cols or "n_others"))
+        return t
+
+    sample = _index(sample, "sample", 3)
+    n_pairs, n_others = (0, 0) if others_base is None else _index(others_base, "others_base", None).shape
+    unknown = [k for k in outputs if k not in WINDOW_INPUT_NAMES]
+    if unknown:
+        raise ValueError("unknown outputs %r (known: %r)" % (unknown, WINDOW_INPUT_NAMES))
+    n = sample.shape[0]
+    enc_width = raw_w if enc_width is None else int(enc_width)
+    shapes = {"enc": (n, T_in, enc_width), "dec_in": (n, 6), "target": (n, T_out, 6), "others": (n, T_out, n_others, 6),
+              "future_raw": (n, T_out, raw_w)}
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=secs.device) for k in WINDOW_INPUT_NAMES if k in outputs}
+    check(_lib.lib().fov_window_inputs(_ptr(secs), _ptr(feat), rows, raw_w // 3, _ptr(sample), n, _ptr(others_base), n_pairs,
+                                       n_others, int(T_in), int(T_out), int(fut_offset), _ptr(out.get("enc")), enc_width,
+                                       *[_ptr(out.get(k)) for k in WINDOW_INPUT_NAMES[1:]], _stream()))
+    return out
+
+
 ONEHOT_BIN_SIZE = 10    # the only bin size: it fixes the ConvLSTM model's 36 x 18 map geometry
 ONE_HOT_MAP_HW = (360 // ONEHOT_BIN_SIZE, 180 // ONEHOT_BIN_SIZE)    # (36, 18): the maps one_hot_maps writes
 
