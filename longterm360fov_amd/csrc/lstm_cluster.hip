@@ -59,6 +59,7 @@ constexpr int MODE_LAYER_ZX = 2;   // MODE_LAYER with the input projection preco
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <bool V> struct BoolC { static constexpr bool value = V; };   // a compile-time flag handed to a generic lambda
 
 __device__ __forceinline__ unsigned long long ld_granule(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -374,6 +375,9 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     constexpr bool LAYER = (MODE != MODE_DECODE);
     constexpr bool ZX = (MODE == MODE_LAYER_ZX);      // input projection precomputed by the caller
     constexpr bool F1 = (FUSED == 1), F2 = (FUSED == 2);
+    // The fused call is only taken for inference from a zero encoder state (no p.hs, no p.reserve, no p.h0): the ONE gate is
+    // the condition in launch_cluster, and both phases compile those paths out instead of testing for them in every step.
+    constexpr bool FZ = (FUSED != 0);
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -601,7 +605,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         return (a0 + a1) + (a2 + a3);
     };
 
-    const bool h_zero = !F2 && p.h0 == nullptr;   // (the decoder phase of the fused kernel starts from the encoder's state)
+    const bool h_zero = F1 || (!F2 && p.h0 == nullptr);   // (fused kernel: the encoder phase always starts from zero - launch_cluster's gate -, the decoder phase from the encoder's state)
     for (int tile = group; tile < p.num_tiles && !aborted; tile += p.num_groups) {
         const int b0 = tile * BT;
         // ---- initial state (the previous tile ended on a barrier) ----
@@ -684,7 +688,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         unsigned yoff[2];
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss)
-            yoff[ss] = (!LAYER && 4 * ss + g4 < p.F_dec) ? (unsigned)((n * p.T_out * p.F_dec + 4 * ss + g4) * 4) : OORB;
+            yoff[ss] = (!LAYER && 4 * ss + g4 < p.F_dec && (!F2 || (slice == 0 && wave == 0))) ? (unsigned)((n * p.T_out * p.F_dec + 4 * ss + g4) * 4) : OORB;   // (F2: only the storing wave keeps real offsets, see the steady-state step)
         f32x4 y4 = (f32x4){0.f, 0.f, 0.f, 0.f};   // DECODE: y_{t-1}[n][4*s + g4], the A fragment of y . K
         if (!LAYER) {
             // (buffer loads with an out-of-range offset for the masked elements: a `cond ? load : 0` sits in a branch whose
@@ -738,7 +742,15 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         float xr[XR];
 #pragma unroll
         for (int i = 0; i < XR; ++i) xr[i] = 0.f;
-        for (int t = 0; t < steps; ++t) {
+        // One step.  ST = the steady-state copy of the fused kernel (see the driver loop below): same-XCD exchange, t > 0,
+        // t + 2 < steps (decoder: t + 1 < steps) and, in the encoder phase, six input k-blocks are compile-time facts there,
+        // so its body is straight-line code between the barriers and the bounded spin loops.  Returns false on an abort.
+        auto step = [&](const int t, auto st_c) __attribute__((always_inline)) -> bool {
+            constexpr bool ST = decltype(st_c)::value;
+            const bool t_pos = ST || t > 0;
+            const bool more = ST || (t + 1 < steps);
+            const bool more2 = ST || (t + 2 < steps);
+            const bool sxcd = ST || same_xcd;
             FOV_STAMP(0);
 #ifdef FOV_STAMPS
             if (stamp_on && t < STAMP_STEPS) g_stamps[MODE & 1][t][9] = __builtin_amdgcn_s_memrealtime();
@@ -746,13 +758,15 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             // ---- x pipeline: x_{t+1} (loaded during step t-1) goes registers -> LDS now; its tile
             // was last read two steps ago and is next read after barrier 1b of this step.  Then
             // x_{t+2} is requested, so every load has a full step to land. ----
-            if (LAYER && !ZX && t > 0 && t + 1 < steps) {
+            if (LAYER && !ZX && t_pos && more) {
                 float* xb = xl + ((t + 1) % 3) * BT * LDX;
+                // (ST: all six columns - Fp = 96 - are written; a masked column's load went out of range and returned 0, which
+                // is what the pad columns hold anyway)
 #pragma unroll
                 for (int i = 0; i < XR; ++i)
-                    if (xcl + 16 * i < F) xb[16 * i] = xr[i];
+                    if (ST || xcl + 16 * i < F) xb[16 * i] = xr[i];
             }
-            if (ZX && t + 1 < steps) {
+            if (ZX && more) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -760,14 +774,14 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                         zr[g][r] = bias[g] + __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                                                  zxrs, zxoff + (unsigned)(((r * p.T + (t + 1)) * 4 * H + g * H) * 4), 0, 0));
             }
-            if (LAYER && !ZX && t + 2 < steps) {
+            if (LAYER && !ZX && more2) {
 #pragma unroll
                 for (int i = 0; i < XR; ++i)
                     xr[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xgrs, xoff[i], (unsigned)((t + 2) * F * 4), 0));
             }
             // ---- the part of h_{t-1} . R that needed the partner slices ----
-            if (LAYER || t == 0) {
-                if (!((h_zero || F2) && t == 0)) recurrent<H, 4, NQ, true, true>(acc, hrow, wR);
+            if (LAYER || (!ST && t == 0)) {
+                if (ST || !((h_zero || F2) && t == 0)) recurrent<H, 4, NQ, true, true>(acc, hrow, wR);
             } else {
                 // DECODE: y_{t-1}.  This workgroup's four wave partials are in LDS since barrier 2 of the previous step; the partners'
                 // partials were published right behind THEIR barrier 2, about when this step began - their loads go out half way
@@ -798,6 +812,9 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                         asm volatile("" ::: "memory");
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) vy[q] = __builtin_amdgcn_raw_buffer_load_b128(yrs, ygoff, yso + (unsigned)(q * 1024), 16);
+                        // (a statement of its own behind the unrolled loop: where that loop closed the spin loop's body hipcc handed
+                        // its unroll request on to the SPIN loop and made sixteen copies of it in the step)
+                        asm volatile("");
                     }
                     f32x2 P[NYG];
 #pragma unroll
@@ -813,7 +830,8 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
 #pragma unroll
                 for (int ss = 0; ss < 2; ++ss) y4[ss] = tanh_f(ysum[ss] + bd4[ss]);
                 // y_{t-1} leaves through a buffer store: lane offset computed once per tile, the step in the scalar offset
-                if (slice == 0 && wave == 0) {
+                // (fused kernel: every other wave's offsets are out of range, the steady-state copy stores without asking)
+                if (ST || (slice == 0 && wave == 0)) {
 #pragma unroll
                     for (int ss = 0; ss < 2; ++ss)
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y4[ss]), yors, yoff[ss], (unsigned)((t - 1) * p.F_dec * 4), 0);
@@ -836,7 +854,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                 c[r] = fmaf(fg, c[r], ig * gg);
                 hcur[r] = og * tanh_f(c[r]);
 #endif
-                if (LAYER && p.reserve) {   // training forward: gates and cell state for BPTT
+                if (LAYER && !FZ && p.reserve) {   // training forward: gates and cell state for BPTT
                     const int row = b0 + 4 * g4 + r;
                     if (row < p.B) {
                         float* rp = p.reserve + (((size_t)row * p.T + t) * 5) * H + col0 + n;
@@ -846,12 +864,12 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             }
             unsigned xsoff = 0;
             // h_t of a layer's last step is needed by nobody inside the kernel: no publish, no gather
-            const bool do_xch = (G > 1) && (!LAYER || t + 1 < steps || F1);
+            const bool do_xch = (G > 1) && (!LAYER || more || F1);
             if (do_xch) {
                 // publish this workgroup's slice of h_t: one 8-byte {value, epoch} granule each
                 ++epoch;
                 xsoff = (epoch & 1u) * (unsigned)(BT * H * sizeof(unsigned long long));
-                if (same_xcd) {
+                if (sxcd) {
 #pragma unroll
                     for (int r = 0; r < 2; ++r)
                         __builtin_amdgcn_raw_buffer_store_b128((u32x4g){__float_as_uint(hcur[2 * r]), epoch, __float_as_uint(hcur[2 * r + 1]), epoch},
@@ -863,7 +881,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                                                                xrs, pub_off + r * H * 16, xsoff, 16 /* sc1: write-through */);
                 }
             }
-            if (LAYER && p.hs) {
+            if (LAYER && !FZ && p.hs) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = b0 + 4 * g4 + r;
@@ -880,7 +898,6 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             for (int r = 0; r < 4; ++r) sH[(4 * g4 + r) * LDH + wave * 16 + n] = hcur[r];
             __syncthreads();  // barrier 1b: the own slice of h_t is visible to all four waves
             FOV_STAMP(4);
-            const bool more = (t + 1 < steps);
             // Pre-activations of step t+1 that need no remote data are computed while the partner
             // slices are in flight: x_{t+1} . K first, then the first sweep of the gather is
             // ISSUED (its ~0.9 us round trip runs under the MFMAs that follow), then the own-slice
@@ -888,7 +905,8 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             if (more) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) acc[g] = ZX ? zr[g] : (f32x4){bias[g], bias[g], bias[g], bias[g]};
-                if (LAYER) input_proj_any<true, false>(acc, sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4, sKw, nq, lane);
+                if constexpr (LAYER && ST) input_proj_fixed<6, true, false>(acc, sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4, sKw, lane);
+                else if (LAYER) input_proj_any<true, false>(acc, sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4, sKw, nq, lane);
             }
             FOV_STAMP(5);
             u32x4g v[NG > 0 ? NG : 1];
@@ -962,14 +980,30 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             FOV_STAMP(6);
             __syncthreads();  // barrier 2: the whole h_t tile is in LDS
             FOV_STAMP(7);
-            if (G > 1 && sFlag[0]) { aborted = true; break; }
+            if (G > 1 && sFlag[0]) { aborted = true; return false; }
             if (!LAYER && G > 1 && wave == 0) {      // the workgroup's Dense partial of y_t, tagged like h_t
                 const f32x2 mine = own_partial(t & 1);
                 const u32x4g yg = (u32x4g){__float_as_uint(mine[0]), epoch, __float_as_uint(mine[1]), epoch};
                 const unsigned yso = (epoch & 1u) * YPAR_BYTES;
-                if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(yg, yrs, ypub_off, yso, 1 /* sc0: stays in L2 */);
+                if (sxcd) __builtin_amdgcn_raw_buffer_store_b128(yg, yrs, ypub_off, yso, 1 /* sc0: stays in L2 */);
                 else __builtin_amdgcn_raw_buffer_store_b128(yg, yrs, ypub_off, yso, 16 /* sc1: write-through */);
             }
+            return true;
+        };
+        // The step loop.  Fused kernel on the same-XCD exchange (encoder phase: with the reference's 90-wide input, six
+        // k-blocks): the steps between the first and the last one (encoder: two) run the steady-state copy; the first and
+        // last steps, the write-through exchange and any other input width run the general copy, as every other launch does.
+        {
+            int t = 0;
+            bool go = true;
+            if constexpr (FZ) {
+                constexpr int TAIL = LAYER ? 2 : 1;
+                const bool fast = (G > 1) && same_xcd && (!LAYER || nq == 6);
+                if (steps > 0) { go = step(0, BoolC<false>{}); t = 1; }
+                if (fast)
+                    for (; go && t + TAIL < steps; ++t) go = step(t, BoolC<true>{});
+            }
+            for (; go && t < steps; ++t) go = step(t, BoolC<false>{});
         }
         if (!LAYER && steps > 0 && !aborted) {
             // y of the last step: the workgroups' partials were published behind the last barrier 2 - one wave of the tile waits for them
@@ -1229,8 +1263,10 @@ int launch_cluster(const LstmParams& p_in, bool decode, hipStream_t stream) {
         return launch_cluster_mode(p, MODE_LAYER, stream);
     }
 
-    if (visits == 1 && p.T > 0 && p.T_out > 0 && !p.hs && !p.reserve && !env_knobs().two_launches) {
-        // one tile per group: encoder and decoder as ONE launch (state in registers, h_T tile in LDS)
+    if (visits == 1 && p.T > 0 && p.T_out > 0 && !p.hs && !p.reserve && !p.h0 && !env_knobs().two_launches) {
+        // one tile per group: encoder and decoder as ONE launch (state in registers, h_T tile in LDS).  This condition is
+        // the ONLY gate: the fused kernel's phases compile the p.hs / p.reserve stores and a non-zero encoder state out
+        // (cluster_body: FZ, h_zero)
         LstmParams f = p;
         f.epoch_span = p.T + p.T_out + 2;
         if (int rc_ = xch_account(p.status, f.epoch_span, stream)) return rc_;

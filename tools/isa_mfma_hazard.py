@@ -1,6 +1,9 @@
 """Diagnostic: hipcc pads no hazards around inline-asm MFMAs.  Reports every v_mfma whose A/B source VGPR was written by a
 VALU instruction fewer than 2 wait states earlier (VALU write -> MFMA SrcA/B read, cdna_hip_programming.md 5.7), and every
 VALU / LDS-store / VMEM-store read of an MFMA result fewer than N wait states after the MFMA.
+The scan goes in text order; behind an unconditional s_branch it goes on at the branch's TARGET for as long as an MFMA result
+is young (up to the next branch there), and the block that merely stands behind the branch in the text starts clean - it is
+reached from elsewhere.
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --offload-device-only -o k.s kernel.hip; python tools/isa_mfma_hazard.py k.s [substr]"""
 import re
 import sys
@@ -18,6 +21,45 @@ def regs(tok):
     if m:
         return [int(m.group(1))]
     return []
+
+
+label_line = {}
+for ln, l in enumerate(lines):
+    m = re.match(r"^(\.LBB\w+):", l.strip())
+    if m:
+        label_line[m.group(1)] = ln
+
+
+def mfma_readers(op, toks):
+    """registers an instruction reads that an MFMA may have written"""
+    srcs = toks[1:] if (op.startswith("v_") or op.startswith("ds_read") or "load" in op) else toks
+    return [r for src in srcs for r in regs(src)]
+
+
+def follow(target, slot, pending, name):
+    """straight-line scan from a branch target: reads of MFMA results that are still young"""
+    found = 0
+    for ln in range(label_line[target] + 1, len(lines)):
+        t = lines[ln].strip()
+        if not t or t.startswith((";", ".", "//")) or t.endswith(":"):
+            continue
+        parts = t.split(None, 1)
+        op = parts[0]
+        toks = [a.strip() for a in (parts[1].split(";")[0] if len(parts) > 1 else "").split(",")]
+        if op == "s_nop":
+            slot += int(toks[0]) + 1
+            continue
+        slot += 1
+        if op.startswith(("s_branch", "s_cbranch", "s_endpgm")) or all(slot - w[0] >= 12 for w in pending.values()):
+            break
+        if op.startswith("s_"):
+            continue
+        for r in (mfma_readers(op, toks) if not op.startswith("v_mfma") else []):
+            w = pending.get(r)
+            if w is not None and slot - w[0] < 12:
+                print("%s line %d (behind a branch to %s): %s reads v%d, written %d slot(s) earlier by an MFMA" % (name[:60], ln + 1, target, t[:50], r, slot - w[0]))
+                found += 1
+    return found
 
 
 name = None
@@ -47,11 +89,15 @@ for ln, l in enumerate(lines):
         slot += int(toks[0]) + 1
         continue
     slot += 1
+    if op == "s_branch":
+        if toks[0] in label_line:
+            bad += follow(toks[0], slot, dict(last_mfma_write), name)
+        last_mfma_write = {}
+        continue
     if not op.startswith("v_mfma") and not op.startswith("s_"):
         # MFMA write -> read by anything else (VALU, LDS / memory store, ...): 8-pass fp32 MFMA needs >= 11 wait states
-        srcs = toks[1:] if (op.startswith("v_") or op.startswith("ds_read") or "load" in op) else toks
-        for src in srcs:
-            for r in regs(src):
+        for r in mfma_readers(op, toks):
+            if True:
                 w = last_mfma_write.get(r)
                 if w is not None and slot - w[0] < 12:
                     print("%s line %d: %s reads v%d, written %d slot(s) earlier by an MFMA" % (name[:60], ln + 1, t[:50], r, slot - w[0]))
