@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(ConvArgs g) {
     constexpr int BM = 16 * MI * WAVES_M, BN = 16 * NI * WAVES_N, BK = 16;
     // B fragments (plain convolution with four column tiles per wave): column tile j, lane li stands for GEMM column
     // wn + 4*li + j, so one ds_read_b128 at [k][wn + 4*li] serves all column tiles of a k-step and a lane's outputs are four
-    // consecutive channels (the row permutation of gemm_f32_kernel, train_kernels.hip).  The CELL forms keep
+    // consecutive channels (the row permutation of gemm_f32_kernel, gemm_f32.hip).  The CELL forms keep
     // the 16*j + li map their gate permutation is written for.
     constexpr bool BPERM = CELL == 0 && NI == 4;   // (NI == 2 measured slower with the pair form: 54 -> 46 TFLOP/s at N = 32)
     constexpr int LDA = 24, LDB = BPERM ? BN : BN + 4;

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs g) {
     constexpr int RA = AVEC ? (BM * 4 + 255) / 256 : BM / 16;
     constexpr int RB = BVEC ? (BN * 4 + 255) / 256 : BN / 16;
     constexpr unsigned OOR = 0x80000000u;
-    // row strides and fragment reads as in gemm_f32_kernel (train_kernels.hip, OperandStage): MFMA tile i, row q of a wave is
+    // row strides and fragment reads as in gemm_f32_kernel (gemm_f32.hip, OperandStage): MFMA tile i, row q of a wave is
     // operand row 4*q + (i%4) of its group of four tiles (ds_read_b128 at [k][4*li]) or 2*q + (i%2) of a trailing pair
     constexpr int LDA = BM + (MI % 4 == 0 ? 0 : 8), LDB = BN + (NI % 4 == 0 ? 0 : 8);
     static_assert(MI % 2 == 0 && NI % 2 == 0, "tiles per wave: groups of four plus at most one pair");

@@ -35,6 +35,11 @@ int launch_check(const char* what) {
     return FOV_OK;
 }
 
+int check_launch(const char* what) {
+    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] launched: %s\n", what);   // FOV_DBG_TRACE=1 (with HIP_LAUNCH_BLOCKING=1: the last line names the launch BEFORE a faulting one)
+    return launch_check(what);
+}
+
 // ---------------------------------------------------------------------------------------
 // Dense: y = act(x W + b).  One wave per output row; lanes stride over In, shuffle-reduce.
 // Memory-bound streaming op (x is read once; W stays in L2): used for the teacher-forced

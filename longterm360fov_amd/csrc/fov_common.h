@@ -106,6 +106,7 @@ void set_error(const char* fmt, ...);
 // 2 GiB" when one of them does not fit.
 bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long ldb2, long weight_bytes, long tiles = 0);
 int launch_check(const char* what);   // after a launch: FOV_OK, or FOV_ERR_LAUNCH with the error "<what> launch: <hip string>"
+int check_launch(const char* what);   // launch_check behind the "[fov trace] launched: <what>" line of FOV_DBG_TRACE=1 (the training step's launches)
 // wide-input layer, H = 256, 96 < F <= 256 (lstm_wide.hip)
 bool wide_shape_ok(int F, int H);
 bool wide_narrow_preferred(int B, int F, int H);
@@ -115,7 +116,7 @@ bool wide16_preferred(const float* x, int B, int F, int H);
 int launch_wide16(const LstmParams& p, hipStream_t stream);
 bool wide512_shape_ok(int F, int H, bool zx);   // width 512: 16 workgroups per tile; F <= 96 in-kernel, else precomputed x.K
 int launch_wide(const LstmParams& p, hipStream_t stream);
-// step-wise layer forward on the matrix-core GEMM (train_kernels.hip): hidden widths above the persistent kernels' 256
+// step-wise layer forward on the matrix-core GEMM (lstm_train.hip): hidden widths above the persistent kernels' 256
 bool stepwise_preferred(int B, int F, int H);
 size_t stepwise_workspace_floats(int B, int T, int H);
 int launch_stepwise(const LstmParams& p, float* ws, size_t ws_floats, hipStream_t stream);
@@ -175,7 +176,7 @@ int convlstm_gates_bwd(const float* dh, long lddh, float* dc, const float* gates
 int conv_weight_transpose(const float* w, float* wt, int kh, int kw, int C, int N, hipStream_t stream);
 int softmax_lastdim_bwd(const float* dp, const float* p, float* dy, long rows, int n, hipStream_t stream);
 int splitk_reduce(const float* part, float* out, long n, int S, int accumulate, hipStream_t stream);
-// deferred split reductions of a training step (train_kernels.hip): one reduce launch per step instead of one per product
+// deferred split reductions of a training step (reduce_defer.hip): one reduce launch per step instead of one per product
 int defer_begin(float* grad_base, size_t grad_floats, float* arena, size_t arena_floats, hipStream_t stream);
 int defer_flush(const float* grad_base, hipStream_t stream);
 int defer_end(const float* grad_base, hipStream_t stream);
@@ -268,7 +269,11 @@ int launch_bwd_cluster(const float* R, const float* reserve, const float* c0, co
                        const float* dcT, float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int H, int act,
                        void* xch_ws, hipStream_t stream);
 
-// training side (train_kernels.hip)
+// fp32 matrix-core GEMM (gemm_f32.hip; the strided forms: gemm_f32.h)
+int matmul_f32(const float* a, const float* b, float* c, int M, int K, int N, float* scratch, size_t scratch_floats,
+               hipStream_t stream);
+
+// a layer's training step: BPTT dispatch, weight-gradient products, Dense backward (lstm_train.hip)
 size_t lstm_bwd_workspace_floats(int B, int T, int F, int H);
 int lstm_seq_wgrad(const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db, int B, int T,
                    int F, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream);
@@ -286,6 +291,8 @@ int wgrad_fused(const float* a1, long lda1, long a1_so, int M1, int shift1, cons
                 float* scratch, size_t scratch_floats, hipStream_t stream);
 int dense_bwd(const float* x, const float* W, const float* dpre, float* dx, float* dW, float* db, int N, int In, int Out,
               int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream, int bf16 = 0);
+
+// losses, pointwise kernels and optimizers (loss_optim_kernels.hip)
 int mse_dense_grad(const float* y, const float* target, float* dpre, float* loss, long n, int activation, float* scratch,
                    size_t scratch_floats, hipStream_t stream);
 bool dense_mse_head_shape_ok(long N, int H, int O);
@@ -296,8 +303,6 @@ int mse_dense_grad_w(const float* y, const float* target, float* dpre, float* lo
                      int tmB, int tmT, int O, float* scratch, size_t scratch_floats, hipStream_t stream, float* db = nullptr, int dbO = 0);
 int scale_inplace(float* x, long n, float s, hipStream_t stream);
 int act_bwd(const float* dy, const float* y, const float* base, float* out, long n, int activation, hipStream_t stream);
-int matmul_f32(const float* a, const float* b, float* c, int M, int K, int N, float* scratch, size_t scratch_floats,
-               hipStream_t stream);
 int adam_step(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2, float eps,
               const unsigned* const* guards, long long* applied, hipStream_t stream);   // guards: NULL or three (nullable) timeout words; applied: nullable counter of updates that ran
 int rmsprop_step(float* p, const float* g, float* a, long n, float lr, float rho, float eps, const unsigned* const* guards,

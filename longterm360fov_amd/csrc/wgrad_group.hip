@@ -2,7 +2,7 @@
 //
 // model.fit's backward forms, per layer, dK = x^T dz, dR = h_{t-1}^T dz (h_{-1} = h0) and db = column sums of dz
 // (mycode/lstm.py:556-567 under its train_op; FoV_seq2seq.py:103,112-117 at the reference's batch of 32).  At 320 rows the
-// split-K GEMM of train_kernels.hip spent 64 us in seven launches on the two layers of lstm.py (two fused products, two
+// split-K GEMM of gemm_f32.hip spent 64 us in seven launches on the two layers of lstm.py (two fused products, two
 // h0^T dz_0 products, one skinny product, reduces): every launch is a ~5 us stub around a few microseconds of MFMAs.
 // Here every (problem, 128 x 128 output tile) is one workgroup that walks ALL rows - no split, no partials, no reduce, a fixed
 // summation order - and the problems of a call share the launch:
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void wgrad_group_kernel(WgBatch g) {
 
 // ---- few rows AND few outputs (round 5): the reference's own batch at its widths (32 sequences x 10 steps, H <= 256) -------------
 // At 320 rows a 128 x 128 tile per workgroup leaves a dozen workgroups walking 20 stages each (36 us), and the split products of
-// train_kernels.hip cost seven launches (fused product, h0^T dz_0, dK, two batch reduces: 45 us of config 1's 160 us step).  Here a
+// lstm_train.hip cost seven launches (fused product, h0^T dz_0, dK, two batch reduces: 45 us of config 1's 160 us step).  Here a
 // workgroup owns a 16 x 64 output tile and its FOUR WAVES SPLIT THE ROWS: a wave issues all the loads of its quarter at once (one A
 // value and four consecutive dz values per lane and MFMA step, straight into the MFMA operand registers - no LDS staging, one
 // memory round trip), multiplies, and the four partial tiles are added through LDS in a fixed order.  Problems of a call (both

@@ -392,6 +392,45 @@ def test_persistent_bptt_matches_stepped_and_oracle():
             assert np.abs(s_ - r).max() <= 1e-4 * scale + 1e-9, (H, k)
 
 
+def test_stepped_bptt_hard_sigmoid_matches_oracle(capfd):
+    """The host-stepped recurrence (FOV_BWD_STEPPED=1) with hard_sigmoid gates against the fp64 oracle: H = 64, B = 21 (one full
+    tile and a ragged one), T = 4, F = 11, given initial state, dhs + dhT / dcT; the bound of the sigmoid twin above.
+    The case is the clamped regime of the oracle's generator (47 % of the i / f / o pre-activations beyond +-2.5, so both
+    values of the derivative occur); seed 155 is the first but one whose fp64 pre-activations all keep 1e-3 from the kinks
+    (1.6e-3, asserted below), so the fp32 forward and the oracle take the same branch at every element.  On the CPU the oracle run
+    on fp32 arrays differs from the fp64 one by at most 0.003 of the bound on this case; the GPU's own error is printed per tensor."""
+    from longterm360fov_amd import ops
+    H, B, T, F = 64, 21, 4, 11
+    p = O.regime_lstm(155, F, H, "R1", B, T)
+    assert p["act"] == "hard_sigmoid"
+    dhs, dhT, dcT = O.regime_upstream(156, B, T, H)
+    d64 = lambda a: a.astype(np.float64)
+    x, K, R, b, h0, c0 = (p[k] for k in ("x", "K", "R", "b", "h0", "c0"))
+    hs64, _, _, res64 = O.lstm_layer_train(d64(x), d64(K), d64(R), d64(b), d64(h0), d64(c0), act="hard_sigmoid")
+    z = O.regime_preactivations(d64(x), d64(K), d64(R), d64(b), hs64, d64(h0))
+    gates = np.concatenate([z[..., :2 * H], z[..., 3 * H:]], axis=-1)
+    assert np.abs(np.abs(gates) - 2.5).min() >= 1e-3
+    assert 0.3 < (np.abs(gates) > 2.5).mean() < 0.7
+    ref = O.lstm_layer_backward(d64(x), d64(K), d64(R), d64(h0), d64(c0), hs64, res64, d64(dhs), d64(dhT), d64(dcT), act="hard_sigmoid")
+    hs, _, _, res = ops.lstm_seq_train(dev(x), dev(K), dev(R), dev(b), dev(h0), dev(c0), act="hard_sigmoid")
+    capfd.readouterr()
+    before = {k: os.environ.get(k) for k in ("FOV_BWD_STEPPED", "FOV_DBG_TRACE")}
+    os.environ.update({k: "1" for k in before})
+    try:
+        sc = ops.Scratch()
+        got = ops.lstm_seq_bwd(dev(x), dev(K), dev(R), hs, res, h0=dev(h0), c0=dev(c0), dhs=dev(dhs), dhT=dev(dhT), dcT=dev(dcT),
+                               need_dx=True, need_state_grads=True, act="hard_sigmoid", scratch=sc)
+        sc.check()
+    finally:
+        for k, v in before.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    assert capfd.readouterr().err.count("launched: lstm_bwd_pointwise") == T       # the stepped form ran, one launch per step
+    for k in ("dz", "dx", "dK", "dR", "db", "dh0", "dc0"):
+        a, r = got[k].cpu().numpy().astype(np.float64), ref[k]
+        print("%-4s max|ref| %.3e  stepped hard_sigmoid err %.3e" % (k, np.abs(r).max(), np.abs(a - r).max()))
+        assert np.abs(a - r).max() <= 1e-4 * np.abs(r).max() + 1e-9, k
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("N,In1,In2,Out", [(5120, 256, 256, 1024), (5120, 256, 0, 1024), (40, 128, 64, 256), (1000, 90, 256, 1024),
                                            (777, 256, 128, 512), (33, 256, 0, 64)])

@@ -48,7 +48,7 @@ pytestmark = pytest.mark.gpu
 LAYER_FORWARD = [("cluster", 64, {}), ("cluster", 128, {}), ("cluster", 256, {}), ("generic", 256, {}), ("auto", 512, {}),
                  ("auto", 512, {"FOV_NO_WIDE16": "1"})]
 LAYER_SHAPE = {"R1": [(37, 8)], "R2": [(37, 8)], "R3": [(37, 8)], "R4": [(16, 256), (21, 256)]}          # (B, T)
-# (name, H, knobs, dtype): which BPTT kernel ops.lstm_seq_bwd takes at three tiles (train_kernels.hip, lstm_seq_bwd)
+# (name, H, knobs, dtype): which BPTT kernel ops.lstm_seq_bwd takes at three tiles (lstm_train.hip, lstm_seq_bwd)
 BACKWARD_FORMS = [
     ("bwd_cluster-64", 64, {}, "f32"),
     ("bwd_cluster-128", 128, {"FOV_NO_BWD16_NARROW": "1"}, "f32"),
