@@ -401,6 +401,35 @@ int fov_seq2seq_decoder_fwd(const float* dec_in0, const float* h0, const float* 
                             float* out, float* hT, float* cT, int B, int T_out, int F_dec, int H, int act, int impl,
                             void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
+/* The 2- and 3-layer target-only seq2seq model's inference in ONE launch (replaces the sampling models and the host loop of
+ * mycode/Fov_seq2seq_2layers.py:360-430 and 3layers.py's loop, batched): the L-layer encoder over enc_in (B,T_in,F_enc) from
+ * zero states (layer l reads layer l-1's h_t), then T_out decoder steps - decoder layer l, seeded with encoder layer l's
+ * (h_T, c_T), takes one LSTM step from its own carried state (layer 0 on the fed-back input, layer l on layer l-1's new h),
+ * y_t = tanh(h_top . dense_W + dense_b) is stored to out (B,T_out,F_dec) and fed back; the first input is dec_in0 (B,1,F_dec).
+ * fp32 on the matrix core, exact expf / tanhf; pre-activations summed in the order bias, x . K, h . R.
+ * Weights per layer, Keras layout: enc0_K (F_enc,4H), dec0_K (F_dec,4H), every other K and every R (H,4H), b (4H); the third
+ * layer's six pointers are NULL (and ignored) for L = 2.  hT, cT (L,B,H) or NULL: every layer's final state of the last
+ * phase that ran.  B = 0: nothing is launched; T_in = 0: the decoder starts from zero states; T_out = 0: the encoder stack
+ * alone, `out` is not written.
+ * One workgroup owns a 16-sequence tile for all layers and steps, so the call takes NO workspace, keeps NO library state, waits
+ * on nothing, and writes every element of `out` exactly once (rows of a ragged last tile beyond B are neither read nor written).
+ * Shapes: H = 32 or 64 (a narrower model zero-padded by the caller, which is exact), L = 2 or 3, 1 <= F_enc <= 96,
+ * 1 <= F_dec <= 8, any B, T_in, T_out >= 0; anything else: FOV_ERR_UNSUPPORTED before any HIP call.
+ * fov_stacked_seq2seq_decode_supported is that rule as arithmetic (no device query), and 0 under FOV_NO_STACKED_DECODE=1
+ * (the caller's host loop stays: A/B timing, cross-check); the _fwd entry itself does not read the knob. */
+int fov_stacked_seq2seq_decode_supported(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);
+int fov_stacked_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0,
+                                   const float* enc0_K, const float* enc0_R, const float* enc0_b,
+                                   const float* enc1_K, const float* enc1_R, const float* enc1_b,
+                                   const float* enc2_K, const float* enc2_R, const float* enc2_b,
+                                   const float* dec0_K, const float* dec0_R, const float* dec0_b,
+                                   const float* dec1_K, const float* dec1_R, const float* dec1_b,
+                                   const float* dec2_K, const float* dec2_R, const float* dec2_b,
+                                   const float* dense_W, const float* dense_b,
+                                   float* out, float* hT, float* cT,
+                                   int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L,
+                                   int act, fov_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Teacher-forced training-graph forward: encoder, decoder seeded with the encoder state over
  * GT decoder inputs, Dense(tanh) on every decoder output.

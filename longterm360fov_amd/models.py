@@ -1009,6 +1009,7 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
         w["dense_W"] = glorot_uniform(rng, self.H, self.O)
         w["dense_b"] = np.zeros(self.O, np.float32)
         self._w = w
+        self._fw = None      # (device weights it was built from, the padded set of the one-launch decode, its width)
         self._init_surface(stacked_weight_order(self.L), impl, device)
 
     def _device(self):
@@ -1040,29 +1041,61 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
 
     predict_on_batch = predict
 
+    FUSED_WIDTHS = (32, 64)      # run widths of the one-launch decode (lstm_stacked_s2s.hip)
+
+    def _fused_weights(self, ops, dw):
+        """The weights at the one-launch decode's run width (zero-padded - exact, see pad_lstm), on the device; None when the
+        model is wider than that kernel.  Built once per set of device weights: set_weights and a training step drop
+        self._dw, and this cache is keyed by it."""
+        import torch
+        if self._fw is None or self._fw[0] is not dw:
+            Hp, w = padded_width(self.H, self.FUSED_WIDTHS), self._w
+            if Hp is None:
+                fw = None
+            elif Hp == self.H:
+                fw = dw
+            else:
+                pw = {"dense_W": pad_rows(w["dense_W"], Hp), "dense_b": w["dense_b"]}
+                for side in ("enc", "dec"):
+                    for l in range(self.L):
+                        name = "%s%d" % (side, l)
+                        pw[name + "_K"], pw[name + "_R"], pw[name + "_b"] = pad_lstm(w[name + "_K"], w[name + "_R"], w[name + "_b"], Hp,
+                                                                                     pad_input=(l > 0))
+                fw = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in pw.items()}
+            self._fw = (dw, fw, Hp)
+        return self._fw[1], self._fw[2]
+
+    def decode_device(self, e, xin, T_out, fused=True):
+        """decode_sequence on device tensors e (B,T_in,F), xin (B,1,O) -> (B,T_out,O) device tensor.  ONE launch
+        (ops.stacked_seq2seq_decode) when the padded width is at most 64 and the library supports the shape; the host loop - a
+        launch per layer and step - for wider models, other depths, impl != 'auto', under FOV_NO_STACKED_DECODE=1 or with
+        fused=False (the timing tool's A/B switch)."""
+        import torch
+        ops, dw = self._device()
+        fw, Hp = self._fused_weights(ops, dw) if (fused and self.impl == "auto") else (None, None)
+        B, T_in = e.shape[0], e.shape[1]
+        xin = xin.reshape(B, 1, self.O)
+        if fw is not None and ops.stacked_seq2seq_decode_supported(B, T_in, T_out, e.shape[2], self.O, Hp, self.L):
+            return ops.stacked_seq2seq_decode(e, xin, fw, self.L, T_out, act=self.recurrent_activation)
+        states = self._encode(ops, dw, e)
+        y = torch.empty((B, T_out, self.O), dtype=torch.float32, device=self.device)
+        for t in range(T_out):
+            inp = xin
+            for l in range(self.L):
+                inp, h, c = ops.lstm_seq(inp, dw["dec%d_K" % l], dw["dec%d_R" % l], dw["dec%d_b" % l], states[l][0], states[l][1],
+                                         act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
+                states[l] = (h, c)
+            xin = ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
+            y[:, t] = xin[:, 0]
+        return y
+
     def decode_sequence(self, input_seq, first_decoder_input, predict_step=None, batch_size=None):
         """Autoregressive loop of :399-430, any batch: encoder states, then `predict_step` steps through all decoder
-        layers, each Dense output fed back as the next input."""
-        import torch
+        layers, each Dense output fed back as the next input (decode_device per chunk of `batch_size` rows)."""
         enc, d0 = _as_f32(input_seq), _as_f32(first_decoder_input)
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
-        ops, dw = self._device()
-
-        def run(e, xin):
-            states = self._encode(ops, dw, e)
-            B = states[0][0].shape[0]
-            xin = xin.reshape(B, 1, self.O)
-            y = torch.empty((B, T_out, self.O), dtype=torch.float32, device=self.device)
-            for t in range(T_out):
-                inp = xin
-                for l in range(self.L):
-                    inp, h, c = ops.lstm_seq(inp, dw["dec%d_K" % l], dw["dec%d_R" % l], dw["dec%d_b" % l], states[l][0], states[l][1],
-                                             act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
-                    states[l] = (h, c)
-                xin = ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
-                y[:, t] = xin[:, 0]
-            return y
-        y = self._predict_chunks([enc, d0], batch_size, run, (T_out, self.O))
+        self._device()
+        y = self._predict_chunks([enc, d0], batch_size, lambda e, xin: self.decode_device(e, xin, T_out), (T_out, self.O))
         self._ws.check()
         return y
 

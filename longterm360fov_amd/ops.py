@@ -52,7 +52,7 @@ def _stream():
 
 _ENV_KNOBS = ("FOV_FORCE_SAFE_EXCHANGE", "FOV_TWO_LAUNCHES", "FOV_DBG_RESIDENT_LIMIT", "FOV_NO_CELL_PATCH", "FOV_NO_CONV_PATCH", "FOV_NO_WIDE16", "FOV_BWD_STEPPED",
               "FOV_NO_WGRAD_FUSION", "FOV_NO_DX_FUSION", "FOV_BWD_GROUPS4", "FOV_GEMM_BF16_NOREMAP", "FOV_GEMM_BF16_SPLIT", "FOV_GEMM_BF16_SHALLOW", "FOV_NO_WGRAD_GROUP", "FOV_NO_WIDE16_TRIO", "FOV_DBG_TRACE", "FOV_GEMM_VARIANT",
-              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES")
+              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES", "FOV_NO_STACKED_DECODE")
 _env_seen = None
 # os.environ.get costs 0.7 us per key (encode, lookup, decode): 9 us for the knob list, paid at every workspace / scratch
 # fetch - 0.15 ms of a 0.3 ms training step at batch 32.  The mapping underneath (bytes -> bytes on POSIX) answers the
@@ -243,6 +243,43 @@ def seq2seq_decoder(dec_in0, h0, c0, w, T_out, act="sigmoid", impl="auto", works
     buf = ws.get(L.fov_seq2seq_decode_workspace_bytes(B, 0, T_out, 1, F_dec, H, impl), h0.device)
     check(L.fov_seq2seq_decoder_fwd(_ptr(dec_in0), _ptr(h0), _ptr(c0), *[_ptr(t) for t in ws_t], _ptr(out), None, None,
                                     B, T_out, F_dec, H, act_code(act), impl, buf.data_ptr(), buf.numel(), _stream()))
+    return out
+
+
+def stacked_seq2seq_decode_supported(B, T_in, T_out, F_enc, F_dec, H, num_layers):
+    """Shapes fov_stacked_seq2seq_decode_fwd takes (H = 32 or 64 at the run width, 2 or 3 layers, F_enc <= 96, F_dec <= 8, any
+    batch and lengths); False under FOV_NO_STACKED_DECODE=1.  Arithmetic only: answers on a machine without a GPU."""
+    _sync_env()
+    return bool(_lib.lib().fov_stacked_seq2seq_decode_supported(B, T_in, T_out, F_enc, F_dec, H, num_layers))
+
+
+def stacked_seq2seq_decode(enc_in, dec_in0, w, num_layers, T_out, act="sigmoid", out=None, hT=None, cT=None):
+    """The L-layer encoder + autoregressive L-layer decoder + Dense head in one launch (Fov_seq2seq_2layers.py:360-430 /
+    3layers.py, batched) -> (B,T_out,F_dec).  w: enc{l}_K/R/b, dec{l}_K/R/b, dense_W/b at the run width; hT / cT (L,B,H): every
+    layer's final state, if wanted.  No workspace."""
+    enc_in, dec_in0 = _dev(enc_in, "enc_in"), _dev(dec_in0, "dec_in0")
+    L_ = int(num_layers)
+    names = ["%s%d_%s" % (side, l, k) for side in ("enc", "dec") for l in range(L_) for k in "KRb"]
+    t = {k: _dev(w[k], k) for k in names + ["dense_W", "dense_b"]}
+    B, T_in, F_enc = enc_in.shape
+    H = t["enc0_R"].shape[0]
+    F_dec = t["dense_W"].shape[1]
+    assert dec_in0.shape == (B, 1, F_dec)
+    for side, f0 in (("enc", F_enc), ("dec", F_dec)):
+        for l in range(L_):
+            assert t["%s%d_K" % (side, l)].shape == (f0 if l == 0 else H, 4 * H) and t["%s%d_R" % (side, l)].shape == (H, 4 * H) \
+                and t["%s%d_b" % (side, l)].shape == (4 * H,), "%s%d" % (side, l)
+    assert t["dense_W"].shape == (H, F_dec) and t["dense_b"].shape == (F_dec,)
+    if out is None:
+        out = torch.empty((B, T_out, F_dec), dtype=torch.float32, device=enc_in.device)
+    else:
+        assert _dev(out, "out").shape == (B, T_out, F_dec)
+    for s_, name in ((hT, "hT"), (cT, "cT")):
+        assert s_ is None or _dev(s_, name).shape == (L_, B, H), name
+    layer_ptrs = [_ptr(t["%s%d_%s" % (side, l, k)]) if l < L_ else None for side in ("enc", "dec") for l in range(3) for k in "KRb"]
+    check(_lib.lib().fov_stacked_seq2seq_decode_fwd(_ptr(enc_in), _ptr(dec_in0), *layer_ptrs, _ptr(t["dense_W"]), _ptr(t["dense_b"]),
+                                                    _ptr(out), _ptr(hT), _ptr(cT), B, T_in, int(T_out), F_enc, F_dec, H, L_,
+                                                    act_code(act), _stream()))
     return out
 
 
