@@ -430,6 +430,42 @@ int fov_stacked_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0,
                                    int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L,
                                    int act, fov_stream_t stream);
 
+/* The self-fed one-layer decoder (mycode/FoV_seq2seq_no_teac_forc.py:37-149, `onelayer_tar_seq2seq`; the unrolled loop is
+ * :96-118, its gradient is Keras autodiff under model.fit, :147-149) as ONE launch per direction, fp32 on the matrix core,
+ * exact expf / tanhf.  One workgroup owns a 16-sequence tile for every step: no workspace, no library state, nothing to wait
+ * on; rows of a ragged last tile beyond B read zeros and store nothing.
+ *
+ * fov_selffed_decoder_fwd - replaces the T iterations of :96-118.  From x0 (B,O) and the state (h0, c0) (B,H; both NULL = the
+ * zero state of :98-99), for t < T:  z = b + x_t . K + h . R  (this order);  the Keras cell update;  a_t = dact(h_t . W + bd);
+ * y_t = a_t + r  (r (B,O): the residual link's term of :103-107, or NULL);  x_{t+1} = y_t, kept on the chip.
+ * K (O,4H), R (H,4H), b (4H), W (H,O), bd (O), Keras gate order.  act: FOV_ACT_*; dact: 1 tanh, 2 relu (the codes of fov_act_fwd).
+ * Outputs, each of which may be NULL and is then not written - the tapes of the training step, time-major:
+ *   Hs, Cs (T+1,B,H)  row t = state before step t (row 0 = the initial state)
+ *   XA (T+1,B,O)      row 0 = x0, row t+1 = y_t          A (T,B,O)  a_t (of interest with a residual only)
+ *   RES (T,B,1,5,H)   activated i, f, g, o and c of step t (the reserve layout of fov_lstm_seq_fwd_train at T = 1)
+ *   y (B,T,O)         the prediction, batch-major
+ *
+ * fov_selffed_decoder_bwd - replaces Keras autodiff through that loop.  dloss (T,B,O) = dL/dy_t.  For t = T-1 .. 0:
+ *   dy_t = dloss_t + dx_{t+1};  dpre_t = dy_t dact'(a_t);  dh = dpre_t . W^T + dz_{t+1} . R^T;  the cell's pointwise backward
+ *   with the gate derivative taken from the stored gate and c_{t-1} = Cs[t];  dx_t = dz_t . K^T  (dx_{T} = dz_{T} = 0).
+ * a_t is read from A when a_from_A != 0, else from XA[1:].  Outputs: DY, DPRE (T,B,O), DZ (T,B,4H), dx0 (B,O), and dh0, dc0
+ * (B,H; either may be NULL).  The weight gradients are products over all steps of these tapes (fov_dense_bwd).
+ *
+ * Shapes: H = 32 or 64, 1 <= O <= 8, B >= 0, T >= 0; anything else is FOV_ERR_UNSUPPORTED, decided before any HIP call.  A
+ * missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 or T = 0 launches nothing: the forward then
+ * writes nothing (no tape row 0 either); the backward, which takes no gradient of the final state, sets dx0, dh0 and dc0 to
+ * zero with T = 0.  fov_selffed_decoder_supported is the shape rule as arithmetic (no device query), and 0 under
+ * FOV_NO_SELFFED_FUSED=1 (the caller's host loop stays: A/B timing, cross-check); the two entries do not read the knob. */
+int fov_selffed_decoder_supported(int B, int T, int O, int H);
+int fov_selffed_decoder_fwd(const float* x0, const float* h0, const float* c0,
+                            const float* K, const float* R, const float* b, const float* W, const float* bd, const float* r,
+                            float* Hs, float* Cs, float* XA, float* A, float* RES, float* y,
+                            int B, int T, int O, int H, int act, int dact, fov_stream_t stream);
+int fov_selffed_decoder_bwd(const float* Cs, const float* XA, const float* A, const float* RES, const float* dloss,
+                            const float* K, const float* R, const float* W,
+                            float* DY, float* DPRE, float* DZ, float* dx0, float* dh0, float* dc0,
+                            int B, int T, int O, int H, int act, int dact, int a_from_A, fov_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Teacher-forced training-graph forward: encoder, decoder seeded with the encoder state over
  * GT decoder inputs, Dense(tanh) on every decoder output.

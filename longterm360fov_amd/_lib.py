@@ -55,6 +55,9 @@ SIGNATURES = {
     "fov_seq2seq_decoder_fwd": (_I, [_P] * 11 + [_I] * 6 + [_P, _SZ, _P]),
     "fov_stacked_seq2seq_decode_supported": (_I, [_I] * 7),
     "fov_stacked_seq2seq_decode_fwd": (_I, [_P] * 25 + [_I] * 8 + [_P]),
+    "fov_selffed_decoder_supported": (_I, [_I] * 4),
+    "fov_selffed_decoder_fwd": (_I, [_P] * 15 + [_I] * 6 + [_P]),
+    "fov_selffed_decoder_bwd": (_I, [_P] * 14 + [_I] * 7 + [_P]),
     "fov_seq2seq_tf_workspace_bytes": (_SZ, [_I] * 7),
     "fov_seq2seq_tf_fwd": (_I, [_P] * 11 + [_I] * 8 + [_P, _SZ, _P]),
     "fov_meanvar_xyz": (_I, [_P, _P, ctypes.c_int64, _I, _P]),

@@ -73,6 +73,7 @@ int launch_cluster(const LstmParams& p, bool decode, hipStream_t stream);
 int launch_cluster_decoder(const LstmParams& p, hipStream_t stream);   // MODE_DECODE alone, from (p.h0, p.c0)
 bool cluster_shape_ok(int F, int H);
 bool stacked_s2s_shape_ok(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);   // lstm_stacked_s2s.hip: the L-layer seq2seq decode as one launch
+bool selffed_shape_ok(int B, int T, int O, int H);   // lstm_selffed.hip: the self-fed one-layer decoder's unroll (forward with tapes, BPTT) as one launch each
 size_t cluster_workspace_bytes(int B, int H);
 int cluster_num_groups(int B, int H);
 int device_cu_count();                               // CUs of the current device a persistent grid may count on (FOV_DBG_RESIDENT_LIMIT caps it: tests)
@@ -91,6 +92,7 @@ struct EnvKnobs {
     int no_stack2;       // FOV_NO_STACK2=1: two stacked width-512 layers as two launches (fov_lstm_stack2_supported -> 0)
     int no_wgrad_bf16_tiles;   // FOV_NO_WGRAD_BF16_TILES=1: the bf16 Conv2D weight gradient on its plain kernel (tests; conv_wgrad_bf16.hip)
     int no_stacked_decode;     // FOV_NO_STACKED_DECODE=1: fov_stacked_seq2seq_decode_supported -> 0, the stacked model's decode stays a host loop (tests / A-B timing)
+    int no_selffed_fused;      // FOV_NO_SELFFED_FUSED=1: fov_selffed_decoder_supported -> 0, the self-fed decoder's unroll stays a host loop (tests / A-B timing)
 };
 const EnvKnobs& env_knobs();
 void env_reload();

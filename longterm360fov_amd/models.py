@@ -882,6 +882,7 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
         self._order = self_fed_weight_order(self.add_residual_link, self.embed_frame_state_enc2dec, self.has_reconstruct_loss)
 
     _dataset_pick_user = None      # (the dataset methods are the teacher-forced graph's: not built for this model)
+    fused_unroll = True            # A/B switch: the non-plain variants' unrolled decoder as one launch where the shape allows it
 
     def _pad_extra(self, k, w, Hp):
         """The optional layers that carry the hidden width (FoV_seq2seq_no_teac_forc.py:47-59): the state embeddings
@@ -921,6 +922,12 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
             return y if dact == "tanh" else ops.act_fwd(y, "relu", out=y)
 
         def unroll(pre, head, xin, h, c, r, dact, width):
+            H_ = dw[pre + "_R"].shape[0]
+            if self.fused_unroll and self.impl == "auto" and ops.selffed_decoder_supported(xin.shape[0], T_out, width, H_):
+                # ONE launch, no tapes (lstm_selffed.hip); the reconstruction decoder's feedback (F wide) stays on the loop
+                return ops.selffed_decoder_fwd(xin, dw[pre + "_K"], dw[pre + "_R"], dw[pre + "_b"], dw[head + "_W"], dw[head + "_b"],
+                                               T_out, h0=h, c0=c, r=r, act=act, dense_activation=dact or self.dense_activation,
+                                               tape=False)[0]
             o = torch.empty((xin.shape[0], T_out, width), dtype=torch.float32, device=self.device)
             for t in range(T_out):
                 _, h, c = ops.lstm_seq(xin.reshape(-1, 1, width), dw[pre + "_K"], dw[pre + "_R"], dw[pre + "_b"], h, c, act=act,

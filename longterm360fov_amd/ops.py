@@ -52,7 +52,8 @@ def _stream():
 
 _ENV_KNOBS = ("FOV_FORCE_SAFE_EXCHANGE", "FOV_TWO_LAUNCHES", "FOV_DBG_RESIDENT_LIMIT", "FOV_NO_CELL_PATCH", "FOV_NO_CONV_PATCH", "FOV_NO_WIDE16", "FOV_BWD_STEPPED",
               "FOV_NO_WGRAD_FUSION", "FOV_NO_DX_FUSION", "FOV_BWD_GROUPS4", "FOV_GEMM_BF16_NOREMAP", "FOV_GEMM_BF16_SPLIT", "FOV_GEMM_BF16_SHALLOW", "FOV_NO_WGRAD_GROUP", "FOV_NO_WIDE16_TRIO", "FOV_DBG_TRACE", "FOV_GEMM_VARIANT",
-              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES", "FOV_NO_STACKED_DECODE")
+              "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES", "FOV_NO_STACKED_DECODE",
+              "FOV_NO_SELFFED_FUSED")
 _env_seen = None
 # os.environ.get costs 0.7 us per key (encode, lookup, decode): 9 us for the knob list, paid at every workspace / scratch
 # fetch - 0.15 ms of a 0.3 ms training step at batch 32.  The mapping underneath (bytes -> bytes on POSIX) answers the
@@ -281,6 +282,61 @@ def stacked_seq2seq_decode(enc_in, dec_in0, w, num_layers, T_out, act="sigmoid",
                                                     _ptr(out), _ptr(hT), _ptr(cT), B, T_in, int(T_out), F_enc, F_dec, H, L_,
                                                     act_code(act), _stream()))
     return out
+
+
+def selffed_decoder_supported(B, T, O, H):
+    """Shapes fov_selffed_decoder_fwd / _bwd take (H = 32 or 64, 1 <= O <= 8, any batch and length); False under
+    FOV_NO_SELFFED_FUSED=1.  Arithmetic only: answers on a machine without a GPU."""
+    _sync_env()
+    return bool(_lib.lib().fov_selffed_decoder_supported(B, T, O, H))
+
+
+def selffed_decoder_fwd(x0, K, R, b, W, bd, T, h0=None, c0=None, r=None, act="sigmoid", dense_activation="tanh", tape=True,
+                        out=None):
+    """The self-fed one-layer decoder (FoV_seq2seq_no_teac_forc.py:96-118) unrolled T times in one launch: x0 (B,O), the state
+    (h0, c0) (B,H) or None for zeros, y_t = dact(h_t . W + bd) + r fed back as x_{t+1}.  -> (y (B,T,O), tapes), tapes = None
+    without `tape`, else the trainer's time-major dict Hs, Cs (T+1,B,H), XA (T+1,B,O), A (T,B,O) (with r only), RES
+    (T,B,1,5,H).  No workspace."""
+    x0 = _dev(x0, "x0")
+    B, O = x0.shape
+    H = R.shape[0]
+    T = int(T)
+    assert K.shape == (O, 4 * H) and R.shape == (H, 4 * H) and b.shape == (4 * H,) and W.shape == (H, O) and bd.shape == (O,)
+    assert (h0 is None) == (c0 is None) and (h0 is None or (h0.shape == (B, H) and c0.shape == (B, H)))
+    assert r is None or r.shape == (B, O)
+    e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=x0.device)
+    y = e(B, T, O) if out is None else out
+    assert _dev(y, "out").shape == (B, T, O)
+    tp = None
+    if tape:
+        tp = {"Hs": e(T + 1, B, H), "Cs": e(T + 1, B, H), "XA": e(T + 1, B, O), "A": e(T, B, O) if r is not None else None,
+              "RES": e(T, B, 1, 5, H)}
+    g = (lambda k: None) if tp is None else (lambda k: _ptr(tp[k]))
+    check(_lib.lib().fov_selffed_decoder_fwd(_ptr(x0), _ptr(_dev(h0, "h0")), _ptr(_dev(c0, "c0")), _ptr(_dev(K, "K")), _ptr(_dev(R, "R")),
+                                             _ptr(_dev(b, "b")), _ptr(_dev(W, "W")), _ptr(_dev(bd, "bd")), _ptr(_dev(r, "r")),
+                                             g("Hs"), g("Cs"), g("XA"), g("A"), g("RES"), _ptr(y), B, T, O, H, act_code(act),
+                                             _ACT_CODES[dense_activation], _stream()))
+    return y, tp
+
+
+def selffed_decoder_bwd(tp, dloss, K, R, W, act="sigmoid", dense_activation="tanh", need_state_grads=True):
+    """BPTT of selffed_decoder_fwd through the feedback in one launch.  tp: the tapes (Cs, RES, XA, and A when the forward had
+    a residual term); dloss (T,B,O) = dL/dy_t, time-major.  -> dict DY, DPRE (T,B,O), DZ (T,B,4H), dx0 (B,O), dh0, dc0 (B,H)
+    (None without need_state_grads).  The weight gradients are dense_bwd products over these tapes."""
+    dloss = _dev(dloss, "dloss")
+    T, B, O = dloss.shape
+    H = R.shape[0]
+    Cs, XA, A, RES = tp["Cs"], tp["XA"], tp.get("A"), tp["RES"]
+    assert K.shape == (O, 4 * H) and R.shape == (H, 4 * H) and W.shape == (H, O)
+    assert Cs.shape == (T + 1, B, H) and XA.shape == (T + 1, B, O) and RES.numel() == T * B * 5 * H and (A is None or A.shape == (T, B, O))
+    e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=dloss.device)
+    o = {"DY": e(T, B, O), "DPRE": e(T, B, O), "DZ": e(T, B, 4 * H), "dx0": e(B, O),
+         "dh0": e(B, H) if need_state_grads else None, "dc0": e(B, H) if need_state_grads else None}
+    check(_lib.lib().fov_selffed_decoder_bwd(_ptr(_dev(Cs, "Cs")), _ptr(_dev(XA, "XA")), _ptr(_dev(A, "A")), _ptr(_dev(RES, "RES")),
+                                             _ptr(dloss), _ptr(_dev(K, "K")), _ptr(_dev(R, "R")), _ptr(_dev(W, "W")), _ptr(o["DY"]),
+                                             _ptr(o["DPRE"]), _ptr(o["DZ"]), _ptr(o["dx0"]), _ptr(o["dh0"]), _ptr(o["dc0"]), B, T, O, H,
+                                             act_code(act), _ACT_CODES[dense_activation], 0 if A is None else 1, _stream()))
+    return o
 
 
 def seq2seq_teacher_forced(enc_in, dec_in, w, act="sigmoid", impl="auto", workspace=None, dtype="f32"):

@@ -501,7 +501,9 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
     (mycode/FoV_seq2seq_no_teac_forc.py:37-149, `onelayer_tar_seq2seq`; Adam + MSE, :147): the decoder is unrolled
     T_out times on its own output.  Same layer kernels as the teacher-forced trainer, walked step by step: forward
     writes a time-major tape, backward joins the loss gradient of step t with the input gradient of step t+1, and
-    every weight gradient is one product over all steps.
+    every weight gradient is one product over all steps.  Up to width 64 and feedback width 8 (the prediction decoder; the
+    reconstruction decoder feeds back F values) the walk is ONE launch per direction on the same tapes (lstm_selffed.hip;
+    `fused_unroll`, `fused_unroll_bwd`), the weight-gradient products unchanged.
 
     decoder_no_init_state       the script's module flag (:29,98-99): step 0 starts from zero state (the encoder then
                                 only matters through enc_last_out_as_dec_in / the reconstruction decoder)
@@ -540,10 +542,21 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
         return y
 
     # ---- one self-fed unrolled decoder: LSTM `lstm`_K/R/b + Dense `head`_W/b, y_t fed back as x_{t+1} ----
+    fused_unroll = True          # A/B switches: the unroll's forward / BPTT as one launch each (lstm_selffed.hip) where the shape
+    fused_unroll_bwd = True      # allows it; False keeps the step-by-step loop
+
+    def _fused_unroll_ok(self, B, T, O, H):
+        return self.impl == "auto" and ops.selffed_decoder_supported(B, T, O, H)
+
     def _unroll_forward(self, lstm, head, x0, h0, c0, T, dact, r=None):
         w, act, impl, ws = self.w, self.act, self.impl, self.ws
         B, O = x0.shape
         H = w[lstm + "_R"].shape[0]
+        if self.fused_unroll and self._fused_unroll_ok(B, T, O, H):
+            y, tp = ops.selffed_decoder_fwd(x0, w[lstm + "_K"], w[lstm + "_R"], w[lstm + "_b"], w[head + "_W"], w[head + "_b"], T,
+                                            h0=h0, c0=c0, r=r, act=act, dense_activation=dact)
+            tp.update({"lstm": lstm, "head": head, "dact": dact, "r": r, "T": T, "y": y})
+            return tp
         e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=self.device)
         tp = {"Hs": e(T + 1, B, H), "Cs": e(T + 1, B, H),    # row t = state before step t
               "XA": e(T + 1, B, O),                           # row t = input x_t; row t+1 = y_t
@@ -573,6 +586,11 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
         _, B, O = XA.shape
         H = Hs.shape[2]
         e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=self.device)
+        if self.fused_unroll_bwd and self._fused_unroll_ok(B, T, O, H):
+            b = ops.selffed_decoder_bwd(tp, dloss_tm, w[lstm + "_K"], w[lstm + "_R"], w[head + "_W"], act=act, dense_activation=dact)
+            DY, DPRE, DZ = b["DY"], b["DPRE"], b["DZ"]
+            self._unroll_wgrads(tp, DPRE, DZ)
+            return b["dx0"], b["dh0"], b["dc0"], DY
         Aout = tp["A"] if tp["r"] is not None else XA[1:]
         DY, DPRE, DZ = e(T, B, O), e(T, B, O), e(T, B, 4 * H)
         dh_rec = dc = dx_next = None
@@ -587,12 +605,21 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
                                  c0=Cs[t], dhs=dh_dense.reshape(B, 1, H), dhT=dh_rec, dcT=dc, need_dx=True, need_state_grads=True,
                                  act=act, dz=DZ[t].view(B, 1, 4 * H), scratch=bsc, need_weight_grads=False)
             dh_rec, dc, dx_next = b["dh0"], b["dc0"], b["dx"]
+        self._unroll_wgrads(tp, DPRE, DZ)
+        return dx_next.reshape(B, O), dh_rec, dc, DY
+
+    def _unroll_wgrads(self, tp, DPRE, DZ):
+        """The unrolled LSTM's and its head's weight gradients: one product over all steps each."""
+        w, g, sc = self.w, self.g, self.scratch
+        lstm, head, T = tp["lstm"], tp["head"], tp["T"]
+        Hs, XA = tp["Hs"], tp["XA"]
+        _, B, O = XA.shape
+        H = Hs.shape[2]
         TB = T * B
         fl = lambda a, n: a.reshape(TB, n)
         ops.dense_bwd(fl(Hs[1:], H), w[head + "_W"], fl(DPRE, O), dW=g[head + "_W"], db=g[head + "_b"], need_dx=False, accumulate=True, scratch=sc)
         ops.dense_bwd(fl(XA[:T], O), w[lstm + "_K"], fl(DZ, 4 * H), dW=g[lstm + "_K"], db=g[lstm + "_b"], need_dx=False, accumulate=True, scratch=sc)
         ops.dense_bwd(fl(Hs[:T], H), w[lstm + "_R"], fl(DZ, 4 * H), dW=g[lstm + "_R"], need_db=False, need_dx=False, accumulate=True, scratch=sc)
-        return dx_next.reshape(B, O), dh_rec, dc, DY
 
     @staticmethod
     def _sum(a, b):
@@ -617,12 +644,12 @@ class SelfFedSeq2SeqTrainer(FlatParamTrainer):
         x0 = self._dense(ehT, w["dense_W"], w["dense_b"]) if self.enc_as_in else dec_in.reshape(B, O)
         r = self._dense(x0, w["res_W"], w["res_b"]) if self.residual else None
         main = self._unroll_forward("dec", "dense", x0, None if self.no_init else sh, None if self.no_init else sc_, T_out, self.dact, r)
-        out = main["XA"][1:].transpose(0, 1).contiguous()
+        out = main["y"] if "y" in main else main["XA"][1:].transpose(0, 1).contiguous()
         rec = None
         if self.recons:
             xr0 = self._dense(ehT, w["recd_W"], w["recd_b"], dact="tanh")
             rec = self._unroll_forward("rec", "recd", xr0, sh, sc_, T_out, "tanh")
-            rec_out = rec["XA"][1:].transpose(0, 1).contiguous()
+            rec_out = rec["y"] if "y" in rec else rec["XA"][1:].transpose(0, 1).contiguous()
             tgt_main, tgt_rec = target[..., :O].contiguous(), target[..., O:].contiguous()
         else:
             tgt_main = target
