@@ -944,30 +944,40 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                 *(f32x2*)(sY + (t & 1) * YPAR_LDS + wave * 128 + lane * 2) = (f32x2){dacc[0][0] + dacc[1][0], dacc[0][1] + dacc[1][1]};
             }
             if (do_xch) {
-                // complete the gather: sweep again until every tag equals the epoch
+                // complete the gather: sweep again until every tag equals the epoch.  The check of the FIRST sweep stands in
+                // front of the spin loop, not at its head (same sequence of checks and sweeps): at the head the six granule
+                // registers were loop-carried values, and hipcc moved them between register sets on the way in and out -
+                // 68 VALU instructions in every encoder step, 11 in every decoder step (tools/isa_step_counts.py), none of
+                // them hidden behind an fp32 MFMA - for a loop that takes no turn in a healthy run.  The scheduling barrier
+                // keeps the tag compares, and the wait for the loads that they carry, behind the MFMA run in front.
                 unsigned spins = 0;
-#ifdef FOV_DBG_NOGATHER   // timing experiment only (wrong results): take whatever the first sweep returned
-                while (false) {
-#else
-                while (true) {
-#endif
+                __builtin_amdgcn_sched_barrier(0);
+#ifndef FOV_DBG_NOGATHER   // (defined: timing experiment only, wrong results - take whatever the first sweep returned)
+                auto tags_ok = [&]() __attribute__((always_inline)) -> bool {
                     bool ok = true;
 #pragma unroll
                     for (int j = 0; j < NG; ++j) ok = ok && (v[j].y == epoch) && (v[j].w == epoch);
-                    if (__all(ok)) break;
-                    ++spins;
-                    if (spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
-                        if (lane == 0) {
-                            xch_give_up(p.status);
-                            sFlag[0] = 1;
+                    return __all(ok);
+                };
+                if (!tags_ok()) {
+                    while (true) {
+                        ++spins;
+                        if (spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                            if (lane == 0) {
+                                xch_give_up(p.status);
+                                sFlag[0] = 1;
+                            }
+                            break;
                         }
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                    asm volatile("" ::: "memory");   // the sweep below must really re-read memory
+                        __builtin_amdgcn_s_sleep(1);
+                        asm volatile("" ::: "memory");   // the sweep below must really re-read memory
 #pragma unroll
-                    for (int j = 0; j < NG; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(xrs, goff[j], xsoff, 16);
+                        for (int j = 0; j < NG; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(xrs, goff[j], xsoff, 16);
+                        asm volatile("");   // (a statement of its own behind the unrolled loop, see the Dense partials' spin loop)
+                        if (tags_ok()) break;
+                    }
                 }
+#endif
 #ifdef FOV_STAMPS
                 if (stamp_on && t < STAMP_STEPS) g_stamps[MODE & 1][t][10] = spins;
 #endif
