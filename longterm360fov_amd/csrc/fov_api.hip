@@ -30,15 +30,13 @@ bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long 
 }
 
 int launch_check(const char* what) {
+    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] launched: %s\n", what);   // FOV_DBG_TRACE=1 (with HIP_LAUNCH_BLOCKING=1: the last line names the launch BEFORE a faulting one)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
     return FOV_OK;
 }
 
-int check_launch(const char* what) {
-    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] launched: %s\n", what);   // FOV_DBG_TRACE=1 (with HIP_LAUNCH_BLOCKING=1: the last line names the launch BEFORE a faulting one)
-    return launch_check(what);
-}
+int check_launch(const char* what) { return launch_check(what); }
 
 // ---------------------------------------------------------------------------------------
 // Dense: y = act(x W + b).  One wave per output row; lanes stride over In, shuffle-reduce.
@@ -215,22 +213,23 @@ static int launch_dense(const float* x, const float* W, const float* b, const fl
         const size_t lds = sizeof(float) * ((size_t)DW_ROWS * In + DW_KQ * DW_ROWS * DW_OT);
         hipLaunchKernelGGL(dense_fewrows_kernel, dim3((unsigned)((N + DW_ROWS - 1) / DW_ROWS)), dim3(256), lds, stream, x, W, b, add,
                            add_stride, y, N, In, Out, activation);
-        return launch_check("dense");
+        return launch_check("dense (few rows)");
     }
+    // (each kernel form under its own name in the FOV_DBG_TRACE line: a test asserts the one it reached)
     if (Out <= 8 && In <= 2048 && N >= 64) {
         long blocks = ((long)N + 15) / 16;
         if (blocks > 2048) blocks = 2048;
-        if ((In & 3) == 0 && (((uintptr_t)x) & 15) == 0)
+        const bool xvec = (In & 3) == 0 && (((uintptr_t)x) & 15) == 0;
+        if (xvec)
             hipLaunchKernelGGL(dense_small_kernel<4>, dim3((unsigned)blocks), dim3(256), sizeof(float) * 8 * In, stream, x, W, b, add,
                                add_stride, y, N, In, Out, activation);
         else
             hipLaunchKernelGGL(dense_small_kernel<1>, dim3((unsigned)blocks), dim3(256), sizeof(float) * 8 * In, stream, x, W, b, add,
                                add_stride, y, N, In, Out, activation);
-    } else {
-        hipLaunchKernelGGL(dense_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, x, W, b, add, add_stride, y, N, In, Out,
-                           activation);
+        return launch_check(xvec ? "dense (16 rows, vector x)" : "dense (16 rows, scalar x)");
     }
-    return launch_check("dense");
+    hipLaunchKernelGGL(dense_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, x, W, b, add, add_stride, y, N, In, Out, activation);
+    return launch_check("dense (wave per row)");
 }
 
 // ---------------------------------------------------------------------------------------

@@ -109,8 +109,10 @@ void set_error(const char* fmt, ...);
 // weight_bytes of weights and, for the bf16 forms, `tiles` 16-row tiles.  false with the error "<what>: operand larger than
 // 2 GiB" when one of them does not fit.
 bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long ldb2, long weight_bytes, long tiles = 0);
-int launch_check(const char* what);   // after a launch: FOV_OK, or FOV_ERR_LAUNCH with the error "<what> launch: <hip string>"
-int check_launch(const char* what);   // launch_check behind the "[fov trace] launched: <what>" line of FOV_DBG_TRACE=1 (the training step's launches)
+// after a launch: FOV_OK, or FOV_ERR_LAUNCH with the error "<what> launch: <hip string>"; under FOV_DBG_TRACE=1 the line
+// "[fov trace] launched: <what>" first - every launch names its kernel form, so a test can assert the form a launcher chose
+int launch_check(const char* what);
+int check_launch(const char* what);   // the same (the training helpers' older name)
 // wide-input layer, H = 256, 96 < F <= 256 (lstm_wide.hip)
 bool wide_shape_ok(int F, int H);
 bool wide_narrow_preferred(int B, int F, int H);

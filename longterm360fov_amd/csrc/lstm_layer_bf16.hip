@@ -312,7 +312,7 @@ int launch_layer_bf16(const LstmParams& p_in, hipStream_t stream) {
         : xvec ? (hs_ ? lstm_layer_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, true> : lstm_layer_bf16_kernel<FOV_ACT_SIGMOID, 8, true>)
                : (hs_ ? lstm_layer_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, false> : lstm_layer_bf16_kernel<FOV_ACT_SIGMOID, 8, false>);
     hipLaunchKernelGGL(kern, dim3(q_padded_groups(p.num_groups) * QG), dim3(256), 0, stream, p);
-    return launch_check("bf16 LSTM layer");
+    return launch_check(narrow ? "bf16 LSTM layer (narrow x)" : xvec ? "bf16 LSTM layer (vector x)" : "bf16 LSTM layer (scalar x)");
 }
 
 }  // namespace fov

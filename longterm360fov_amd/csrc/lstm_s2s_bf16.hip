@@ -352,7 +352,7 @@ int launch_s2s_bf16(const LstmParams& p_in, hipStream_t stream) {
         : xvec ? (hs_ ? s2s_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, true> : s2s_bf16_kernel<FOV_ACT_SIGMOID, 8, true>)
                : (hs_ ? s2s_bf16_kernel<FOV_ACT_HARD_SIGMOID, 8, false> : s2s_bf16_kernel<FOV_ACT_SIGMOID, 8, false>);
     hipLaunchKernelGGL(kern, dim3(q_padded_groups(p.num_groups) * QG), dim3(256), 0, stream, p);
-    return launch_check("bf16 seq2seq decode");
+    return launch_check(narrow ? "bf16 seq2seq decode (narrow x)" : xvec ? "bf16 seq2seq decode (vector x)" : "bf16 seq2seq decode (scalar x)");
 }
 
 bool dense_bf16_shape_ok(int In, int Out) { return In >= 1 && In <= QH && Out >= 1 && Out <= 16; }

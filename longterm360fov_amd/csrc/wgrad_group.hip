@@ -539,7 +539,11 @@ int wgrad_group_layers(int L, const float* const* x, const int* F, const float* 
     }
     if (blocks == 0) return FOV_OK;
     if (int rc = touch_outputs(g, stream)) return rc;
-    if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] wgrad_group: %d problems, %d workgroups\n", g.count, blocks);
+    if (env_knobs().dbg_trace) {     // vector_stores: how many problems' result tiles take the kernel's 16-byte stores (its own branch on c)
+        int vec = 0;
+        for (int i = 0; i < g.count; ++i) vec += ((g.p[i].ldc & 3) == 0 && (((uintptr_t)g.p[i].c) & 15) == 0) ? 1 : 0;
+        fprintf(stderr, "[fov trace] wgrad_group: %d problems, %d workgroups, vector_stores %d\n", g.count, blocks, vec);
+    }
     hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g);
     return launch_check("wgrad_group");
 }
