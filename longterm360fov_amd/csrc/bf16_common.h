@@ -20,7 +20,6 @@ constexpr int QG = 8;       // workgroups per tile
 constexpr int QBT = 16;     // sequences per tile
 constexpr int QLD = 272;    // bf16 elements per LDS row of an activation tile: 544 B, conflict-free ds_read_b128 of A fragments
 constexpr int QNG = 4;      // 16-byte loads (two adjacent units' tagged granules) per thread and exchange: 7 slices * 8 row pairs * 16 unit pairs / 256, rounded up
-constexpr unsigned Q_SPIN = 1u << 20;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -294,7 +293,7 @@ __device__ __forceinline__ bool q_gather_finish(QGather& g, const __amdgpu_buffe
     bool ok = true;
     while (__any(bad != 0)) {
         ++spins;
-        if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(status))) {
+        if (xch_wait_expired(spins, status)) {
             if ((tid & 63) == 0) xch_give_up(status);
             ok = false;
             break;
@@ -324,93 +323,15 @@ __device__ __forceinline__ bool q_gather_finish(QGather& g, const __amdgpu_buffe
 // granules per step (K-split with partial sums: 16 to 48) and every workgroup then forms ITS 32 output units of
 // dz . R^T from the whole tile (N-split) - no reduction across workgroups, the 8-byte write-through stores (the
 // expensive side of the exchange) shrink 4 to 12 times.
-// Granules of one tile and parity: [row pair 8][unit 256][gate 4] (round 3): the four gate granules of a lane's cells are 32
-// adjacent bytes - two 16-byte stores to publish, two 16-byte loads per (row pair, unit, slice) to gather, each 8-byte
-// granule with its own tag.
+// The four gate granules of a lane's cells are 32 adjacent bytes - two 16-byte stores to publish, two 16-byte loads per
+// (row, unit pair, slice) to gather, each 8-byte granule with its own tag.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int QLDZ = 1024 + 16;                   // bf16 per LDS row of a dz tile: 520 dwords = 8 (mod 64): conflict-free b128 reads
 constexpr unsigned Q_DZ_BYTES = 4u * 8u * QH * 8u;   // 64 KB
 constexpr int QNDZ = 14;                          // 16-byte loads per thread: 7 slices * 2 gate pairs
 
-// this lane's cells: rows row0, row0 + 1 of `unit`; dzp[g] = packed bf16 pair of gate g
-__device__ __forceinline__ void q_dz_publish(const __amdgpu_buffer_rsrc_t rs, unsigned base, int row0, int unit, const unsigned (&dzp)[4],
-                                             unsigned epoch, unsigned short* tile, bool same_xcd) {
-    const unsigned off = (unsigned)(((row0 >> 1) * QH + unit) * 4) * 8u;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const qu32x4 gr = {dzp[2 * h], epoch, dzp[2 * h + 1], epoch};
-        if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(gr, rs, off + h * 16, base, 1);
-        else __builtin_amdgcn_raw_buffer_store_b128(gr, rs, off + h * 16, base, 16);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        tile[row0 * QLDZ + g * QH + unit] = (unsigned short)(dzp[g] & 0xffffu);
-        tile[(row0 + 1) * QLDZ + g * QH + unit] = (unsigned short)(dzp[g] >> 16);
-    }
-}
-__device__ __forceinline__ bool q_dz_gather(const __amdgpu_buffer_rsrc_t rs, unsigned base, int slice, int tid, unsigned epoch,
-                                            unsigned short* tile, unsigned* status) {
-    const int p = tid >> 5, u = tid & 31;
-    const unsigned voff = (unsigned)((p * QH + u) * 4) * 8u;
-    const int lbase = 2 * p * QLDZ + u;
-    auto put = [&](int j, int h, const qu32x4& q) {   // gates 2h, 2h + 1 of (row pair p, unit u of slice slice + 1 + j)
-        const int lo = lbase + ((slice + 1 + j) & (QG - 1)) * 32 + 2 * h * QH;
-        tile[lo] = (unsigned short)(q.x & 0xffffu);
-        tile[lo + QLDZ] = (unsigned short)(q.x >> 16);
-        tile[lo + QH] = (unsigned short)(q.z & 0xffffu);
-        tile[lo + QH + QLDZ] = (unsigned short)(q.z >> 16);
-    };
-    unsigned bad = 0;
-    {
-        qu32x4 v[QNDZ];
-#pragma unroll
-        for (int j = 0; j < 7; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                v[j * 2 + h] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + h * 16, base + (unsigned)(((slice + 1 + j) & (QG - 1)) * 32 * 4) * 8u, 16);
-#pragma unroll
-        for (int j = 0; j < 7; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (v[j * 2 + h].y == epoch && v[j * 2 + h].w == epoch) put(j, h, v[j * 2 + h]);
-                else bad |= (1u << (j * 2 + h));
-            }
-    }
-    unsigned spins = 0;
-    bool ok = true;
-    while (__any(bad != 0)) {
-        ++spins;
-        if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(status))) {
-            if ((tid & 63) == 0) xch_give_up(status);
-            ok = false;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-        // a whole new sweep, all loads in flight together (re-reading slot by slot serialises the round trips: measured
-        // 10 000 cycles per stale step against 3 000 for the first sweep, tools/stamp_bf16_layer.py --bwd)
-        qu32x4 tv[QNDZ];
-#pragma unroll
-        for (int j = 0; j < 7; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                tv[j * 2 + h] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + h * 16, base + (unsigned)(((slice + 1 + j) & (QG - 1)) * 32 * 4) * 8u, 16);
-#pragma unroll
-        for (int j = 0; j < 7; ++j)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned bit = 1u << (j * 2 + h);
-                if ((bad & bit) && tv[j * 2 + h].y == epoch && tv[j * 2 + h].w == epoch) {
-                    put(j, h, tv[j * 2 + h]);
-                    bad &= ~bit;
-                }
-            }
-    }
-    return ok;
-}
-
-// UNIT-PAIR form of the same exchange (round 4): a lane owns the cells (row, units u0, u0 + 1) - two ADJACENT units of ONE row
-// instead of one unit of two rows - so that every tape access of the pointwise phase is an 8-byte access that a wave
+// UNIT-PAIR ownership (round 4): a lane owns the cells (row, units u0, u0 + 1) - two ADJACENT units of ONE row, not one
+// unit of two rows as in the forward exchange above - so that every tape access of the pointwise phase is an 8-byte access that a wave
 // coalesces into whole 128-byte lines (the kernels were bound by the number of VMEM instructions the CU's one address unit
 // processes per step, tools/stamp_bf16_layer.py --bwd), and the bf16 pair of a granule is one 32-bit LDS word of the tile.
 // Granule order [row 16][unit pair 128][gate 4] of {bf16 pair, epoch}: 32 bytes per (row, pair) = two 16-byte stores.
@@ -458,14 +379,16 @@ __device__ __forceinline__ bool q_dz_gather2(const __amdgpu_buffer_rsrc_t rs, un
     bool ok = true;
     while (__any(bad != 0)) {
         ++spins;
-        if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(status))) {
+        if (xch_wait_expired(spins, status)) {
             if ((tid & 63) == 0) xch_give_up(status);
             ok = false;
             break;
         }
         __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
-        qu32x4 tv[QNDZ];   // a whole new sweep, all loads in flight together (see q_dz_gather)
+        // a whole new sweep, all loads in flight together (re-reading slot by slot serialises the round trips: measured
+        // 10 000 cycles per stale step against 3 000 for the first sweep, tools/stamp_bf16_layer.py --bwd)
+        qu32x4 tv[QNDZ];
 #pragma unroll
         for (int j = 0; j < 7; ++j)
 #pragma unroll

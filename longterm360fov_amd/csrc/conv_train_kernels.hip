@@ -11,13 +11,6 @@
 
 namespace fov {
 
-// derivative of the recurrent activation expressed in its OUTPUT a (as Keras/TF autodiff evaluates it)
-template <int ACT>
-__device__ __forceinline__ float conv_act_grad(float a) {
-    if (ACT == FOV_ACT_HARD_SIGMOID) return (a > 0.f && a < 1.f) ? 0.2f : 0.f;
-    return a * (1.f - a);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256) void convlstm_gates_train_kernel(const float* __restrict__ z, const float* __restrict__ c_prev,
                                                                    float* __restrict__ c_new, float* __restrict__ h, long ldh,
@@ -53,10 +46,10 @@ __global__ __launch_bounds__(256) void convlstm_gates_bwd_kernel(const float* __
     const float dct = dc[idx] + dhv * o * (1.f - tc * tc);
     const float cp = c_prev ? c_prev[idx] : 0.f;
     float* dp = dz + m * 4 * F + j;
-    dp[0] = dct * gg * conv_act_grad<ACT>(i);
-    dp[F] = dct * cp * conv_act_grad<ACT>(f);
+    dp[0] = dct * gg * rec_act_grad<ACT>(i);
+    dp[F] = dct * cp * rec_act_grad<ACT>(f);
     dp[2 * F] = dct * i * (1.f - gg * gg);
-    dp[3 * F] = dhv * tc * conv_act_grad<ACT>(o);
+    dp[3 * F] = dhv * tc * rec_act_grad<ACT>(o);
     dc[idx] = dct * f;
 }
 

@@ -27,6 +27,30 @@ template <int ACT>
 __device__ __forceinline__ float rec_act(float x) {
     return ACT == FOV_ACT_HARD_SIGMOID ? hard_sigmoid_f(x) : sigmoid_f(x);
 }
+// its derivative s'(a) from the stored OUTPUT a (as Keras/TF autodiff evaluates it): a(1-a) (sigmoid) or 0.2*[0<a<1] (hard_sigmoid)
+template <int ACT>
+__device__ __forceinline__ float rec_act_grad(float a) {
+    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
+}
+// BPTT pointwise step t of one cell (Keras LSTMCell backward), from the activated gates i,f,g,o, c = c_t and c_prev = c_{t-1}:
+//   dh = dhs[:,t] + dh_rec;  tc = tanh(c_t);  do = dh*tc;  dc += dh*o*(1-tc^2)
+//   dz = [dc*g*s'(i), dc*c_{t-1}*s'(f), dc*i*(1-g^2), do*s'(o)];  dc *= f
+// `dc` comes in as the gradient that reaches c_t from step t+1 and goes out as the gradient for c_{t-1}.  No masking here:
+// a kernel that zeroes the dz of dead rows does so on the result.
+// The other BPTT kernels (lstm_bwd16, lstm_bwd_cluster, mix_decoder_bwd, the bf16 forms, the stepped pointwise kernels) still
+// write the same expression tree out, with rec_act_grad: through this helper their instruction schedule changes (the
+// values do not), and a schedule change of those kernels wants a measurement of its own.
+template <int ACT>
+__device__ __forceinline__ void lstm_cell_bwd(float i, float f, float g, float o, float c, float c_prev, float dh, float& dc,
+                                              float (&dz)[4]) {
+    const float tc = tanh_f(c);
+    const float dcv = dc + dh * o * (1.f - tc * tc);
+    dz[0] = dcv * g * rec_act_grad<ACT>(i);
+    dz[1] = dcv * c_prev * rec_act_grad<ACT>(f);
+    dz[2] = dcv * i * (1.f - g * g);
+    dz[3] = dh * tc * rec_act_grad<ACT>(o);
+    dc = dcv * f;
+}
 
 // Everything one launch of the LSTM kernels needs.  Phase 1 ("layer"/encoder): T steps over
 // x:(B,T,F) with weights K,R,b from (h0,c0).  Phase 2 (decode only): T_out autoregressive

@@ -50,10 +50,6 @@ struct Bwd16Params {
 __device__ __forceinline__ void x_mfma_a(f32x4& acc, float a, float w_agpr) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(w_agpr));
 }
-template <int ACT>
-__device__ __forceinline__ float x_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
 
 // ROLE 0: one layer per launch.  ROLES 1, 2, 3: the BPTT of TWO stacked layers as ONE launch (lstm_bwd16_pair_kernel; width 512,
 // sixteen workgroups per tile and role), the lower layer about a step behind the upper one on other CUs - at lstm.py's batch
@@ -111,7 +107,7 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
     const int my_row0 = 4 * g4 + CPL * hi;
     const int T = p.T;
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
-    const unsigned arrival = xch_arrive(p.status, sXch, hgroup, slice);
+    xch_arrive(p.status, sXch, hgroup, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -141,7 +137,7 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
         ROLE == 0 ? gbase : p.ring_xb + (size_t)group * p.T * X_PAR, 0, ROLE == 0 ? 0 : (int)((size_t)p.T * X_PAR * 8), 0x00020000);
     xch_hello_poll(p.status, sXch, hgroup, XG, &sFlag[0]);   // same-XCD handshake (xch_common.h)
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -170,7 +166,7 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
                 break;
             }
@@ -256,10 +252,10 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
                     const float dht = dh[r] + cur[6][r];
                     const float tc = tanh_f(cc);
                     const float dcv = dc[r] + dht * og * (1.f - tc * tc);
-                    dzv[r][0] = live[r] ? dcv * gg * x_act_grad<ACT>(ig) : 0.f;
-                    dzv[r][1] = live[r] ? dcv * cprev * x_act_grad<ACT>(fg) : 0.f;
+                    dzv[r][0] = live[r] ? dcv * gg * rec_act_grad<ACT>(ig) : 0.f;
+                    dzv[r][1] = live[r] ? dcv * cprev * rec_act_grad<ACT>(fg) : 0.f;
                     dzv[r][2] = live[r] ? dcv * ig * (1.f - gg * gg) : 0.f;
-                    dzv[r][3] = live[r] ? dht * tc * x_act_grad<ACT>(og) : 0.f;
+                    dzv[r][3] = live[r] ? dht * tc * rec_act_grad<ACT>(og) : 0.f;
                     dc[r] = dcv * fg;
                 }
                 if constexpr (ROLE == 1) {   // the product role waits for these: first
@@ -305,7 +301,7 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
                 unsigned spins = 0;
                 while (__any(bad != 0)) {
                     ++spins;
-                    if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                    if (xch_wait_expired(spins, p.status)) {
                         if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
                         break;
                     }
@@ -410,7 +406,7 @@ __device__ __forceinline__ void bwd16_body(const Bwd16Params& p, const int bx, c
                 unsigned spins = 0;
                 while (__any(bad != 0)) {
                     ++spins;
-                    if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                    if (xch_wait_expired(spins, p.status)) {
                         if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
                         break;
                     }

@@ -24,7 +24,6 @@ namespace fov {
 namespace {
 
 constexpr int B8LDZ = 128 + 4;     // fp32 LDS row stride of the dz tile
-constexpr int B8LDQ = 128 + 16;    // bf16 LDS row stride: 288 B = 72 dwords = 8 (mod 64): conflict-free ds_read_b128
 constexpr size_t B8_PAR = (size_t)QG * QG * QBT * 32;   // granules per parity: [dest][src][row][unit]
 
 struct Bwd8Params {
@@ -50,10 +49,6 @@ struct Bwd8Params {
 __device__ __forceinline__ void b8_mfma_a(f32x4& acc, float a, float w_agpr) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(w_agpr));
 }
-template <int ACT>
-__device__ __forceinline__ float b8_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
 
 // DXF (round 5): the layer's data gradient dx_t = dz_t K^T (a 256-wide input: the stacked encoder layer of the mixing model) is
 // formed here as well.  K^T's own-gate-column slice sits in the OTHER 128 accumulation registers (the same fragments as R^T's,
@@ -64,9 +59,7 @@ __device__ __forceinline__ float b8_act_grad(float a) {
 // (profiles/r05_train_mixing_f32_step_timeline.txt).
 template <int ACT, bool DXF>
 __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
-    constexpr bool BF16 = false;   // the bf16 form is lstm_bwd8n_bf16_kernel below (N-split)
-    __shared__ __attribute__((aligned(16))) float sDZ[BF16 ? 4 : QBT * B8LDZ];
-    __shared__ __attribute__((aligned(16))) unsigned short sDQ[BF16 ? QBT * B8LDQ : 8];
+    __shared__ __attribute__((aligned(16))) float sDZ[QBT * B8LDZ];
     __shared__ int sFlag[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 15, g4 = lane >> 4;
@@ -80,33 +73,27 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
     const int T = p.T;
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
     // ---- resident R^T fragments.  Tile tl of this wave: destination slice 2*wave + (tl>>1), half tl&1; its output unit
     // on this lane is nout; k index lc is an own gate column: gate lc>>5, unit 32*slice + (lc & 31). ----
-    float rt[BF16 ? 1 : 4][BF16 ? 1 : 8][4];   // fp32: [tl][jb][s], lc = 16*jb + 4*g4 + s
+    float rt[4][8][4];                          // [tl][jb][s], lc = 16*jb + 4*g4 + s
     float kt[DXF ? 4 : 1][DXF ? 8 : 1][4];      // DXF: the same fragments of K (input unit nout, own gate column lc)
-    qu32x4 rq[BF16 ? 4 : 1][BF16 ? 4 : 1];     // bf16: [tl][kb],    lc = 32*kb + 8*g4 + j
 #pragma unroll
     for (int tl = 0; tl < 4; ++tl) {
         const int nout = 32 * (2 * wave + (tl >> 1)) + 16 * (tl & 1) + n;
-        if constexpr (BF16) {
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) rq[tl][kb] = load_bfrag_rowmajor(p.R + (size_t)nout * H4 + kb * QH + 32 * slice + 8 * g4);
-        } else {
+        for (int jb = 0; jb < 8; ++jb) {
+            const int lc = 16 * jb + 4 * g4;
+            const f32x4 v = *(const f32x4*)(p.R + (size_t)nout * H4 + (lc >> 5) * QH + 32 * slice + (lc & 31));
 #pragma unroll
-            for (int jb = 0; jb < 8; ++jb) {
-                const int lc = 16 * jb + 4 * g4;
-                const f32x4 v = *(const f32x4*)(p.R + (size_t)nout * H4 + (lc >> 5) * QH + 32 * slice + (lc & 31));
+            for (int s = 0; s < 4; ++s) rt[tl][jb][s] = v[s];
+            if constexpr (DXF) {
+                const f32x4 w = *(const f32x4*)(p.K + (size_t)nout * H4 + (lc >> 5) * QH + 32 * slice + (lc & 31));
 #pragma unroll
-                for (int s = 0; s < 4; ++s) rt[tl][jb][s] = v[s];
-                if constexpr (DXF) {
-                    const f32x4 w = *(const f32x4*)(p.K + (size_t)nout * H4 + (lc >> 5) * QH + 32 * slice + (lc & 31));
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) kt[tl][jb][s] = w[s];
-                }
+                for (int s = 0; s < 4; ++s) kt[tl][jb][s] = w[s];
             }
         }
     }
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(gbase, 0, (int)(2 * B8_PAR * 8), 0x00020000);
     xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -162,14 +149,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
                 const float ig = cur[0][r], fg = cur[1][r], gg = cur[2][r], og = cur[3][r], cc = cur[4][r];
                 const float cprev = (t > 0 || p.c0) ? cur[5][r] : 0.f;   // step 0 without a given state: c_{-1} = 0
                 const float dht = dh[r] + cur[6][r];
-                const float tc = tanh_f(cc);
-                const float dcv = dc[r] + dht * og * (1.f - tc * tc);
                 float dzv[4];
-                dzv[0] = live[r] ? dcv * gg * b8_act_grad<ACT>(ig) : 0.f;
-                dzv[1] = live[r] ? dcv * cprev * b8_act_grad<ACT>(fg) : 0.f;
-                dzv[2] = live[r] ? dcv * ig * (1.f - gg * gg) : 0.f;
-                dzv[3] = live[r] ? dht * tc * b8_act_grad<ACT>(og) : 0.f;
-                dc[r] = dcv * fg;
+                lstm_cell_bwd<ACT>(ig, fg, gg, og, cc, cprev, dht, dc[r], dzv);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) dzv[g] = live[r] ? dzv[g] : 0.f;
                 if (live[r]) {
                     float* zp = p.dz + ((size_t)(b0 + my_row0 + r) * T + t) * H4 + unit;
 #pragma unroll
@@ -178,8 +161,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     dbacc[g] += dzv[g];
-                    if constexpr (BF16) sDQ[(my_row0 + r) * B8LDQ + g * 32 + ul] = bf16_bits(dzv[g]);
-                    else sDZ[(my_row0 + r) * B8LDZ + g * 32 + ul] = dzv[g];
+                    sDZ[(my_row0 + r) * B8LDZ + g * 32 + ul] = dzv[g];
                 }
             }
             // the tape of step t-1 is requested here, a whole step before its use
@@ -189,14 +171,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
             f32x4 acc[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (BF16) {
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const qu32x4 a = *(const qu32x4*)(sDQ + n * B8LDQ + 32 * kb + 8 * g4);
-#pragma unroll
-                    for (int tl = 0; tl < 4; ++tl) qmfma(acc[tl], a, rq[tl][kb]);
-                }
-            } else {
+            {
                 asm volatile("s_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
                 const float* arow = sDZ + n * B8LDZ + 4 * g4;
                 f32x4 a = *(const f32x4*)arow, an = a;
@@ -271,26 +246,13 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8_kernel(Bwd8Params p) {
                         if (v[s].y != epoch || v[s].w != epoch) bad |= (1u << s);
                     }
                 }
-                unsigned spins = 0;
-                while (__any(bad != 0)) {
-                    ++spins;
-                    if (spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
-                        if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                    asm volatile("" ::: "memory");
-                    qu32x4 tv[8];
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) tv[s] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + s * SSTR, par, 16);
-#pragma unroll
-                    for (int s = 0; s < 8; ++s)
-                        if (((bad >> s) & 1u) && tv[s].y == epoch && tv[s].w == epoch) {
-                            part[0][s] = __uint_as_float(tv[s].x);
-                            part[1][s] = __uint_as_float(tv[s].z);
-                            bad &= ~(1u << s);
-                        }
-                }
+                const bool ok = xch_retry<8, 8>(
+                    bad, epoch, p.status, [&](int s) -> qu32x4 { return __builtin_amdgcn_raw_buffer_load_b128(rs, voff + s * SSTR, par, 16); },
+                    [&](int s, const qu32x4& g) {
+                        part[0][s] = __uint_as_float(g.x);
+                        part[1][s] = __uint_as_float(g.z);
+                    });
+                if (!ok && lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     float a = 0.f;
@@ -387,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8n_bf16_kernel(Bwd8Params p) {
     const int unit0 = 32 * slice + pu;
     const int T = p.T;
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 #ifdef FOV_STAMPS
@@ -415,7 +377,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8n_bf16_kernel(Bwd8Params p) {
         p.xch + (size_t)group * 2 * (Q_DZ_BYTES / 8), 0, (int)(2 * Q_DZ_BYTES), 0x00020000);
     xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -462,10 +424,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd8n_bf16_kernel(Bwd8Params p) {
                 const float dht = dh[u] + cur[6][u];
                 const float tc = tanh_f(cc);
                 const float dcv = dc[u] + dht * og * (1.f - tc * tc);
-                dzv[0][u] = live ? dcv * gg * b8_act_grad<ACT>(ig) : 0.f;
-                dzv[1][u] = live ? dcv * cprev * b8_act_grad<ACT>(fg) : 0.f;
+                dzv[0][u] = live ? dcv * gg * rec_act_grad<ACT>(ig) : 0.f;
+                dzv[1][u] = live ? dcv * cprev * rec_act_grad<ACT>(fg) : 0.f;
                 dzv[2][u] = live ? dcv * ig * (1.f - gg * gg) : 0.f;
-                dzv[3][u] = live ? dht * tc * b8_act_grad<ACT>(og) : 0.f;
+                dzv[3][u] = live ? dht * tc * rec_act_grad<ACT>(og) : 0.f;
                 dc[u] = dcv * fg;
             }
             // publish first (the partners wait for it), then the tape traffic of this step

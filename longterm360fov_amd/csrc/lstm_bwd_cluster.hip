@@ -26,7 +26,6 @@
 namespace fov {
 
 constexpr int BBT = 16;
-constexpr unsigned BSPIN_LIMIT = 1u << 20;
 #ifndef FOV_GATHER_AFTER_Q
 #define FOV_GATHER_AFTER_Q 8
 #endif
@@ -56,11 +55,6 @@ struct BwdParams {
     int epoch_span;         // epochs this launch may consume (xch_common.h)
 };
 
-template <int ACT>
-__device__ __forceinline__ float bwd_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
-
 template <int H, int ACT>
 __global__ __launch_bounds__(256, 1) void lstm_bwd_cluster_kernel(BwdParams p) {
     constexpr int G = H / 64;
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_cluster_kernel(BwdParams p) {
     const int unit = slice * 64 + wave * 16 + n;   // the hidden unit this lane owns
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
     __shared__ unsigned sXch[4];
-    const unsigned arrival = G > 1 ? xch_arrive(p.status, sXch, group, slice) : 0u;
+    if (G > 1) xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = G > 1 && xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -116,8 +110,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_cluster_kernel(BwdParams p) {
 
     if (G > 1) xch_hello_poll(p.status, sXch, group, G, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    XchTicket ticket = {0u, 0u, 0u};
-    if (G > 1) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (G > 1) ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (G > 1 && tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -166,10 +160,10 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_cluster_kernel(BwdParams p) {
                 const float dht = dh[r] + (p.dhs ? dhs_cur[r] : 0.f);
                 const float tc = tanh_f(cc);
                 const float dcv = dc[r] + dht * og * (1.f - tc * tc);
-                dzv[0][r] = live[r] ? dcv * gg * bwd_act_grad<ACT>(ig) : 0.f;
-                dzv[1][r] = live[r] ? dcv * cprev * bwd_act_grad<ACT>(fg) : 0.f;
+                dzv[0][r] = live[r] ? dcv * gg * rec_act_grad<ACT>(ig) : 0.f;
+                dzv[1][r] = live[r] ? dcv * cprev * rec_act_grad<ACT>(fg) : 0.f;
                 dzv[2][r] = live[r] ? dcv * ig * (1.f - gg * gg) : 0.f;
-                dzv[3][r] = live[r] ? dht * tc * bwd_act_grad<ACT>(og) : 0.f;
+                dzv[3][r] = live[r] ? dht * tc * rec_act_grad<ACT>(og) : 0.f;
                 dc[r] = live[r] ? dcv * fg : 0.f;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) dbacc[g] += dzv[g][r];
@@ -259,7 +253,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_cluster_kernel(BwdParams p) {
                     for (int j = 0; j < (G - 1) * 2; ++j) ok = ok && (v[j].y == epoch) && (v[j].w == epoch);
                     if (__all(ok)) break;
                     ++spins;
-                    if (spins > BSPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                    // xch_wait_expired(spins, p.status), written out: through the helper this loop alone compiles differently
+                    if (spins > kXchSpinLimit || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
                         if (lane == 0) {
                             xch_give_up(p.status);
                             sFlag[0] = 1;

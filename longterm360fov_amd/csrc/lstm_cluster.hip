@@ -47,7 +47,6 @@ constexpr int KPAD = 2;         // spare K-slice blocks per wave for the run-ahe
 constexpr int NXBUF = 3;        // x tiles in LDS: x_{t+2} is written while x_{t+1} and x_t may be read
 constexpr int CL_MAX_F = 96;
 constexpr int CL_MAX_O = 8;
-constexpr unsigned SPIN_LIMIT = 1u << 20;
 
 constexpr int MODE_LAYER = 0;   // T steps over x:(B,T,F) from (h0,c0); optional hs / hT / cT
 constexpr int MODE_DECODE = 1;  // T_out autoregressive steps from (h0,c0): y_t = tanh(h_t W + bias) fed back
@@ -475,7 +474,6 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     if constexpr (!F2) load_weights<H, !LAYER, JA, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);
     FOV_PSTAMP(2);
     const bool poisoned = hdr && xch_poisoned(p.status);   // one wave-wide load per wave; wave 0's value decides (sFlag[0])
-    const unsigned arrival = 0;
     if (tid == 0) { sFlag[0] = (poisoned || (F2 && cy.aborted)) ? 1 : 0; sFlag[1] = 0; }
     if (hdr && !poisoned && tid < G) {   // (lanes of wave 0: thread 0 has just written sFlag, program order)
         const unsigned long long hello_tag = (unsigned long long)sXch[0] + 1ull;
@@ -484,7 +482,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         while (true) {
             hv = ld_granule(hello + tid);
             if ((hv >> 32) == hello_tag) break;
-            if (++spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(++spins, p.status)) {
                 xch_give_up(p.status);
                 sFlag[0] = 1;
                 break;
@@ -553,8 +551,8 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
 
     __syncthreads();
     FOV_PSTAMP(5);
-    XchTicket ticket = {0u, 0u, 0u};
-    if (xch_used && !F2) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (xch_used && !F2) ticket = xch_ticket(sXch);
     if constexpr (F2) ticket = cy.ticket;
     unsigned epoch = F2 ? cy.epoch : ticket.base;
     const bool same_xcd = F2 ? cy.same_xcd : (xch_used && (sFlag[1] == 0) && (p.force_safe_exchange == 0));
@@ -804,7 +802,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) ok = ok && (vy[q].y == epoch) && (vy[q].w == epoch);
                         if (__all(ok)) break;
-                        if (++spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                        if (xch_wait_expired(++spins, p.status)) {
                             if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }      // (seen by every wave behind this step's barrier 2)
                             break;
                         }
@@ -962,7 +960,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                 if (!tags_ok()) {
                     while (true) {
                         ++spins;
-                        if (spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                        if (xch_wait_expired(spins, p.status)) {
                             if (lane == 0) {
                                 xch_give_up(p.status);
                                 sFlag[0] = 1;
@@ -1031,7 +1029,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) ok = ok && (vy[q].y == epoch) && (vy[q].w == epoch);
                         if (__all(ok)) break;
-                        if (++spins > SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                        if (xch_wait_expired(++spins, p.status)) {
                             if (lane == 0) xch_give_up(p.status);
                             got = false;
                             break;

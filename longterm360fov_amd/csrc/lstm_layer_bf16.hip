@@ -56,7 +56,6 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_bf16_kernel(LstmParams p) {
     __shared__ unsigned sXch[4];
     const XchHeader header = xch_arrive_request(p.status, xch_used);   // taken behind the first weight requests (xch_common.h)
     const unsigned timeout_word = xch_timeout_word(p.status);
-    const unsigned arrival = 0u;
 #ifdef FOV_STAMPS
     __shared__ unsigned long long sStamps[QSTAMP_STEPS * QSTAMP_SLOTS];
     const bool stamp_on = (blockIdx.x == 5 && tid == 0);
@@ -84,8 +83,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_bf16_kernel(LstmParams p) {
 #endif
     if (xch_used) xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    XchTicket ticket = {0u, 0u, 0u};
-    if (xch_used) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (xch_used) ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (xch_used && tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)

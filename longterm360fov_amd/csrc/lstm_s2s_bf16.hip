@@ -45,7 +45,6 @@ __global__ __launch_bounds__(256, 1) void s2s_bf16_kernel(LstmParams p) {
     __shared__ unsigned sXch[4];
     const XchHeader header = xch_arrive_request(p.status, xch_used);
     const unsigned timeout_word = xch_timeout_word(p.status);
-    const unsigned arrival = 0u;
 
     // ---- resident weights: packed bf16 B fragments ----
     qu32x4 wk[NKB][2], wr[8][2], wkd[1][2], wrd[8][2], wd[2];
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(256, 1) void s2s_bf16_kernel(LstmParams p) {
     const unsigned pub_off = (unsigned)((my_row0 >> 1) * QH + unit) * 8u;
     if (xch_used) xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);
     __syncthreads();
-    XchTicket ticket = {0u, 0u, 0u};
-    if (xch_used) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (xch_used) ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (xch_used && tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)

@@ -47,12 +47,6 @@ __host__ __device__ constexpr int sf_ldz(int HP) { return 4 * HP + 4; }
 // floats of the backward's LDS: R^T in B-operand order, the dz tile, one partial dx fragment per wave
 __host__ __device__ constexpr int sf_bwd_lds_floats(int HP) { return HP * 4 * HP + SF_BT * sf_ldz(HP) + (HP / 16) * 64 * 4; }
 
-// derivative of the recurrent activation from its stored output (lstm_train.hip)
-template <int ACT>
-__device__ __forceinline__ float sf_rec_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
-
 template <int HP, int ACT>
 __global__ __launch_bounds__(4 * HP, 1) void selffed_fwd_kernel(SelfFedFwdParams p) {
     constexpr int NJ = HP / 16, H4 = 4 * HP, LDH = HP + 4, HT = SF_BT * LDH;
@@ -258,10 +252,10 @@ __global__ __launch_bounds__(4 * HP, 1) void selffed_bwd_kernel(SelfFedBwdParams
             const float dov = dh[r] * tc;
             const float dcv = dc[r] + dh[r] * go[r] * (1.f - tc * tc);
             float dz[4];
-            dz[0] = dcv * gg[r] * sf_rec_act_grad<ACT>(gi[r]);
-            dz[1] = dcv * cp[r] * sf_rec_act_grad<ACT>(gf[r]);
+            dz[0] = dcv * gg[r] * rec_act_grad<ACT>(gi[r]);
+            dz[1] = dcv * cp[r] * rec_act_grad<ACT>(gf[r]);
             dz[2] = dcv * gi[r] * (1.f - gg[r] * gg[r]);
-            dz[3] = dov * sf_rec_act_grad<ACT>(go[r]);
+            dz[3] = dov * rec_act_grad<ACT>(go[r]);
             dc[r] = dcv * gf[r];
             const int row = b0 + 4 * g4 + r;
             float* zt = sZ + (4 * g4 + r) * LDZ + unit;

@@ -130,7 +130,6 @@ __device__ __forceinline__ void stack2_body(const Stack2Params& p, unsigned shor
 #endif
     const XchHeader header = xch_arrive_request(p.status);   // taken behind the first weight set (xch_common.h)
     const unsigned timeout_word = xch_timeout_word(p.status);
-    const unsigned arrival = 0u;
     qu32x4 wk[NKB][2], wr[8][2];
     auto commit = [&]() {
         xch_arrive_commit(p.status, sXch, header, ROLE * p.num_groups + group, slice);
@@ -189,7 +188,7 @@ __device__ __forceinline__ void stack2_body(const Stack2Params& p, unsigned shor
     if (stamp_on) g_s2_stamps[ROLE][S2STAMP_STEPS - 2][3] = __builtin_amdgcn_s_memtime();   // every member's hello word seen
 #endif
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
 #ifdef FOV_STAMPS
     if (stamp_on) g_s2_stamps[ROLE][S2STAMP_STEPS - 2][4] = __builtin_amdgcn_s_memtime();   // first barrier passed
 #endif
@@ -227,7 +226,7 @@ __device__ __forceinline__ void stack2_body(const Stack2Params& p, unsigned shor
                     bad &= ~(1u << j);
                 }
             if (!__any(bad != 0)) return true;
-            if (++spins > Q_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(++spins, p.status)) {
                 if ((tid & 63) == 0) xch_give_up(p.status);
                 return false;
             }

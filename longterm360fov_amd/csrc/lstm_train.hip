@@ -11,16 +11,9 @@
 namespace fov {
 
 // ---------------------------------------------------------------------------------------
-// BPTT pointwise step t (Keras LSTMCell backward):
-//   dh = dhs[:,t] + dh_rec;  tc = tanh(c_t);  do = dh*tc;  dc += dh*o*(1-tc^2)
-//   dz = [dc*g*s'(i), dc*c_{t-1}*s'(f), dc*i*(1-g^2), do*s'(o)];  dc *= f
-// s'(a) = a(1-a) (sigmoid) or 0.2*[0<a<1] (hard_sigmoid).  dh_rec / dc live in (B,H) buffers.
+// BPTT pointwise step t of the host-stepped recurrence: the formula of lstm_cell_bwd (fov_common.h), written out.
+// dh_rec / dc live in (B,H) buffers.
 // ---------------------------------------------------------------------------------------
-template <int ACT>
-__device__ __forceinline__ float rec_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256) void lstm_bwd_pointwise(const float* __restrict__ reserve, const float* __restrict__ c0,
                                                           const float* __restrict__ dhs, const float* __restrict__ dh_rec,

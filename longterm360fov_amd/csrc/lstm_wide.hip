@@ -29,7 +29,6 @@ namespace fov {
 namespace {
 
 constexpr int WBT = 16;
-constexpr unsigned WSPIN = 1u << 20;
 
 typedef unsigned wu32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned wu32x4 __attribute__((ext_vector_type(4)));
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(256, 1) void lstm_wide_kernel(LstmParams p) {
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
     const bool xch_used = steps > 1;
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_used ? xch_arrive(p.status, sXch, group, slice) : 0u;
+    if (xch_used) xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_used && xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -120,8 +119,8 @@ __global__ __launch_bounds__(256, 1) void lstm_wide_kernel(LstmParams p) {
     constexpr unsigned PARITY = WBT * WH * 8u;
     if (xch_used) xch_hello_poll(p.status, sXch, group, WG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    XchTicket ticket = {0u, 0u, 0u};
-    if (xch_used) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (xch_used) ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (xch_used && tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void lstm_wide_kernel(LstmParams p) {
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > WSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) {
                     xch_give_up(p.status);
                     sFlag[0] = 1;

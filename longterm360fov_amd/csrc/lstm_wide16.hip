@@ -24,7 +24,6 @@ namespace fov {
 namespace {
 
 constexpr int VBT = 16;
-constexpr unsigned VSPIN = 1u << 20;
 
 // granule offsets of the three-role launch's extra areas behind layer 1's ring (T slots per group) and layer 2's parity slots
 // (2 per group): the mailboxes (T slots of W16_MAIL granules per workgroup of layer 2), then the mirror rings (T slots per group)
@@ -203,7 +202,7 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
     float* tw = sT + wave * (16 * 17);
     const bool xch_used = ROLE != 0 || steps > 1;
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_used ? xch_arrive(p.status, sXch, hgroup, slice) : 0u;
+    if (xch_used) xch_arrive(p.status, sXch, hgroup, slice);
     const bool poisoned = xch_used && xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -245,8 +244,8 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
     constexpr unsigned PARITY = VBT * WH * 8u;
     if (xch_used) xch_hello_poll(p.status, sXch, hgroup, WG, &sFlag[0]);
     __syncthreads();
-    XchTicket ticket = {0u, 0u, 0u};
-    if (xch_used) ticket = xch_ticket(sXch, arrival);
+    XchTicket ticket = {0u, 0u, false};
+    if (xch_used) ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base + (L2 ? (unsigned)p.T : 0u);   // layer 2's own tags follow layer 1's T
     bool aborted = sFlag[0] != 0;
     if (xch_used && tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);
@@ -277,7 +276,7 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) {
                     xch_give_up(p.status);
                     sFlag[0] = 1;
@@ -336,7 +335,7 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
             unsigned spins = 0;
             while (__any(bad != 0)) {
                 ++spins;
-                if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                if (xch_wait_expired(spins, p.status)) {
                     if (lane == 0) {
                         xch_give_up(p.status);
                         sFlag[0] = 1;
@@ -377,7 +376,7 @@ __device__ __forceinline__ void wide16_body(const LstmParams& p, const int bx, f
             unsigned spins = 0;
             while (__any(zq[0].y != want || zq[0].w != want || zq[1].y != want || zq[1].w != want)) {
                 ++spins;
-                if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+                if (xch_wait_expired(spins, p.status)) {
                     if (lane == 0) {
                         xch_give_up(p.status);
                         sFlag[0] = 1;
@@ -614,7 +613,7 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
     const int unit = 16 * slice + 4 * wave + (n & 3);
     const int col = (n >> 2) * WH + unit;
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, -1, 0);   // header words + arrival count; no handshake of its own
+    xch_arrive(p.status, sXch, -1, 0);   // header words + arrival count; no handshake of its own
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
     float wk[NJX][4];
@@ -626,7 +625,7 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
         p.xch + w16_mail_base(p.num_groups, p.T, WH) + ((size_t)group * WG + slice) * p.T * W16_MAIL, 0,
         p.T * (int)(W16_MAIL * sizeof(unsigned long long)), 0x00020000);
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     bool aborted = sFlag[0] != 0;
 
     // thread (row tid / 16, c = tid % 16) gathers the unit pairs c + 16 i of layer 1's h tile of step s (slot s, tags
@@ -652,7 +651,7 @@ __device__ __forceinline__ void wide16_product_body(const LstmParams& p, const i
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) {
                     xch_give_up(p.status);
                     sFlag[0] = 1;
@@ -796,7 +795,7 @@ __global__ __launch_bounds__(256, 1) void wide16_s2s_kernel(LstmParams p) {
     const int row_o = 4 * g4 + (n >> 2);
     float* tw = sT + wave * (16 * 17);
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -827,7 +826,7 @@ __global__ __launch_bounds__(256, 1) void wide16_s2s_kernel(LstmParams p) {
     constexpr unsigned PARITY = VBT * WH * 8u;
     xch_hello_poll(p.status, sXch, group, WG, &sFlag[0]);
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);
@@ -857,7 +856,7 @@ __global__ __launch_bounds__(256, 1) void wide16_s2s_kernel(LstmParams p) {
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > VSPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }
                 break;
             }

@@ -44,7 +44,6 @@ constexpr int MG = 8;            // workgroups per tile
 constexpr int MBT = 16;          // sequences per tile
 constexpr int MLDH = MH + 4;     // LDS row stride of an h tile
 constexpr int MNG = 7;           // 16-byte loads (TWO adjacent units' tagged granules) per thread and exchange: 7 slices * 16 rows * 16 pairs / 256
-constexpr unsigned M_SPIN_LIMIT = 1u << 20;
 
 typedef unsigned mu32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned mu32x4 __attribute__((ext_vector_type(4)));
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_kernel(MixDecParams p) {
 
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
     // ---- resident weights ----
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_kernel(MixDecParams p) {
 #endif
     xch_hello_poll(p.status, sXch, group, MG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -236,7 +235,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_kernel(MixDecParams p) {
             for (int j = 0; j < MNG; ++j) ok = ok && (v[j].y == epoch) && (v[j].w == epoch);
             if (__all(ok)) break;
             ++spins;
-            if (spins > M_SPIN_LIMIT || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 if (lane == 0) {
                     xch_give_up(p.status);
                     sFlag[0] = 1;

@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bf16_kernel(MixDecParams p
     __shared__ unsigned sXch[4];
     const XchHeader header = xch_arrive_request(p.status);   // taken behind the first weight requests (xch_common.h)
     const unsigned timeout_word = xch_timeout_word(p.status);
-    const unsigned arrival = 0u;
     // ---- resident weights (packed bf16 B fragments) ----
     qu32x4 w1[8][2], wk2[8][2], w2[8][2], wk1[1][2];
     load_weight_set<1>(wk1, p.K1, H4, O, g4, col0, col1);      // K1 (O <= 8 rows): one zero-padded k-block
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bf16_kernel(MixDecParams p
     constexpr unsigned LAYER_BYTES = 2u * Q_TILE_BYTES;
     xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)

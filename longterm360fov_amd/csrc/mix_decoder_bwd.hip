@@ -34,7 +34,6 @@ constexpr int BH = 256;
 constexpr int BG = 8;
 constexpr int BBT = 16;
 constexpr int BLDZ = 128 + 4;    // LDS row stride of the dz tile (16 x 128 own gate columns)
-constexpr unsigned B_SPIN = 1u << 20;
 constexpr int BK2_LDS_BLOCKS = 28;
 
 typedef unsigned bwu32x2 __attribute__((ext_vector_type(2)));
@@ -57,10 +56,6 @@ __device__ __forceinline__ void bm_end(f32x4 (&acc)[N]) {
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");
 #pragma unroll
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(acc[i]));
-}
-template <int ACT>
-__device__ __forceinline__ float bact_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
 }
 
 }  // namespace
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
     const int my_row0 = 4 * g4 + 2 * hi;
     // epoch tags continue from the workspace header, a poisoned workspace skips the body (xch_common.h)
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) sFlag[0] = poisoned ? 1 : 0;
 
@@ -185,25 +180,10 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
                 if (v[s].y != epoch) bad |= (1u << s);
             }
         }
-        unsigned spins = 0;
-        while (__any(bad != 0)) {
-            ++spins;
-            if (spins > B_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
-                give_up();
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-            asm volatile("" ::: "memory");
-            bwu32x2 tv[8];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) tv[s] = __builtin_amdgcn_raw_buffer_load_b64(rs, voff + s * sstride, base, 16);
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (((bad >> s) & 1u) && tv[s].y == epoch) {
-                    part[s] = __uint_as_float(tv[s].x);
-                    bad &= ~(1u << s);
-                }
-        }
+        if (!xch_retry<8, 8>(
+                bad, epoch, p.status, [&](int s) -> bwu32x2 { return __builtin_amdgcn_raw_buffer_load_b64(rs, voff + s * sstride, base, 16); },
+                [&](int s, const bwu32x2& g) { part[s] = __uint_as_float(g.x); }))
+            give_up();
         float acc = 0.f;
 #pragma unroll
         for (int s = 0; s < 8; ++s) acc += part[s];
@@ -229,7 +209,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
         unsigned spins = 0;
         while (__any(bad != 0)) {
             ++spins;
-            if (spins > B_SPIN || ((spins & 63u) == 0 && xch_poisoned(p.status))) {
+            if (xch_wait_expired(spins, p.status)) {
                 give_up();
                 break;
             }
@@ -256,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
     };
     xch_hello_poll(p.status, sXch, group, BG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     epoch = ticket.base;
     aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -319,10 +299,10 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
                 const float dh = dhd + dh2r[r];
                 const float dct = dc2[r] + dh * og * (1.f - tc * tc);
                 const bool rl = row < p.B;
-                dz[r][0] = rl ? dct * gg * bact_grad<ACT>(ig) : 0.f;
-                dz[r][1] = rl ? dct * cp * bact_grad<ACT>(fg) : 0.f;
+                dz[r][0] = rl ? dct * gg * rec_act_grad<ACT>(ig) : 0.f;
+                dz[r][1] = rl ? dct * cp * rec_act_grad<ACT>(fg) : 0.f;
                 dz[r][2] = rl ? dct * ig * (1.f - gg * gg) : 0.f;
-                dz[r][3] = rl ? dh * tc * bact_grad<ACT>(og) : 0.f;
+                dz[r][3] = rl ? dh * tc * rec_act_grad<ACT>(og) : 0.f;
                 dc2[r] = rl ? dct * fg : 0.f;
                 if (row < p.B) {
                     float* zp = p.DZ2 + ((size_t)t * p.B + row) * H4 + unit;
@@ -417,10 +397,10 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_kernel(MixDecBwdParams
                 const float dh = dh1in[r] + dh1r[r];
                 const float dct = dc1[r] + dh * og * (1.f - tc * tc);
                 const bool rl = row < p.B;
-                dz[r][0] = rl ? dct * gg * bact_grad<ACT>(ig) : 0.f;
-                dz[r][1] = rl ? dct * cp * bact_grad<ACT>(fg) : 0.f;
+                dz[r][0] = rl ? dct * gg * rec_act_grad<ACT>(ig) : 0.f;
+                dz[r][1] = rl ? dct * cp * rec_act_grad<ACT>(fg) : 0.f;
                 dz[r][2] = rl ? dct * ig * (1.f - gg * gg) : 0.f;
-                dz[r][3] = rl ? dh * tc * bact_grad<ACT>(og) : 0.f;
+                dz[r][3] = rl ? dh * tc * rec_act_grad<ACT>(og) : 0.f;
                 dc1[r] = rl ? dct * fg : 0.f;
                 if (row < p.B) {
                     float* zp = p.DZ1 + ((size_t)t * p.B + row) * H4 + unit;

@@ -26,11 +26,6 @@ namespace {
 constexpr int DRS = 33;   // row stride of a partial (16 x 32) tile in LDS
 
 template <int ACT>
-__device__ __forceinline__ float db_act_grad(float a) {
-    return ACT == FOV_ACT_HARD_SIGMOID ? ((a > 0.f && a < 1.f) ? 0.2f : 0.f) : a * (1.f - a);
-}
-
-template <int ACT>
 __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_bf16_kernel(MixDecBwdParams p) {
     __shared__ __attribute__((aligned(16))) unsigned short sDZ[QBT * QLDZ];   // the whole dz tile of the current layer, bf16
     __shared__ float sRedA[4 * QBT * DRS];       // [wave][row][unit] partial of product A (R2^T / R1^T)
@@ -52,7 +47,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_bf16_kernel(MixDecBwdP
     const int pu = 2 * (tid & 15);
     const int unit0 = 32 * slice + pu;
     __shared__ unsigned sXch[4];
-    const unsigned arrival = xch_arrive(p.status, sXch, group, slice);
+    xch_arrive(p.status, sXch, group, slice);
     const bool poisoned = xch_poisoned(p.status);
     if (tid == 0) { sFlag[0] = poisoned ? 1 : 0; sFlag[1] = 0; sFlag[2] = 0; }
 
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_bf16_kernel(MixDecBwdP
     constexpr unsigned LAYER_BYTES = 2u * Q_DZ_BYTES;
     xch_hello_poll(p.status, sXch, group, QG, &sFlag[0]);   // same-XCD handshake (xch_common.h): partners' words, published at entry
     __syncthreads();
-    const XchTicket ticket = xch_ticket(sXch, arrival);
+    const XchTicket ticket = xch_ticket(sXch);
     unsigned epoch = ticket.base;
     bool aborted = sFlag[0] != 0;
     if (tid == 0 && !ticket.same_xcd && !aborted) xch_count_safe(p.status, ticket);   // (fov_exchange_mode)
@@ -156,10 +151,10 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_bf16_kernel(MixDecBwdP
                     const float tc = tanh_f(ct);
                     const float dh = dhd + dh2r[u];
                     const float dct = dc2[u] + dh * og * (1.f - tc * tc);
-                    dz[0][u] = lv ? dct * gg * db_act_grad<ACT>(ig) : 0.f;
-                    dz[1][u] = lv ? dct * cp * db_act_grad<ACT>(fg) : 0.f;
+                    dz[0][u] = lv ? dct * gg * rec_act_grad<ACT>(ig) : 0.f;
+                    dz[1][u] = lv ? dct * cp * rec_act_grad<ACT>(fg) : 0.f;
                     dz[2][u] = lv ? dct * ig * (1.f - gg * gg) : 0.f;
-                    dz[3][u] = lv ? dh * tc * db_act_grad<ACT>(og) : 0.f;
+                    dz[3][u] = lv ? dh * tc * rec_act_grad<ACT>(og) : 0.f;
                     dc2[u] = dct * fg;
                 }
                 unsigned dzp[4];
@@ -218,10 +213,10 @@ __global__ __launch_bounds__(256, 1) void mix_decoder_bwd_bf16_kernel(MixDecBwdP
                     const float tc = tanh_f(ct);
                     const float dh = dh1in[u] + dh1r[u];
                     const float dct = dc1[u] + dh * og * (1.f - tc * tc);
-                    dz[0][u] = lv ? dct * gg * db_act_grad<ACT>(ig) : 0.f;
-                    dz[1][u] = lv ? dct * cp * db_act_grad<ACT>(fg) : 0.f;
+                    dz[0][u] = lv ? dct * gg * rec_act_grad<ACT>(ig) : 0.f;
+                    dz[1][u] = lv ? dct * cp * rec_act_grad<ACT>(fg) : 0.f;
                     dz[2][u] = lv ? dct * ig * (1.f - gg * gg) : 0.f;
-                    dz[3][u] = lv ? dh * tc * db_act_grad<ACT>(og) : 0.f;
+                    dz[3][u] = lv ? dh * tc * rec_act_grad<ACT>(og) : 0.f;
                     dc1[u] = dct * fg;
                 }
                 unsigned dzp[4];

@@ -83,13 +83,59 @@ __device__ __forceinline__ bool xch_timeout_set(unsigned word) {
 __device__ __forceinline__ void xch_give_up(unsigned* status) {
     __hip_atomic_store(status + ST_TIMEOUT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The bound of EVERY in-kernel wait on a partner's tag or hello word: what turns a lost partner into FOV_ERR_TIMEOUT instead
+// of a hung GPU.  A wait gives up after kXchSpinLimit re-reads, or - looked at every 64th - as soon as another wait on the
+// workspace has given up (the partner it waits for may have left for that reason).
+constexpr unsigned kXchSpinLimit = 1u << 20;
+__device__ __forceinline__ bool xch_wait_expired(unsigned spins, const unsigned* status) {
+    return spins > kXchSpinLimit || ((spins & 63u) == 0 && xch_poisoned(status));
+}
+// A loaded granule against the tag it is waited for with: {value, tag}, or two neighbours {value, tag, value, tag} of one
+// 16-byte load, each checked on its own tag.
+typedef unsigned xch_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned xch_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bool xch_fresh(xch_u32x2 g, unsigned tag) { return g.y == tag; }
+__device__ __forceinline__ bool xch_fresh(xch_u32x4 g, unsigned tag) { return g.y == tag && g.w == tag; }
+// The retry sweeps of the BPTT kernels' gathers, behind a first sweep (the hot path, in each kernel) that left the stale
+// granules of this lane in the bit mask `bad`: until no lane of the wave has one left, all N granules are loaded again, CH
+// at a time - `load(j)` - and `take(j, granule)` stores those that were stale and now carry `tag`.  A whole sweep with its
+// loads in flight together, not slot by slot: that serialises the round trips (measured 10 000 cycles per stale step against
+// 3 000 for the first sweep, tools/stamp_bf16_layer.py --bwd).  -> false when the wait expired: the caller gives up.
+// Users: lstm_bwd8_kernel's gather and mix_decoder_bwd's gather_one.  The loops of the same shape in lstm_bwd16.hip,
+// mix_decoder_bwd's gather_pair and q_dz_gather2 stay written out: through this helper those kernels came out with scratch
+// (pair launch, fused decoder), other fused multiply-adds in the gates (width 128, hard_sigmoid) or 0.3 % slower (pair launch).
+template <int N, int CH, class Load, class Take>
+__device__ __forceinline__ bool xch_retry(unsigned bad, unsigned tag, const unsigned* status, Load load, Take take) {
+    static_assert(N <= 32 && N % CH == 0, "one mask bit per granule, whole chunks");
+    unsigned spins = 0;
+    while (__any(bad != 0)) {
+        ++spins;
+        if (xch_wait_expired(spins, status)) return false;
+        __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int h = 0; h < N / CH; ++h) {
+            decltype(load(0)) tv[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) tv[u] = load(h * CH + u);
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int j = h * CH + u;
+                if (((bad >> j) & 1u) && xch_fresh(tv[u], tag)) {
+                    take(j, tv[u]);
+                    bad &= ~(1u << j);
+                }
+            }
+        }
+    }
+    return true;
+}
 
 // What a workgroup takes from the header when it starts.  `base` and `launch` are uniform over the grid: the words are
 // only rewritten after every workgroup of the launch has read them (xch_settle).
 struct XchTicket {
     unsigned base;      // epoch base of this launch: its tags lie in (base, base + span]
     unsigned launch;    // index of this launch on the workspace
-    unsigned arrival;   // unused since round 3 (kept for the call sites' signature)
     bool same_xcd;      // the hello handshake of this launch found every member of the group on one XCD (XCH_STORE_B64)
 };
 
@@ -110,7 +156,7 @@ __device__ __forceinline__ void xch_count_arrival(unsigned* status) {
 // -> (group, slice) map, which round-robin dispatch puts on one XCD - a placement PREFERENCE that the handshake verifies
 // at run time): thread 0 publishes {launch tag, HW_REG_XCC_ID} at once, xch_hello_poll() collects the partners' words
 // later, behind the weight loads, when they have long become visible.
-__device__ __forceinline__ unsigned xch_arrive(unsigned* status, unsigned* lds2, int group = -1, int slice = 0) {
+__device__ __forceinline__ void xch_arrive(unsigned* status, unsigned* lds2, int group = -1, int slice = 0) {
     if (threadIdx.x == 0) {
         unsigned base = xch_status_load(status + ST_EPOCH);
         unsigned launch = xch_status_load(status + ST_LAUNCHES);
@@ -126,7 +172,6 @@ __device__ __forceinline__ unsigned xch_arrive(unsigned* status, unsigned* lds2,
             __hip_atomic_store(xch_hello_words(status, group) + slice, ((unsigned long long)(base + 1u) << 32) | xch_xcc_id(),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    return 0u;
 }
 // xch_arrive in two halves (round 4) for a kernel that loads weights in its prologue: thread 0 REQUESTS the header words at
 // the kernel's entry, the first batch of weight loads goes out behind them, and only then does it take the words, count the
@@ -169,8 +214,7 @@ __device__ __forceinline__ void xch_arrive_commit(unsigned* status, unsigned* ld
     const unsigned arrive_off = (unsigned)(256 + kXchBytes - kArriveBytes) + (xch_linear_block() % kArriveWords) * (unsigned)(kArriveStride * 4);
     (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(one, rs, off + arrive_off, 0, 0);   // agent scope, no return (as xch_count_arrival)
     const unsigned hello_off = (unsigned)(256 + kXchBytes - kHelloBytes) + (unsigned)((group < 0 ? 0 : group) * kHelloStride + slice) * 8u;
-    typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64((u32x2_){xch_xcc_id(), base + 1u}, rs, (group >= 0 ? off : 0x80000000u) + hello_off, 0, 16 /* sc1 */);
+    __builtin_amdgcn_raw_buffer_store_b64((xch_u32x2){xch_xcc_id(), base + 1u}, rs, (group >= 0 ? off : 0x80000000u) + hello_off, 0, 16 /* sc1 */);
     if (threadIdx.x == 0 && active) {   // (LDS only: the vector memory counters are the same on both sides of this branch)
         lds2[0] = base;
         lds2[1] = launch;
@@ -189,7 +233,7 @@ __device__ __forceinline__ void xch_hello_poll(unsigned* status, unsigned* lds2,
         while (true) {
             hv = __hip_atomic_load(hello, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if ((unsigned)(hv >> 32) == tag) break;
-            if (++spins > (1u << 20) || ((spins & 63u) == 0 && xch_poisoned(status))) {
+            if (xch_wait_expired(++spins, status)) {
                 xch_give_up(status);
                 *abort_flag = 1;
                 break;
@@ -199,14 +243,13 @@ __device__ __forceinline__ void xch_hello_poll(unsigned* status, unsigned* lds2,
         if ((unsigned)hv != xch_xcc_id()) lds2[3] = 1u;
     }
 }
-__device__ __forceinline__ XchTicket xch_ticket(const unsigned* lds2, unsigned arrival) {
+__device__ __forceinline__ XchTicket xch_ticket(const unsigned* lds2) {
     // readfirstlane: the words are the same for every lane, but a value loaded from LDS is divergent to the compiler, and an
     // epoch-derived scalar offset of a buffer load / store (the parity buffer) then becomes a waterfall loop around EVERY
     // granule access (v_readfirstlane + v_cmp + s_and_saveexec + branch, 16 of them per step of lstm_cluster)
     XchTicket t;
     t.base = (unsigned)__builtin_amdgcn_readfirstlane((int)lds2[0]);
     t.launch = (unsigned)__builtin_amdgcn_readfirstlane((int)lds2[1]);
-    t.arrival = arrival;
     t.same_xcd = __builtin_amdgcn_readfirstlane((int)lds2[2]) != 0 && __builtin_amdgcn_readfirstlane((int)lds2[3]) == 0;
     return t;
 }
@@ -224,7 +267,7 @@ __device__ __forceinline__ void xch_settle(unsigned* status, const XchTicket& t,
         unsigned spins = 0;
         bool ok = true;
         while (xch_status_load(word) != expect) {
-            if (++spins > (1u << 20)) {
+            if (++spins > kXchSpinLimit) {   // (the arrival count only: no poison check here)
                 ok = false;
                 break;
             }
