@@ -8,6 +8,8 @@
 //                         N = output channels.  Roofline: MFMA (2*K*N FLOP per pixel).
 //   convlstm_gates_kernel i,f,c,o gates + cell update on z (pixels, 4F)                         - HBM
 //   softmax_lastdim       channel softmax                                                       - HBM
+#include <stdio.h>
+
 #include "fov_common.h"
 
 namespace fov {
@@ -390,6 +392,11 @@ int conv2d_fwd2(const float* x, long ldx, long ldb, int C, const float* x2, long
         FOV_CONV_LAUNCH(4, 4, 2, grid);
     }
 #undef FOV_CONV_LAUNCH
+    if (env_knobs().dbg_trace)      // which of the twelve kernels behind the one launch name: a test asserts the form it reached
+        fprintf(stderr, "[fov trace] conv2d form: igemm tile %s avec %d bvec %d segments %d dil %d epilogue16 %d\n",
+                N <= 32 ? "N<=32" : N <= 64 ? "N<=64" : "N>64", (int)avec, (int)bvec, x2 ? 2 : 1, g.dil,
+                // the kernel's own vec_out: four column tiles per wave, N % 4 == 0 and y, add, bias on 16-byte boundaries
+                (int)(N > 32 && (N & 3) == 0 && ((((uintptr_t)y) | ((uintptr_t)add) | ((uintptr_t)bias)) & 15) == 0));
     return launch_check("conv2d_igemm");
 }
 
@@ -437,6 +444,9 @@ int convlstm_cell_fwd(const float* x, long ldx, long ldb, int C, const float* h_
     else FOV_CELL_SHAPES(FOV_ACT_SIGMOID);
 #undef FOV_CELL_SHAPES
 #undef FOV_CELL_LAUNCH
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] convlstm_cell form: igemm tile %s avec %d bvec %d segments %d dil %d\n", F <= 8 ? "F<=8" : F <= 16 ? "F<=16" : "F>16",
+                (int)avec, (int)bvec, h_prev ? 2 : 1, g.dil);
     return launch_check("convlstm_cell");
 }
 

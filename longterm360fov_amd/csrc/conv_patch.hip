@@ -20,6 +20,7 @@
 //     WAVES_N = 1 -> 11 row tiles, BN = 32 (the 30-channel output layer).
 // Blocks are ordered n-block major: all resident workgroups work on the same BN columns, whose weights (3.3 MB at C = 512)
 // stay in every XCD's L2; an input map is read once per n-block (16 times for the 512 -> 1024 layer instead of 25 x 8).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "fov_common.h"
@@ -273,6 +274,8 @@ int launch_conv_patch(const float* x, long ldx, long ldb, const float* w, const 
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.nblocks * B)), dim3(256), lds, stream, g);
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] conv2d form: patch waves_n %d step %s cvec %d\n", N > 32 ? 2 : 1, fixed ? "fixed" : "run-time", (C & 3) == 0 ? 1 : 0);
     return launch_check("conv2d_patch");
 }
 

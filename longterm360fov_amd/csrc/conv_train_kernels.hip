@@ -7,6 +7,8 @@
 //   conv_weight_transpose_kernel W'(kh-1-i, kw-1-j, n, c) = W(i, j, c, n): with it the data gradient of a
 //                                'same' convolution is the forward kernel on dz (dx = conv2d_same(dz, W'))
 //   softmax_bwd_kernel           dy = p * (dp - sum_c dp*p)                                              - HBM
+#include <stdio.h>
+
 #include "fov_common.h"
 
 namespace fov {
@@ -357,6 +359,9 @@ int conv2d_wgrad(const float* x, long ldx, const float* dz, float* dw, int B, in
     else if (variant == 3) FOV_WGRAD_LAUNCH(4, 2, 4);
     else FOV_WGRAD_LAUNCH(4, 4, 2);
 #undef FOV_WGRAD_LAUNCH
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] conv2d_wgrad form: tap-wise variant %d split %d tiles_per_split %ld avec %d bvec %d\n", variant, split, tps,
+                (int)avec, (int)bvec);
     int rc = launch_check("conv_wgrad");
     if (rc || !via_scratch) return rc;
     return splitk_reduce(scratch, dw, (long)wn, split, accumulate, stream);

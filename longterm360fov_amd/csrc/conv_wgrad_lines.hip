@@ -15,6 +15,8 @@
 // the next map, ...).  Operands: A = x [pixel][channel], B = dz [pixel][output], both k-slow as they lie; LDS pixel strides of 16 or
 // 48 (mod 64) floats put the four pixel rows of an MFMA step on disjoint banks.  Waves split the (tap, tile) products: tiles if
 // there are four or more, taps otherwise.  Split over the maps (blockIdx.z), partial slices, fixed-order reduce (deterministic).
+#include <stdio.h>
+
 #include "fov_common.h"
 
 namespace fov {
@@ -288,6 +290,9 @@ int conv_wgrad_lines(const float* x, long ldx, const float* dz, float* dw, int B
         else FOV_WLINES(4, 2, 3);
     }
 #undef FOV_WLINES
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] conv2d_wgrad form: lines %dx%d ks %d %s avec %d bvec %d slices %ld maps_per_slice %d\n", MI, NI, ks,
+                g.colmode ? "columns" : "rows", (int)g.avec, (int)g.bvec, split, g.maps_per_split);
     if (int rc = launch_check("conv_wgrad_lines")) return rc;
     if (!via_scratch) return FOV_OK;
     return splitk_reduce(scratch, dw, (long)wn, (int)split, accumulate, stream);

@@ -20,6 +20,8 @@
 // Two workgroups per CU (patch 63 KB at 64 channels): one stages / stores while the other multiplies.
 // The accumulation order per output (taps outer, 16-channel blocks, k-steps) equals conv2d_igemm_kernel's whenever C is
 // a multiple of 16, so the two forms agree bit for bit there (tests/test_gpu_convlstm.py).
+#include <stdio.h>
+
 #include "fov_common.h"
 
 namespace fov {
@@ -213,6 +215,8 @@ int launch_patch_t(const CellPatchArgs& g, int act, size_t lds, hipStream_t stre
     int rc = ensure_dynamic_lds((const void*)kern, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(g.B * g.groups)), dim3(256), lds, stream, g);
+    if (env_knobs().dbg_trace)
+        fprintf(stderr, "[fov trace] convlstm_cell form: patch F %d CB %d rows %d groups %d\n", g.F, CB, g.rows, g.groups);
     return launch_check("convlstm_cell_patch");
 }
 
