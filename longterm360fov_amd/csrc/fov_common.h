@@ -136,7 +136,9 @@ bool operand_fits_31bit(const char* what, int B, long ldb, const void* x2, long 
 // after a launch: FOV_OK, or FOV_ERR_LAUNCH with the error "<what> launch: <hip string>"; under FOV_DBG_TRACE=1 the line
 // "[fov trace] launched: <what>" first - every launch names its kernel form, so a test can assert the form a launcher chose
 int launch_check(const char* what);
-int check_launch(const char* what);   // the same (the training helpers' older name)
+// FOV_OK when `need` bytes fit the 16-byte aligned workspace (need = 0: no workspace wanted), else FOV_ERR_WORKSPACE with its message
+int check_ws(void* ws, size_t have, size_t need);
+inline bool valid_act(int act) { return act == FOV_ACT_SIGMOID || act == FOV_ACT_HARD_SIGMOID; }
 // wide-input layer, H = 256, 96 < F <= 256 (lstm_wide.hip)
 bool wide_shape_ok(int F, int H);
 bool wide_narrow_preferred(int B, int F, int H);
@@ -152,6 +154,11 @@ size_t stepwise_workspace_floats(int B, int T, int H);
 int launch_stepwise(const LstmParams& p, float* ws, size_t ws_floats, hipStream_t stream);
 
 constexpr size_t kStatusBytes = 256;  // head of every workspace: status words (layout: xch_common.h)
+// the status words and, behind them, the granule area of the exchanging kernels
+inline void bind_workspace(LstmParams& p, void* workspace) {
+    p.status = (unsigned*)workspace;
+    p.xch = (unsigned long long*)((char*)workspace + kStatusBytes);
+}
 
 // ConvLSTM building blocks (conv_kernels.hip)
 // dil: dilation of the taps over x (Keras dilation_rate; 'same' padding grows with it); the second segment of conv2d_fwd2 / the
@@ -236,7 +243,7 @@ struct MixDecParams {
     int B, T_out, O, num_groups, num_tiles;
     int epoch_span;          // epochs this launch may consume (xch_common.h)
 };
-// one-shot marks 'the packed K2 of this workspace is current' (fov_api.hip)
+// one-shot marks 'the packed K2 of this workspace is current' (api_state.hip)
 void prepack_mark(void* workspace, const float* K2);
 bool prepack_consume(void* workspace, const float* K2);
 void prepack_forget(void* workspace);                    // the workspace was zero-filled: no packed copy in it any more

@@ -456,7 +456,7 @@ int gemm_f32(GemmArgs g, int accumulate, float* scratch, size_t scratch_floats, 
     else { FOV_GEMM_MODES(4, 4, 2) }
 #undef FOV_GEMM_MODES
 #undef FOV_GEMM_LAUNCH
-    int rc = check_launch("gemm_f32");
+    int rc = launch_check("gemm_f32");
     if (rc || !via_scratch) return rc;
     return reduce_or_defer(deferred, scratch, c_final, (long)mn, split, accumulate, stream, "splitk_reduce");
 }
@@ -558,7 +558,7 @@ int skinny_tn(const float* S, long ss, int ns, const float* Wd, long ldw, int nw
         FOV_SKINNY(1); FOV_SKINNY(2); FOV_SKINNY(3); FOV_SKINNY(4); FOV_SKINNY(5); FOV_SKINNY(6); FOV_SKINNY(7); FOV_SKINNY(8);
     }
 #undef FOV_SKINNY
-    int rc = check_launch("skinny_tn");
+    int rc = launch_check("skinny_tn");
     if (rc) return rc;
     rc = reduce_or_defer(deferred, scratch, out, (long)n, (int)chunks, accumulate, stream, "skinny_reduce");
     return rc ? rc : 1;

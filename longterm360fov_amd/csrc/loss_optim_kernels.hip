@@ -594,7 +594,7 @@ static unsigned* loss_ticket_of(hipStream_t stream) {
 // a loss asked for without a ticket slot (or by a kernel that takes none): the blocks' partials added by a launch of its own
 static int sum_partials(const float* part, float* out, int n, float scale, hipStream_t stream) {
     hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, stream, part, out, n, scale);
-    return check_launch("sum_scale");
+    return launch_check("sum_scale");
 }
 
 // Body of the two entries below (`name`: the entry's error prefix and trace label).  weight: on the gradient AND the loss
@@ -613,7 +613,7 @@ static int mse_dense_grad_body(const char* name, const float* y, const float* ta
     hipLaunchKernelGGL(mse_dense_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, target, dpre, scratch, n,
                        weight / (float)n, activation, tmB, tmT, O, ticket, loss, weight / (float)n,
                        fused_db ? scratch + ((blocks + 3) & ~3L) : nullptr, fused_db ? db : nullptr, fused_db ? dbO : 0);
-    int rc = check_launch(name);
+    int rc = launch_check(name);
     if (rc) return rc;
     if (db && !fused_db) {   // (no ticket slot, wide or time-major head: the column-sum launches)
         if (dbO < 1 || n % dbO) { set_error("%s: db needs the head's width", name); return FOV_ERR_INVALID; }
@@ -655,7 +655,7 @@ int dense_mse_head(const float* hs, const float* W, const float* b, const float*
     if (chunks <= HD_MAXB) {      // one launch: the last block to finish adds the partials
         hipLaunchKernelGGL(dense_mse_head_kernel, dim3((unsigned)chunks), dim3(256), lds, stream, hs, W, b, target, y, dX, scratch, dW, db, loss,
                            (int)N, H, O, activation, scale, ticket, 1, 1);
-        return check_launch("dense_mse_head");
+        return launch_check("dense_mse_head");
     }
     // many rows: about one block per CU walking several tiles (two per CU measured no faster: 39.9 vs 37.1 us at 30 720 rows), then the reduce launch
     const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
@@ -663,12 +663,12 @@ int dense_mse_head(const float* hs, const float* W, const float* b, const float*
     const int blocks = (chunks + cpb - 1) / cpb;
     hipLaunchKernelGGL(dense_mse_head_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, hs, W, b, target, y, dX, scratch, dW, db, loss,
                        (int)N, H, O, activation, scale, ticket, cpb, 0);
-    rc = check_launch("dense_mse_head");
+    rc = launch_check("dense_mse_head");
     if (rc) return rc;
     const int NE = H * O + O + 1;
     hipLaunchKernelGGL(dense_mse_head_reduce_kernel, dim3((unsigned)((NE + 15) / 16)), dim3(256), 0, stream, scratch, blocks, NE, H * O, O, dW, db,
                        loss, scale);
-    return check_launch("dense_mse_head_reduce");
+    return launch_check("dense_mse_head_reduce");
 }
 
 int gauss_nll_grad(const float* mu, const float* var, const float* y, float* loss, float* dmu, float* dvar, int B, int Ty,
@@ -678,7 +678,7 @@ int gauss_nll_grad(const float* mu, const float* var, const float* y, float* los
     unsigned* ticket = loss ? loss_ticket_of(stream) : nullptr;
     hipLaunchKernelGGL(gauss_nll_kernel, dim3(B), dim3(256), 0, stream, mu, var, y, scratch, dmu, dvar, B, Ty, fps, scale, ticket, loss,
                        scale / (float)B);
-    int rc = check_launch("gauss_nll");
+    int rc = launch_check("gauss_nll");
     if (rc || !loss || ticket) return rc;
     return sum_partials(scratch, loss, B, scale / (float)B, stream);
 }
@@ -689,7 +689,7 @@ int cce_grad(const float* p, const float* t, float* dp, float* loss, long n_pix,
     const long blocks = (n_pix + 255) / 256;
     if ((size_t)blocks > scratch_floats) { set_error("categorical_crossentropy_grad: scratch too small"); return FOV_ERR_WORKSPACE; }
     hipLaunchKernelGGL(cce_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, t, dp, scratch, n_pix, C);
-    int rc = check_launch("cce_grad");
+    int rc = launch_check("cce_grad");
     if (rc || !loss) return rc;
     return sum_partials(scratch, loss, (int)blocks, 1.0f / (float)n_pix, stream);
 }
@@ -699,7 +699,7 @@ int xyz_sum1_grad(const float* p, float* dp, float* reg, long n_pix, int C, floa
     const long blocks = (n_pix + 255) / 256;
     if ((size_t)blocks > scratch_floats) { set_error("xyz_sum1_grad: scratch too small"); return FOV_ERR_WORKSPACE; }
     hipLaunchKernelGGL(xyz_sum1_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, dp, scratch, n_pix, C);
-    int rc = check_launch("xyz_sum1");
+    int rc = launch_check("xyz_sum1");
     if (rc || !reg) return rc;
     return sum_partials(scratch, reg, (int)blocks, 0.5f / (float)n_pix, stream);
 }
@@ -708,7 +708,7 @@ int sample_refeed_fwd(const float* mu, const float* var, const float* noise, flo
                       int layout, hipStream_t stream) {
     if (B <= 0) return FOV_OK;
     hipLaunchKernelGGL(sample_refeed_fwd_kernel, dim3(B), dim3(64), 0, stream, mu, var, noise, x, ldx, fps, std_mode, layout);
-    return check_launch("sample_refeed_fwd");
+    return launch_check("sample_refeed_fwd");
 }
 
 int sample_refeed_bwd(const float* dx, long ldx, const float* var, const float* noise, float* dmu, float* dvar, int B, int fps,
@@ -716,7 +716,7 @@ int sample_refeed_bwd(const float* dx, long ldx, const float* var, const float* 
     if (B <= 0) return FOV_OK;
     hipLaunchKernelGGL(sample_refeed_bwd_kernel, dim3(B), dim3(64), 0, stream, dx, ldx, var, noise, dmu, dvar, fps, std_mode, layout,
                        accumulate);
-    return check_launch("sample_refeed_bwd");
+    return launch_check("sample_refeed_bwd");
 }
 
 // x *= s (fallback gradient weighting of the trainers that do not fold the weight into their loss kernel)
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, long 
 int scale_inplace(float* x, long n, float s, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, n, s);
-    return check_launch("scale");
+    return launch_check("scale");
 }
 
 // y = act(x): 1 tanh, 2 relu, 3 exp (heads of mycode/lstm.py:321-337); in place allowed
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const float* x, float* y, 
 int act_fwd(const float* x, float* y, long n, int activation, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
     hipLaunchKernelGGL(act_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, y, n, activation);
-    return check_launch("act_fwd");
+    return launch_check("act_fwd");
 }
 
 // out = base + dy * act'(y)   (act' = 1 - y^2 for tanh, [y > 0] for relu, y for exp, 1 for linear); base may be NULL; out may alias base/dy
@@ -755,7 +755,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
 int act_bwd(const float* dy, const float* y, const float* base, float* out, long n, int activation, hipStream_t stream) {
     if (n <= 0) return FOV_OK;
     hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dy, y, base, out, n, activation);
-    return check_launch("act_bwd");
+    return launch_check("act_bwd");
 }
 
 // Keras-2.2 optimizers on one flat buffer (oracle/fov_oracle.py::adam_step / rmsprop_step)
@@ -861,7 +861,7 @@ int adam_step(float* p, const float* g, float* m, float* v, long n, float lr_t, 
         hipLaunchKernelGGL(adam_kernel4, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, p, g, m, v, n, lr_t, b1, b2, eps, w[0], w[1], w[2], applied);
     else
         hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, n, lr_t, b1, b2, eps, w[0], w[1], w[2], applied);
-    return check_launch("adam");
+    return launch_check("adam");
 }
 
 int rmsprop_step(float* p, const float* g, float* a, long n, float lr, float rho, float eps, const unsigned* const* guards,
@@ -870,7 +870,7 @@ int rmsprop_step(float* p, const float* g, float* a, long n, float lr, float rho
     if (int rc = defer_touch(g, (size_t)n, stream)) return rc;
     const unsigned* const* w = guards ? guards : kNoGuards;
     hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, a, n, lr, rho, eps, w[0], w[1], w[2], applied);
-    return check_launch("rmsprop");
+    return launch_check("rmsprop");
 }
 
 int rmsprop_tf_step(float* p, const float* g, float* ms, long n, float lr, float decay, float eps, float clip,
@@ -879,7 +879,7 @@ int rmsprop_tf_step(float* p, const float* g, float* ms, long n, float lr, float
     if (int rc = defer_touch(g, (size_t)n, stream)) return rc;
     const unsigned* const* w = guards ? guards : kNoGuards;
     hipLaunchKernelGGL(rmsprop_tf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, ms, n, lr, decay, eps, clip, w[0], w[1], w[2], applied);
-    return check_launch("rmsprop_tf");
+    return launch_check("rmsprop_tf");
 }
 
 }  // namespace fov

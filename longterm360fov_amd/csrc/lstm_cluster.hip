@@ -1122,10 +1122,8 @@ __global__ __launch_bounds__(256, 1) void lstm_cluster_fused_kernel(LstmParams p
 // CUs of the CURRENT device (cached per device ordinal: a process may drive several GPUs)
 int device_cu_count() {
     static std::atomic<int> cus[64];    // (threads that race on the first use store the same value)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = cus[dev].load(std::memory_order_relaxed);
-    if (n == 0) {
+    int dev = 0, n = 256;               // no device (the size queries answer on a machine without a GPU): an MI355X's count
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && (n = cus[dev].load(std::memory_order_relaxed)) == 0) {
         hipDeviceProp_t prop;
         n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
         cus[dev].store(n, std::memory_order_relaxed);

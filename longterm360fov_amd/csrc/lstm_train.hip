@@ -130,7 +130,7 @@ int launch_stepwise(const LstmParams& p, float* ws, size_t ws_floats, hipStream_
         float* res = p.reserve ? p.reserve + (size_t)t * 5 * H : nullptr;
         hipLaunchKernelGGL(pointwise, pgrid, dim3(256), 0, stream, zx + (size_t)t * 4 * H, (long)T * 4 * H, zrp, p.b, cprev, cbuf,
                            hout, ldh, res, (long)T * 5 * H, last ? p.hT : nullptr, last ? p.cT : nullptr, B, H);
-        rc = check_launch("lstm_pointwise_fwd");
+        rc = launch_check("lstm_pointwise_fwd");
         if (rc) return rc;
         hprev = hout;
         ldhp = ldh;
@@ -379,7 +379,7 @@ int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0
         const auto pointwise = act == FOV_ACT_HARD_SIGMOID ? lstm_bwd_pointwise<FOV_ACT_HARD_SIGMOID> : lstm_bwd_pointwise<FOV_ACT_SIGMOID>;
         for (int t = T - 1; t >= 0; --t) {
             hipLaunchKernelGGL(pointwise, pgrid, dim3(256), 0, stream, reserve, c0, dhs, dh_rec, dc, dz, B, T, H, t);
-            int rc = check_launch("lstm_bwd_pointwise");
+            int rc = launch_check("lstm_bwd_pointwise");
             if (rc) return rc;
             // dh_rec (B,H) = dz_t (B,4H) . R^T :  A(m,k) = dz[m][t][k], B(k,n) = R[n][k]
             rc = gemm_f32(gemm_nt(dz + (size_t)t * 4 * H, (long)T * 4 * H, R, 4 * H, dh_rec, H, B, H, 4 * H), 0, scratch, scratch_floats, stream);
@@ -588,7 +588,7 @@ int mix_head_wgrad(const float* h2, const float* dpre_p, const float* others, co
         default: set_error("mix_head_wgrad: O <= 8"); return FOV_ERR_UNSUPPORTED;
     }
 #undef FOV_HEADW
-    int rc = check_launch("mix_head_wgrad");
+    int rc = launch_check("mix_head_wgrad");
     if (rc) return rc;
     return reduce_or_defer(deferred, scratch, out, (long)n, (int)chunks, accumulate, stream, "mix_head_wgrad reduce");
 }

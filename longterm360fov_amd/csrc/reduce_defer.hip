@@ -139,7 +139,7 @@ int defer_flush_locked(DeferState& st, hipStream_t stream) {
     t.count = 0; t.blocks = 0;
     // the arena is NOT rewound here: a caller may flush on one stream (its products run on a side stream) and go on recording
     // on another - slices are written once per begin ... end, what does not fit any more is reduced at once
-    return check_launch("splitk_reduce_batch");
+    return launch_check("splitk_reduce_batch");
 }
 void defer_close_locked(int i) {
     g_defer[i] = g_defer[g_defer_open - 1];
@@ -236,7 +236,7 @@ int reduce_or_defer(bool deferred, const float* part, float* out, long n, int S,
         hipLaunchKernelGGL(splitk_reduce_kernel<true>, splitk_reduce_grid((size_t)n, true), dim3(256), 0, stream, part, out, n, S, accumulate);
     else
         hipLaunchKernelGGL(splitk_reduce_kernel<false>, splitk_reduce_grid((size_t)n), dim3(256), 0, stream, part, out, n, S, accumulate);
-    return check_launch(what);
+    return launch_check(what);
 }
 
 int splitk_reduce(const float* part, float* out, long n, int S, int accumulate, hipStream_t stream) {
@@ -317,7 +317,7 @@ int colsum(const float* x, float* out, long rows, int cols, int accumulate, floa
         hipLaunchKernelGGL(colsum_partial_kernel, dim3((cols + 255) / 256, chunks), dim3(256), 0, stream, x, scratch, rows,
                            cols, rpc > 0 ? rpc : 1);
     }
-    int rc = check_launch("colsum_partial");
+    int rc = launch_check("colsum_partial");
     if (rc) return rc;
     return reduce_or_defer(deferred, scratch, out, (long)cols, chunks, accumulate, stream, "colsum_reduce");
 }
