@@ -296,7 +296,8 @@ def selffed_decoder_fwd(x0, K, R, b, W, bd, T, h0=None, c0=None, r=None, act="si
     """The self-fed one-layer decoder (FoV_seq2seq_no_teac_forc.py:96-118) unrolled T times in one launch: x0 (B,O), the state
     (h0, c0) (B,H) or None for zeros, y_t = dact(h_t . W + bd) + r fed back as x_{t+1}.  -> (y (B,T,O), tapes), tapes = None
     without `tape`, else the trainer's time-major dict Hs, Cs (T+1,B,H), XA (T+1,B,O), A (T,B,O) (with r only), RES
-    (T,B,1,5,H).  No workspace."""
+    (T,B,1,5,H).  T = 0: no launch; row 0 of Hs, Cs, XA (the initial state, zeros without one, and x0) is written here.  No
+    workspace."""
     x0 = _dev(x0, "x0")
     B, O = x0.shape
     H = R.shape[0]
@@ -316,6 +317,12 @@ def selffed_decoder_fwd(x0, K, R, b, W, bd, T, h0=None, c0=None, r=None, act="si
                                              _ptr(_dev(b, "b")), _ptr(_dev(W, "W")), _ptr(_dev(bd, "bd")), _ptr(_dev(r, "r")),
                                              g("Hs"), g("Cs"), g("XA"), g("A"), g("RES"), _ptr(y), B, T, O, H, act_code(act),
                                              _ACT_CODES[dense_activation], _stream()))
+    if tp is not None and T == 0:      # the entry writes nothing without a step: row 0 of the tapes is the initial state and x0
+        for k, src in (("Hs", h0), ("Cs", c0), ("XA", x0)):
+            if src is None:
+                tp[k].zero_()
+            else:
+                tp[k][0].copy_(src)
     return y, tp
 
 

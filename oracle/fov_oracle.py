@@ -1728,3 +1728,185 @@ def regime_convlstm_reference(p, dt=np.float64, x=None, b=None, h=None, c=None):
     gates = np.concatenate([s(z[..., :F]), s(z[..., F:2 * F]), np.tanh(z[..., 2 * F:3 * F]), s(z[..., 3 * F:])], axis=-1).astype(dt)
     cn = gates[..., F:2 * F] * c + gates[..., :F] * gates[..., 2 * F:3 * F]
     return {"h": (gates[..., 3 * F:] * np.tanh(cn)).astype(dt), "c": cn.astype(dt), "gates": gates, "z": z}
+
+
+# --------------------------------------------------------------------------------------
+# The one-tile decoders (tests/test_tile_decoders_host.py, tests/test_gpu_tile_decoders.py): the 2- and 3-layer decode
+# (fov_stacked_seq2seq_decode_fwd) and the self-fed decoder with its BPTT (fov_selffed_decoder_fwd / _bwd) in the value regimes
+# above, references that keep every pre-activation, and a BPTT written out on GIVEN tapes.  The references take `mistake`: a
+# named way of being wrong on purpose (finite, plausible), with which the host tests show what the GPU checks can see.
+# --------------------------------------------------------------------------------------
+def regime_stacked_seq2seq(seed, regime, L, H, F_enc, F_dec, B, T_in, dtype=np.float32):
+    """L-layer target-only seq2seq (stacked_seq2seq_forward's keys) with every layer of both sides in `regime` (R1 / R2 / R3) and
+    a saturating head.  Layer 0 of each side as regime_seq2seq builds its layers; the layers above read a computed hidden state
+    (regime_layer(rng, H, H, regime, 0.5, xk=0.5)).  -> dict(w, enc (B,T_in,F_enc), dec0 (B,1,F_dec), act, regime) and, for R3,
+    regime_lstm's extreme rows on the encoder's last input feature: extreme, enc_calm (that feature zero in every row), and an edge
+    batch for the same weights under zero LSTM biases (w_edge): enc_edge / dec0_edge, whose second tile is all zero and whose rows
+    from 32 on hold inputs of order 1e-6."""
+    assert regime in ("R1", "R2", "R3")
+    rng = np.random.default_rng(seed)
+    w = {}
+    for side, F0, rms, xk in (("enc", F_enc, 1.0 / np.sqrt(3.0), None), ("dec", F_dec, 0.8, 0.25)):
+        for l in range(L):
+            lay = regime_layer(rng, F0, H, regime, rms, 1.0, None, dtype, xk=xk) if l == 0 else \
+                regime_layer(rng, H, H, regime, 0.5, 1.0, None, dtype, xk=0.5)
+            w["%s%d_K" % (side, l)], w["%s%d_R" % (side, l)], w["%s%d_b" % (side, l)] = lay
+    w["dense_W"], w["dense_b"] = _regime_head(rng, H, F_dec, dtype)
+    enc = rng.uniform(-1, 1, (B, T_in, F_enc)).astype(dtype)
+    dec0 = rng.uniform(-1, 1, (B, 1, F_dec)).astype(dtype)
+    p = {"w": w, "enc": enc, "dec0": dec0, "act": REGIME_ACT[regime], "regime": regime}
+    if regime == "R3":
+        assert B > 32 and F_enc >= 2 and T_in >= 2
+        rows = np.array([3, 9, 12])
+        p["extreme"] = rows
+        w["enc0_K"][F_enc - 1] = np.where(rng.random(4 * H) < 0.5, -1.0, 1.0)
+        enc[:, :, F_enc - 1] = 0
+        p["enc_calm"] = enc.copy()
+        for r, A, t0 in ((rows[0], 130.0, 0), (rows[1], 300.0, 0), (rows[2], 300.0, T_in // 2)):
+            enc[r, t0:, F_enc - 1] = A * (-1.0) ** np.arange(t0, T_in)
+        ee, de = p["enc_calm"].copy(), dec0.copy()
+        ee[16:32], de[16:32] = 0, 0
+        ee[32:] = rng.uniform(-1e-6, 1e-6, ee[32:].shape)
+        p["enc_edge"], p["dec0_edge"] = ee.astype(dtype), de
+        p["w_edge"] = {k: (np.zeros_like(v) if (k.endswith("_b") and k != "dense_b") else v) for k, v in w.items()}
+    return p
+
+
+STACKED_MISTAKES = ("feedback rows 0..3", "partial k-block dropped", "layer below one step late", "encoder state returned",
+                    "head bias of outputs 0..3")
+
+
+def stacked_decode_reference(w, enc, dec0, L, T_out, act, dt=np.float64, mistake=None):
+    """The stacked decode in dtype dt, pre-activations summed as the kernel does (bias, x . K, h . R)
+    -> dict(out (B,T_out,O), hT, cT (L,B,H), z_enc [l] (B,T_in,4H), z_dec [l] (B,T_out,4H), pre (B,T_out,O)).
+    mistake, one of STACKED_MISTAKES: the decoder's layer 0 contracts only input rows 0..3 of dec0_K; the encoder drops the partial
+    last 16-row block of x . enc0_K; a layer l >= 1 reads the layer below at the previous step; with T_out > 0 the returned states
+    are the encoder's; the head's outputs 4..7 take the bias of outputs 0..3."""
+    assert mistake is None or mistake in STACKED_MISTAKES
+    c_ = lambda a: np.asarray(a, dt)
+    w = {k: c_(v) for k, v in w.items()}
+    enc, dec0 = c_(enc), c_(dec0)
+    B, T_in, F = enc.shape
+    H, O = w["enc0_R"].shape[0], w["dense_W"].shape[1]
+    s = _rec_act(act)
+    h, c = [np.zeros((B, H), dt) for _ in range(L)], [np.zeros((B, H), dt) for _ in range(L)]
+    late = mistake == "layer below one step late"
+
+    def stack_step(x, side, rows, zs):
+        for l in range(L):
+            K, R, b = (w["%s%d_%s" % (side, l, k)] for k in "KRb")
+            below = h[l - 1] if l else None
+            inp = x if l == 0 else (prev_below if late else below)
+            prev_below = h[l].copy()                      # this layer's h before its update: what the layer above reads when late
+            k_rows = rows if l == 0 else H
+            z = (b + inp[:, :k_rows] @ K[:k_rows]) + h[l] @ R
+            c[l] = s(z[:, H:2 * H]) * c[l] + s(z[:, :H]) * np.tanh(z[:, 2 * H:3 * H])
+            h[l] = s(z[:, 3 * H:]) * np.tanh(c[l])
+            zs[l].append(z)
+
+    z_enc, z_dec = [[] for _ in range(L)], [[] for _ in range(L)]
+    f_rows = F // 16 * 16 if mistake == "partial k-block dropped" else F
+    for t in range(T_in):
+        stack_step(enc[:, t], "enc", f_rows, z_enc)
+    enc_state = (np.stack(h), np.stack(c))
+    bd = w["dense_b"].copy()
+    if mistake == "head bias of outputs 0..3":
+        bd[4:] = bd[:max(O - 4, 0)]
+    o_rows = min(O, 4) if mistake == "feedback rows 0..3" else O
+    y, out, pre = dec0[:, 0], [], []
+    for _ in range(T_out):
+        stack_step(y, "dec", o_rows, z_dec)
+        a = h[L - 1] @ w["dense_W"] + bd
+        y = np.tanh(a)
+        out.append(y); pre.append(a)
+    st = lambda v, n: np.stack(v, axis=1) if v else np.zeros((B, 0, n), dt)
+    hT, cT = enc_state if (mistake == "encoder state returned" and T_out > 0) else (np.stack(h), np.stack(c))
+    return {"out": st(out, O), "hT": hT, "cT": cT, "z_enc": [st(z, 4 * H) for z in z_enc], "z_dec": [st(z, 4 * H) for z in z_dec],
+            "pre": st(pre, O)}
+
+
+RELU_HEAD_BIAS = (0.3, -0.3, 0.1, -0.1, 0.6, -0.6)     # a relu head about half of whose outputs are exactly zero
+
+
+def regime_selffed(seed, regime, H, O, B, T, dact, residual, dtype=np.float32):
+    """The self-fed decoder's inputs with the layer in `regime` (R1 / R2 / R4; it reads a fed-back output: xk = 0.25) -> dict(K, R,
+    b, W, bd, x0 (B,O), h0, c0 (B,H; None in R4: the zero state), r (B,O) or None, dloss (T,B,O), act, dact, regime).  The tanh
+    head is _regime_head's; the relu head has gain 1 and a bias of both signs."""
+    assert regime in ("R1", "R2", "R4") and dact in ("tanh", "relu")
+    rng = np.random.default_rng(seed)
+    K, R, b = regime_layer(rng, O, H, regime, 0.8, 1.0, None, dtype, xk=0.25)
+    if dact == "tanh":
+        W, bd = _regime_head(rng, H, O, dtype)
+    else:
+        W = rng.normal(0.0, 1.0 / np.sqrt(H), (H, O)).astype(dtype)
+        bd = np.resize(np.array(RELU_HEAD_BIAS), O).astype(dtype)
+    h0, c0 = (None, None) if regime == "R4" else regime_state(rng, B, b, regime, dtype)
+    p = {"K": K, "R": R, "b": b, "W": W, "bd": bd, "x0": rng.uniform(-1, 1, (B, O)).astype(dtype), "h0": h0, "c0": c0,
+         "r": rng.uniform(-0.5, 0.5, (B, O)).astype(dtype) if residual else None,
+         "dloss": rng.standard_normal((T, B, O)).astype(dtype), "act": REGIME_ACT[regime], "dact": dact, "regime": regime}
+    return p
+
+
+def selffed_forward(x0, h0, c0, r, K, R, b, W, bd, T, act, dact, dt=np.float64):
+    """fov_selffed_decoder_fwd in dtype dt (z = b + x . K + h . R, this order) -> the tapes in the kernel's layouts: y (B,T,O), Hs,
+    Cs (T+1,B,H), XA (T+1,B,O), A (T,B,O), RES (T,B,1,5,H), and the pre-activations z (T,B,4H), pre (T,B,O)."""
+    c_ = lambda a: None if a is None else np.asarray(a, dt)
+    x, h, c, r, K, R, b, W, bd = (c_(a) for a in (x0, h0, c0, r, K, R, b, W, bd))
+    B, O = x.shape
+    H = R.shape[0]
+    h = np.zeros((B, H), dt) if h is None else h
+    c = np.zeros((B, H), dt) if c is None else c
+    s = _rec_act(act)
+    Hs, Cs, XA, A, RES, zs, pres = [h], [c], [x], [], [], [], []
+    for _ in range(T):
+        z = (b + x @ K) + h @ R
+        i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
+        c = f * c + i * g
+        h = o * np.tanh(c)
+        pre = h @ W + bd
+        a = np.tanh(pre) if dact == "tanh" else np.maximum(pre, 0)
+        x = a if r is None else a + r
+        Hs.append(h); Cs.append(c); XA.append(x); A.append(a); zs.append(z); pres.append(pre)
+        RES.append(np.stack([i, f, g, o, c], axis=1)[:, None])
+    st = lambda v, shape: np.stack(v).astype(dt) if v else np.zeros(shape, dt)
+    XA = np.stack(XA).astype(dt)
+    return {"y": np.ascontiguousarray(np.swapaxes(XA[1:], 0, 1)), "Hs": np.stack(Hs).astype(dt), "Cs": np.stack(Cs).astype(dt), "XA": XA,
+            "A": st(A, (0, B, O)), "RES": st(RES, (0, B, 1, 5, H)), "z": st(zs, (0, B, 4 * H)), "pre": st(pres, (0, B, O))}
+
+
+SELFFED_MISTAKES = ("feedback gradient dropped", "c_prev one step late", "tanh derivative from XA", "dc0 without f")
+
+
+def selffed_backward(tapes, dloss, K, R, W, act, dact, mistake=None):
+    """fov_selffed_decoder_bwd written out on GIVEN tapes (Cs, XA, RES and, when the forward had a residual term, A; else a_t =
+    XA[t + 1]), in the dtype of dloss: the gate derivative from the stored gate, the relu derivative from a_t > 0, c_{t-1} = Cs[t].
+    -> dict(DY, DPRE (T,B,O), DZ (T,B,4H), dx0 (B,O), dh0, dc0 (B,H)).
+    mistake, one of SELFFED_MISTAKES: dy_t = dloss_t alone; c_{t-1} read from Cs[t + 1]; a_t of the tanh derivative read from
+    XA[1:] although A is given; dc0 without the last multiplication by f."""
+    assert mistake is None or mistake in SELFFED_MISTAKES
+    dt = dloss.dtype
+    c_ = lambda a: np.asarray(a, dt)
+    K, R, W, Cs, XA = c_(K), c_(R), c_(W), c_(tapes["Cs"]), c_(tapes["XA"])
+    T, B, O = dloss.shape
+    H = R.shape[0]
+    RES = c_(tapes["RES"]).reshape(T, B, 5, H)
+    aout = c_(tapes["A"]) if tapes.get("A") is not None else XA[1:]
+    if mistake == "tanh derivative from XA" and dact == "tanh":
+        aout = XA[1:]
+    DY, DPRE, DZ = np.zeros((T, B, O), dt), np.zeros((T, B, O), dt), np.zeros((T, B, 4 * H), dt)
+    dx, dhR, dc = np.zeros((B, O), dt), np.zeros((B, H), dt), np.zeros((B, H), dt)
+    for t in range(T - 1, -1, -1):
+        dy = dloss[t] if mistake == "feedback gradient dropped" else dloss[t] + dx
+        a = aout[t]
+        dpre = dy * ((a > 0).astype(dt) if dact == "relu" else (1 - a * a))
+        dh = dhR + dpre @ W.T
+        i, f, g, o, c = (RES[t, :, q] for q in range(5))
+        c_prev = Cs[t + 1] if mistake == "c_prev one step late" else Cs[t]
+        tc = np.tanh(c)
+        dcv = dc + dh * o * (1 - tc * tc)
+        dz = np.concatenate([dcv * g * _rec_act_grad(i, act), dcv * c_prev * _rec_act_grad(f, act), dcv * i * (1 - g * g),
+                             dh * tc * _rec_act_grad(o, act)], axis=1)
+        dc = dcv if (mistake == "dc0 without f" and t == 0) else dcv * f
+        DY[t], DPRE[t], DZ[t] = dy, dpre, dz
+        dhR, dx = dz @ R.T, dz @ K.T
+    return {"DY": DY, "DPRE": DPRE, "DZ": DZ, "dx0": dx, "dh0": dhR, "dc0": dc}
