@@ -156,6 +156,22 @@ __device__ __forceinline__ void mfma_f32(f32x4& acc, float a, float w, int pos) 
         else asm volatile(FOV_MFMA_STR("s_nop 1\n\t", "\n\ts_nop 7\n\ts_nop 3") : "+v"(acc) : "v"(a), "v"(w));
     }
 }
+// Three-source form, acc = a . w + c: the first MFMA on an accumulator of a step takes the splatted bias as its C operand,
+// so the accumulators are not initialised by copy (eight v_mov_b64 in front of every step's first run, none of them hidden
+// behind an fp32 MFMA).  D is an early-clobber output: D and C must be the same registers or fully disjoint.  C was
+// written long before, so the MFMA owes the two opening wait states only where its A operand is VALU-written (`a_fresh`:
+// the decoder's y fragment).  It never closes a run: a k-block has four k-steps and only the first one takes this form.
+#define FOV_MFMA_C_STR(pre) pre "v_mfma_f32_16x16x4_f32 %0, %1, %2, %3"
+template <bool W_AGPR>
+__device__ __forceinline__ void mfma_f32_c(f32x4& acc, float a, float w, const f32x4& c, bool a_fresh) {
+    if constexpr (W_AGPR) {
+        if (a_fresh) asm volatile(FOV_MFMA_C_STR("s_nop 1\n\t") : "=&v"(acc) : "v"(a), "a"(w), "v"(c));
+        else asm volatile(FOV_MFMA_C_STR("") : "=&v"(acc) : "v"(a), "a"(w), "v"(c));
+    } else {
+        if (a_fresh) asm volatile(FOV_MFMA_C_STR("s_nop 1\n\t") : "=&v"(acc) : "v"(a), "v"(w), "v"(c));
+        else asm volatile(FOV_MFMA_C_STR("") : "=&v"(acc) : "v"(a), "v"(w), "v"(c));
+    }
+}
 // position of MFMA number i of a run of n: the flags say whether the run opens / closes an MFMA sequence
 __host__ __device__ constexpr int mf_pos(bool first_run, bool last_run, bool is_first, bool is_last) {
     return ((first_run && is_first) ? MF_FIRST : 0) | ((last_run && is_last) ? MF_LAST : 0);
@@ -260,44 +276,60 @@ __device__ __forceinline__ void load_dec_small(float (&bias)[4], f32x4 (&kb)[2],
 // the run-ahead reads of the last iterations stay inside LDS (their values are never used) and
 // every block offset is an instruction immediate instead of VALU work.  The last k-block is peeled: its last MFMA
 // carries the closing wait states.
-template <bool FIRST, bool LAST>
-__device__ __forceinline__ void input_proj(f32x4 (&acc)[4], const float* arow, const float* sKw, int nq, int lane) {
-    if (nq <= 0) return;
+template <bool FIRST, bool LAST, bool CINIT = false>
+__device__ __forceinline__ void input_proj(f32x4 (&acc)[4], const float* arow, const float* sKw, int nq, int lane, const f32x4* c0 = nullptr) {
+    if (nq <= 0) {
+        if constexpr (CINIT) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) acc[g] = c0[g];
+        }
+        return;
+    }
     const float* bl = sKw + lane * 4;
     f32x4 a = *(const f32x4*)arow;
     f32x4 b0 = *(const f32x4*)bl;
     f32x4 b1 = *(const f32x4*)(bl + 256);
-    if (FIRST) asm volatile("s_nop 1" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));   // (rare path; the first MFMA sits in a loop or in the peeled block)
-    for (int q = 0; q < nq - 1; ++q) {
-        const f32x4 an = *(const f32x4*)(arow + 16 * (q + 1));
+    if (FIRST && !CINIT) asm volatile("s_nop 1" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));   // (rare path; the first MFMA sits in a loop or in the peeled block)
+    // one k-block; CINIT: block 0 is peeled as well, its first k-step takes c0 as the C operand
+    auto block = [&](const int q, auto first_c, auto last_c) __attribute__((always_inline)) {
+        constexpr bool C0 = decltype(first_c)::value, LB = decltype(last_c)::value;
         const float* bq = bl + q * 1024;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const f32x4 bn = *(const f32x4*)(bq + (s + 2) * 256);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) mfma_f32<false>(acc[g], a[s], b0[g], MF_MID);
+            for (int g = 0; g < 4; ++g) {
+                if (C0 && s == 0) mfma_f32_c<false>(acc[g], a[s], b0[g], c0[g], false);
+                else mfma_f32<false>(acc[g], a[s], b0[g], mf_pos(false, LB && LAST, false, s == 3 && g == 3));
+            }
             b0 = b1;
             b1 = bn;
         }
+    };
+    int q = 0;
+    if constexpr (CINIT) {
+        // (one copy of block 0 for nq == 1 and nq > 1: it carries the closing wait states of a LAST run either way - twelve
+        // idle cycles in step 0 of a layer whose input is wider than 16 and not 90-odd)
+        const f32x4 an = *(const f32x4*)(arow + 16);   // (nq == 1: a run-ahead read inside the tile's spare tail)
+        block(0, BoolC<true>{}, BoolC<true>{});
+        if (nq == 1) return;
+        a = an;
+        q = 1;
+    }
+    for (; q < nq - 1; ++q) {
+        const f32x4 an = *(const f32x4*)(arow + 16 * (q + 1));
+        block(q, BoolC<false>{}, BoolC<false>{});
         a = an;
     }
-    const float* bq = bl + (nq - 1) * 1024;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const f32x4 bn = *(const f32x4*)(bq + (s + 2) * 256);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) mfma_f32<false>(acc[g], a[s], b0[g], mf_pos(false, LAST, false, s == 3 && g == 3));
-        b0 = b1;
-        b1 = bn;
-    }
+    block(nq - 1, BoolC<false>{}, BoolC<true>{});
 }
 
 // The same with the block count known at compile time: every LDS offset is an instruction immediate and the operand
 // registers are renamed instead of rotated - the run-time loop above carries two v_mov_b64 and two v_add_u32 per 16
 // MFMAs, and on this chip a VALU instruction is never hidden behind an fp32 MFMA (tools/microbench/mfma_f32_overlap.hip:
 // 32 -> 46 cycles for ONE v_fma_f32 in an MFMA gap).
-template <int NQC, bool FIRST, bool LAST>
-__device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* arow, const float* sKw, int lane) {
+template <int NQC, bool FIRST, bool LAST, bool CINIT = false>
+__device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* arow, const float* sKw, int lane, const f32x4* c0 = nullptr) {
     const float* bl = sKw + lane * 4;
     f32x4 a = *(const f32x4*)arow;
     f32x4 b0 = *(const f32x4*)bl;
@@ -311,33 +343,39 @@ __device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* a
             f32x4 bn = b1;
             if (4 * q + s + 2 < 4 * NQC) bn = *(const f32x4*)(bl + (4 * q + s + 2) * 256);
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                mfma_f32<false>(acc[g], a[s], b0[g], mf_pos(FIRST, LAST, q == 0 && s == 0, q == NQC - 1 && s == 3 && g == 3));
+            for (int g = 0; g < 4; ++g) {
+                if (CINIT && q == 0 && s == 0) mfma_f32_c<false>(acc[g], a[s], b0[g], c0[g], false);
+                else mfma_f32<false>(acc[g], a[s], b0[g], mf_pos(FIRST && !CINIT, LAST, q == 0 && s == 0, q == NQC - 1 && s == 3 && g == 3));
+            }
             b0 = b1;
             b1 = bn;
         }
         a = an;
     }
 }
-template <bool FIRST, bool LAST>
-__device__ __forceinline__ void input_proj_any(f32x4 (&acc)[4], const float* arow, const float* sKw, int nq, int lane) {
-    if (nq == 6) input_proj_fixed<6, FIRST, LAST>(acc, arow, sKw, lane);   // F in (80, 96]: the reference's 90-wide input (FoV_seq2seq.py:24-26)
-    else input_proj<FIRST, LAST>(acc, arow, sKw, nq, lane);
+template <bool FIRST, bool LAST, bool CINIT = false>
+__device__ __forceinline__ void input_proj_any(f32x4 (&acc)[4], const float* arow, const float* sKw, int nq, int lane, const f32x4* c0 = nullptr) {
+    if (nq == 6) input_proj_fixed<6, FIRST, LAST, CINIT>(acc, arow, sKw, lane, c0);   // F in (80, 96]: the reference's 90-wide input (FoV_seq2seq.py:24-26)
+    else input_proj<FIRST, LAST, CINIT>(acc, arow, sKw, nq, lane, c0);
 }
 
 // DECODE: acc += y(16 x 8) . Kslice, y fragment and the two K blocks already in registers (y is VALU-written: the run
-// always opens with the two wait states)
-template <bool LAST>
-__device__ __forceinline__ void input_proj_reg(f32x4 (&acc)[4], f32x4 y4, const f32x4 (&kb)[2]) {
+// always opens with the two wait states).  CINIT: acc = c0 + y . Kslice (step 0, where this run opens the accumulation)
+template <bool LAST, bool CINIT = false>
+__device__ __forceinline__ void input_proj_reg(f32x4 (&acc)[4], f32x4 y4, const f32x4 (&kb)[2], const f32x4* c0 = nullptr) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) mfma_f32<false>(acc[g], y4[s], kb[s][g], mf_pos(true, LAST, s == 0, s == 1 && g == 3));
+        for (int g = 0; g < 4; ++g) {
+            if (CINIT && s == 0) mfma_f32_c<false>(acc[g], y4[s], kb[s][g], c0[g], true);
+            else mfma_f32<false>(acc[g], y4[s], kb[s][g], mf_pos(true, LAST, s == 0, s == 1 && g == 3));
+        }
 }
 
 // acc += h tile (LDS, columns in rotated slice order) . register-resident R blocks [J0, J1)
-template <int H, int J0, int J1, bool FIRST, bool LAST>
-__device__ __forceinline__ void recurrent(f32x4 (&acc)[4], const float* hrow, const float (&wR)[H / 16][4][4]) {
+// CINIT: the run opens the step's accumulation, acc = c0 + ... (mfma_f32_c)
+template <int H, int J0, int J1, bool FIRST, bool LAST, bool CINIT = false>
+__device__ __forceinline__ void recurrent(f32x4 (&acc)[4], const float* hrow, const float (&wR)[H / 16][4][4], const f32x4* c0 = nullptr) {
     if (J0 >= J1) return;
     f32x4 a = *(const f32x4*)(hrow + 16 * J0);
 #pragma unroll
@@ -347,8 +385,10 @@ __device__ __forceinline__ void recurrent(f32x4 (&acc)[4], const float* hrow, co
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int g = 0; g < 4; ++g)
-                mfma_f32<true>(acc[g], a[s], wR[j][s][g], mf_pos(FIRST, LAST, j == J0 && s == 0, j == J1 - 1 && s == 3 && g == 3));
+            for (int g = 0; g < 4; ++g) {
+                if (CINIT && j == J0 && s == 0) mfma_f32_c<true>(acc[g], a[s], wR[j][s][g], c0[g], false);
+                else mfma_f32<true>(acc[g], a[s], wR[j][s][g], mf_pos(FIRST && !CINIT, LAST, j == J0 && s == 0, j == J1 - 1 && s == 3 && g == 3));
+            }
         a = an;
     }
 }
@@ -701,9 +741,15 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         FOV_PSTAMP(6);
 
         // ---- pre-activations of step 0 that need no remote data ----
+        // The splatted bias is the C operand of the first MFMA on each accumulator of every step (mfma_f32_c).  Opaque to
+        // hipcc from here on: sixteen registers written once per tile, never re-made in front of an MFMA that reads them.
+        f32x4 bias4[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bias4[g] = (f32x4){bias[g], bias[g], bias[g], bias[g]};
+        asm volatile("" : "+v"(bias4[0]), "+v"(bias4[1]), "+v"(bias4[2]), "+v"(bias4[3]));
         f32x4 acc[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = (f32x4){bias[g], bias[g], bias[g], bias[g]};
+        for (int g = 0; g < 4; ++g) acc[g] = bias4[g];   // (dead where a run below opens with bias4 as its C operand)
         if (ZX && steps > 0) {
 #pragma unroll
             for (int g = 0; g < 4; ++g)
@@ -712,8 +758,9 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                     acc[g][r] = bias[g] + __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(zxrs, zxoff + (unsigned)((r * p.T * 4 * H + g * H) * 4), 0, 0));
         }
         if (steps > 0) {
-            if (LAYER) input_proj_any<true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane);
-            else input_proj_reg<true>(acc, y4, kb);
+            if constexpr (ZX) input_proj_any<true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane);   // (nq = 0: nothing)
+            else if constexpr (LAYER) input_proj_any<true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane, bias4);
+            else input_proj_reg<true, true>(acc, y4, kb, bias4);
             // a zero initial state (the encoder of every seq2seq call): h_0 . R is exactly 0 - its 4H/16 k-blocks (256 of the
             // 352 MFMAs of an encoder step at H = 256) are skipped here and at the top of step 0
             if constexpr (F2) {
@@ -796,23 +843,32 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                 __builtin_amdgcn_sched_barrier(0);
                 f32x2 ysum;
                 if constexpr (NYG > 0) {
+                    // The check of the loads issued above stands in front of the spin loop, not at its head, as for the gather of
+                    // h below (same sequence of checks and sweeps): at the head the vy registers were loop-carried and hipcc
+                    // moved all sixteen between register sets on the healthy path, which takes no turn of the loop.  The
+                    // scheduling barrier above keeps the compares, and the wait they carry, behind the MFMA run.
                     unsigned spins = 0;
-                    while (true) {
+                    auto ytags_ok = [&]() __attribute__((always_inline)) -> bool {
                         bool ok = true;
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) ok = ok && (vy[q].y == epoch) && (vy[q].w == epoch);
-                        if (__all(ok)) break;
-                        if (xch_wait_expired(++spins, p.status)) {
-                            if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }      // (seen by every wave behind this step's barrier 2)
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(1);
-                        asm volatile("" ::: "memory");
+                        return __all(ok);
+                    };
+                    if (!ytags_ok()) {
+                        while (true) {
+                            if (xch_wait_expired(++spins, p.status)) {
+                                if (lane == 0) { xch_give_up(p.status); sFlag[0] = 1; }      // (seen by every wave behind this step's barrier 2)
+                                break;
+                            }
+                            __builtin_amdgcn_s_sleep(1);
+                            asm volatile("" ::: "memory");
 #pragma unroll
-                        for (int q = 0; q < NYG; ++q) vy[q] = __builtin_amdgcn_raw_buffer_load_b128(yrs, ygoff, yso + (unsigned)(q * 1024), 16);
-                        // (a statement of its own behind the unrolled loop: where that loop closed the spin loop's body hipcc handed
-                        // its unroll request on to the SPIN loop and made sixteen copies of it in the step)
-                        asm volatile("");
+                            for (int q = 0; q < NYG; ++q) vy[q] = __builtin_amdgcn_raw_buffer_load_b128(yrs, ygoff, yso + (unsigned)(q * 1024), 16);
+                            // (a statement of its own behind the unrolled loop: where that loop closed the spin loop's body hipcc handed
+                            // its unroll request on to the SPIN loop and made sixteen copies of it in the step)
+                            asm volatile("");
+                            if (ytags_ok()) break;
+                        }
                     }
                     f32x2 P[NYG];
 #pragma unroll
@@ -901,10 +957,17 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             // ISSUED (its ~0.9 us round trip runs under the MFMAs that follow), then the own-slice
             // k-blocks of h_t . R, and only then are the granule tags checked.
             if (more) {
+                // the bias is no copy into the accumulators: it is the C operand of the run that opens the accumulation -
+                // x_{t+1} . K here, the decoder's first own-slice k-block below.  A ZX layer starts from zr (bias + zx).
+                const float* xa = sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4;
+                if constexpr (ZX) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) acc[g] = ZX ? zr[g] : (f32x4){bias[g], bias[g], bias[g], bias[g]};
-                if constexpr (LAYER && ST) input_proj_fixed<6, true, false>(acc, sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4, sKw, lane);
-                else if (LAYER) input_proj_any<true, false>(acc, sX + ((t + 1) % 3) * BT * LDX + n * LDX + 4 * g4, sKw, nq, lane);
+                    for (int g = 0; g < 4; ++g) acc[g] = zr[g];
+                } else if constexpr (LAYER && ST) {
+                    input_proj_fixed<6, true, false, true>(acc, xa, sKw, lane, bias4);
+                } else if constexpr (LAYER) {
+                    input_proj_any<true, false, true>(acc, xa, sKw, nq, lane, bias4);
+                }
             }
             FOV_STAMP(5);
             u32x4g v[NG > 0 ? NG : 1];
@@ -914,7 +977,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             constexpr int GJ = LAYER ? 0 : 1;
             // (one branch around both MFMA runs: where two `if (more)` met, hipcc copied the accumulators between them)
             if (more) {
-                recurrent<H, 0, GJ, true, false>(acc, hrow, wR);
+                recurrent<H, 0, GJ, true, false, true>(acc, hrow, wR, bias4);   // (DECODE only: GJ = 0 is no run)
                 if (do_xch) {
 #pragma unroll
                     for (int j = 0; j < NG; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(xrs, goff[j], xsoff, 16);
@@ -1022,20 +1085,31 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                     u32x4g vy[NYG];
                     const unsigned yso = (epoch & 1u) * YPAR_BYTES;
                     unsigned spins = 0;
-                    while (true) {
+                    // (the same shape as the waits inside the step: first sweep and check in front of the spin loop)
+                    auto ysweep = [&]() __attribute__((always_inline)) {
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) vy[q] = __builtin_amdgcn_raw_buffer_load_b128(yrs, ygoff, yso + (unsigned)(q * 1024), 16);
+                    };
+                    auto ytags_ok = [&]() __attribute__((always_inline)) -> bool {
                         bool ok = true;
 #pragma unroll
                         for (int q = 0; q < NYG; ++q) ok = ok && (vy[q].y == epoch) && (vy[q].w == epoch);
-                        if (__all(ok)) break;
-                        if (xch_wait_expired(++spins, p.status)) {
-                            if (lane == 0) xch_give_up(p.status);
-                            got = false;
-                            break;
+                        return __all(ok);
+                    };
+                    ysweep();
+                    if (!ytags_ok()) {
+                        while (true) {
+                            if (xch_wait_expired(++spins, p.status)) {
+                                if (lane == 0) xch_give_up(p.status);
+                                got = false;
+                                break;
+                            }
+                            __builtin_amdgcn_s_sleep(1);
+                            asm volatile("" ::: "memory");
+                            ysweep();
+                            asm volatile("");   // (a statement of its own behind the unrolled loop, see the step's spin loops)
+                            if (ytags_ok()) break;
                         }
-                        __builtin_amdgcn_s_sleep(1);
-                        asm volatile("" ::: "memory");
                     }
                     f32x2 P[NYG];
 #pragma unroll
