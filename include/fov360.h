@@ -252,6 +252,19 @@ int fov_lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1
                             int B, int H, int accumulate,
                             void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
+/* The same for the layers of a STACK (Fov_seq2seq_2layers.py:232-272,332-343: the encoder stack or the decoder stack under
+ * model.fit): 1 <= L <= 4 layers that share the batch and the width, arrays of L entries - x[l] (B,T[l],F[l]), hs[l] (B,T[l],H),
+ * h0[l] (B,H) or NULL, dz[l] (B,T[l],4H) -> dK[l] (F[l],4H), dR[l] (H,4H), db[l] (4H), any of which may be NULL.  Where the
+ * few-row form takes every layer (B T[l] <= 640 rows, H <= 512 a multiple of 16, 16-byte aligned dz and gradients) all of them are
+ * ONE launch; otherwise the call makes one fov_lstm_seq_wgrad-equivalent call per layer.  Either way the results equal the
+ * per-layer calls' bit for bit.  Another L: FOV_ERR_UNSUPPORTED.  workspace: max over the layers of
+ * fov_lstm_seq_bwd_workspace_bytes(B, T[l], F[l], H). */
+int fov_lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs,
+                              const float* const* h0, const float* const* dz,
+                              float* const* dK, float* const* dR, float* const* db,
+                              int B, int H, int accumulate,
+                              void* workspace, size_t workspace_bytes, fov_stream_t stream);
+
 /* A HIP stream of a given priority for such side work: priority < 0 high, 0 normal, > 0 low (clamped to the device's range).
  * Work enqueued on a LOW-priority stream yields the compute units to the caller's stream whenever both have workgroups ready:
  * weight-gradient products put there fill the gaps of the persistent recurrence kernels instead of delaying their launch.
@@ -465,6 +478,52 @@ int fov_selffed_decoder_bwd(const float* Cs, const float* XA, const float* A, co
                             const float* K, const float* R, const float* W,
                             float* DY, float* DPRE, float* DZ, float* dx0, float* dh0, float* dc0,
                             int B, int T, int O, int H, int act, int dact, int a_from_A, fov_stream_t stream);
+
+/* The 2- and 3-layer target-only seq2seq model's TRAINING graph as ONE launch per direction (replaces the layer-by-layer
+ * graph of mycode/Fov_seq2seq_2layers.py:232-272 under model.fit / model.predict, :332-343, and 3layers.py's): fp32 on the matrix
+ * core, exact expf / tanhf, pre-activations summed in the order bias, x . K, h . R.  One workgroup owns a 16-sequence tile for
+ * every layer and step: no exchange, no workspace header, no library state, nothing to wait on; rows of a ragged last tile beyond
+ * B read zeros and store nothing.  Weights as arrays of L pointers, Keras layout: enc_K[0] (F_enc,4H), dec_K[0] (F_dec,4H),
+ * every other K and every R (H,4H), b (4H).
+ *
+ * fov_stacked_seq2seq_train_fwd - replaces the forward of :232-272.  The L-layer encoder over enc_in (B,T_in,F_enc) from zero
+ * states (layer l reads layer l-1's h_t), then the L-layer teacher-forced decoder over dec_in (B,T_out,F_dec), decoder layer l
+ * seeded with encoder layer l's (h_T, c_T).  The Dense head is not part of it.  Outputs, each of which may be NULL and is then
+ * not written, in the layouts of the per-layer entry points - slice l is a valid operand of fov_lstm_seq_bwd / _wgrad:
+ *   enc_hs (L,B,T_in,H), enc_res (L,B,T_in,5,H)     h_t and the activated i, f, g, o and c_t (fov_lstm_seq_fwd_train's reserve)
+ *   dec_hs (L,B,T_out,H), dec_res (L,B,T_out,5,H)   the same of the decoder stack
+ *   dec_top (B,T_out,H)                             the top decoder layer's h_t alone: with every tape NULL, the inference forward
+ *   hT, cT (L,B,H)                                  the encoder's final states (zeros with T_in = 0)
+ * T_in = 0: the decoder starts from zero states; T_out = 0: the encoder stack alone.
+ *
+ * fov_stacked_seq2seq_train_bwd - replaces Keras autodiff through both stacks (:332-343).  From the reserves, cT, every R_l, K_l of
+ * the layers l >= 1 (entry 0 of enc_K / dec_K is not read) and dhs_top (B,T_out,H), the gradient that reaches the top decoder
+ * layer's h_t from the head: BPTT through the decoder stack, top layer first,
+ *   dh_{l,t} = (dx_{l+1,t}, or dhs_top at the top) + dz_{l,t+1} . R_l^T;  the cell's pointwise backward with the gate derivative
+ *   taken from the stored gate;  dx_{l,t} = dz_{l,t} . K_l^T for l >= 1;
+ * then each decoder layer's (dh_0, dc_0) enters the matching encoder layer as (dh_T, dc_T) and the encoder stack is walked the
+ * same way.  Outputs: dec_dz (L,B,T_out,4H), enc_dz (L,B,T_in,4H); the weight gradients are products over these tapes
+ * (fov_lstm_seq_wgrad_layers), the h tapes and hT are read there only.  scratch: fov_stacked_seq2seq_train_bwd_scratch_bytes
+ * bytes of plain memory (the dx hand-off between layers), nothing is kept in it between calls.
+ *
+ * Shapes: H = 32 or 64 (a narrower model zero-padded by the caller, which is exact), L = 2 or 3, 1 <= F_enc <= 96,
+ * 1 <= F_dec <= 8, any B, T_in, T_out >= 0; anything else is FOV_ERR_UNSUPPORTED, decided before any pointer is looked at and
+ * before any HIP call.  A missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 launches nothing.
+ * fov_stacked_seq2seq_train_supported is the shape rule as arithmetic (no device query), and 0 under FOV_NO_STACKED_TRAIN=1 (the
+ * caller's per-layer path stays: A/B timing, cross-check); the two entries do not read the knob. */
+int fov_stacked_seq2seq_train_supported(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);
+size_t fov_stacked_seq2seq_train_bwd_scratch_bytes(int B, int T_in, int T_out, int H);
+int fov_stacked_seq2seq_train_fwd(const float* enc_in, const float* dec_in,
+                                  const float* const* enc_K, const float* const* enc_R, const float* const* enc_b,
+                                  const float* const* dec_K, const float* const* dec_R, const float* const* dec_b,
+                                  float* enc_hs, float* enc_res, float* dec_hs, float* dec_res, float* dec_top, float* hT, float* cT,
+                                  int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L, int act, fov_stream_t stream);
+int fov_stacked_seq2seq_train_bwd(const float* enc_res, const float* dec_res, const float* cT, const float* dhs_top,
+                                  const float* const* enc_R, const float* const* enc_K,
+                                  const float* const* dec_R, const float* const* dec_K,
+                                  float* enc_dz, float* dec_dz,
+                                  int B, int T_in, int T_out, int H, int L, int act,
+                                  void* scratch, size_t scratch_bytes, fov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Teacher-forced training-graph forward: encoder, decoder seeded with the encoder state over
@@ -696,7 +755,7 @@ int fov_rmsprop_step_guarded(float* params, const float* grads, float* accum, in
  * instead of one per product; results are bit-identical.  In-stream order is kept for writes made through this library (a
  * later product over a pending range flushes first); a caller that reads or writes the gradient buffer by other means
  * between _begin and _end calls _flush before.  Writers covered: fov_lstm_seq_bwd(_bf16), fov_lstm_seq_wgrad,
- * fov_lstm_seq_wgrad_pair, fov_lstm_stack2_bwd, fov_dense_bwd(_bf16), fov_wgrad_fused, fov_colsum, fov_mix_head_wgrad,
+ * fov_lstm_seq_wgrad_pair, fov_lstm_seq_wgrad_layers, fov_lstm_stack2_bwd, fov_dense_bwd(_bf16), fov_wgrad_fused, fov_colsum, fov_mix_head_wgrad,
  * fov_mse_dense_grad_db / _w (db), fov_dense_mse_head, fov_mlp_head_bwd, fov_tf_head_bwd, fov_conv2d_wgrad,
  * fov_conv2d_dilated_wgrad, fov_conv2d_wgrad_bf16, in every kernel form and in their empty-shape zeroing; readers covered (they
  * flush over the gradients they read): fov_adam_step(_guarded), fov_rmsprop_step(_guarded), fov_rmsprop_tf_step(_guarded).

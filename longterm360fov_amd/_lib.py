@@ -58,6 +58,10 @@ SIGNATURES = {
     "fov_selffed_decoder_supported": (_I, [_I] * 4),
     "fov_selffed_decoder_fwd": (_I, [_P] * 15 + [_I] * 6 + [_P]),
     "fov_selffed_decoder_bwd": (_I, [_P] * 14 + [_I] * 7 + [_P]),
+    "fov_stacked_seq2seq_train_supported": (_I, [_I] * 7),
+    "fov_stacked_seq2seq_train_bwd_scratch_bytes": (_SZ, [_I] * 4),
+    "fov_stacked_seq2seq_train_fwd": (_I, [_P] * 15 + [_I] * 8 + [_P]),
+    "fov_stacked_seq2seq_train_bwd": (_I, [_P] * 10 + [_I] * 6 + [_P, _SZ, _P]),
     "fov_seq2seq_tf_workspace_bytes": (_SZ, [_I] * 7),
     "fov_seq2seq_tf_fwd": (_I, [_P] * 11 + [_I] * 8 + [_P, _SZ, _P]),
     "fov_meanvar_xyz": (_I, [_P, _P, ctypes.c_int64, _I, _P]),
@@ -125,6 +129,7 @@ SIGNATURES = {
     "fov_lstm_seq_wgrad": (_I, [_P] * 7 + [_I] * 6 + [_P, _SZ, _P]),
     "fov_lstm_seq_wgrad_pair_one_launch": (_I, [_I] * 4),
     "fov_lstm_seq_wgrad_pair": (_I, [_P] * 7 + [_I] * 2 + [_P] * 7 + [_I] * 2 + [_I] * 3 + [_P, _SZ, _P]),
+    "fov_lstm_seq_wgrad_layers": (_I, [_I] + [_P] * 9 + [_I] * 3 + [_P, _SZ, _P]),
     "fov_stream_create": (_I, [_I, ctypes.POINTER(ctypes.c_void_p)]),
     "fov_stream_destroy": (_I, [_P]),
     "fov_conv2d_dilated_fwd": (_I, [_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P] + [_I] * 9 + [_P]),

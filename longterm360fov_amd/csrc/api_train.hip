@@ -39,6 +39,31 @@ int fov_lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1
                                (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
+int fov_lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
+                              const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
+                              void* workspace, size_t workspace_bytes, fov_stream_t stream) {
+    if (L < 1 || L > 4) {
+        set_error("fov_lstm_seq_wgrad_layers: 1 to 4 layers (got %d)", L);
+        return FOV_ERR_UNSUPPORTED;
+    }
+    bool ok = B >= 0 && H > 0 && x && F && T && hs && h0 && dz && dK && dR && db;
+    size_t need = 0;
+    for (int l = 0; ok && l < L; ++l) {
+        ok = T[l] >= 0 && F[l] > 0 && !(B > 0 && T[l] > 0 && (!dz[l] || (dK[l] && !x[l]) || (dR[l] && !hs[l])));
+        if (ok) {
+            const size_t n = fov_lstm_seq_bwd_workspace_bytes(B, T[l], F[l], H);
+            need = n > need ? n : need;
+        }
+    }
+    if (!ok) {
+        set_error("fov_lstm_seq_wgrad_layers: invalid argument");
+        return FOV_ERR_INVALID;
+    }
+    if (int rc = check_ws(workspace, workspace_bytes, need)) return rc;
+    return lstm_seq_wgrad_layers(L, x, F, T, hs, h0, dz, dK, dR, db, B, H, accumulate, (float*)workspace, workspace_bytes / sizeof(float),
+                                 (hipStream_t)stream);
+}
+
 size_t fov_dense_bwd_workspace_bytes(int N, int In, int Out) {
     if (N <= 0 || In <= 0 || Out <= 0) return 256;
     size_t a = (size_t)(Out <= 8 ? 1024 : 64) * In * Out, b = (size_t)256 * Out, c = (size_t)(N + 255) / 256 + 64;

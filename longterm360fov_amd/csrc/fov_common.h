@@ -96,7 +96,7 @@ int launch_wide16_s2s(const LstmParams& p, hipStream_t stream);
 int launch_cluster(const LstmParams& p, bool decode, hipStream_t stream);
 int launch_cluster_decoder(const LstmParams& p, hipStream_t stream);   // MODE_DECODE alone, from (p.h0, p.c0)
 bool cluster_shape_ok(int F, int H);
-bool stacked_s2s_shape_ok(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);   // lstm_stacked_s2s.hip: the L-layer seq2seq decode as one launch
+bool stacked_s2s_shape_ok(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);   // lstm_stacked_s2s.hip, lstm_stacked_train.hip: the L-layer seq2seq decode / training graph as one launch per direction
 bool selffed_shape_ok(int B, int T, int O, int H);   // lstm_selffed.hip: the self-fed one-layer decoder's unroll (forward with tapes, BPTT) as one launch each
 size_t cluster_workspace_bytes(int B, int H);
 int cluster_num_groups(int B, int H);
@@ -117,6 +117,7 @@ struct EnvKnobs {
     int no_wgrad_bf16_tiles;   // FOV_NO_WGRAD_BF16_TILES=1: the bf16 Conv2D weight gradient on its plain kernel (tests; conv_wgrad_bf16.hip)
     int no_stacked_decode;     // FOV_NO_STACKED_DECODE=1: fov_stacked_seq2seq_decode_supported -> 0, the stacked model's decode stays a host loop (tests / A-B timing)
     int no_selffed_fused;      // FOV_NO_SELFFED_FUSED=1: fov_selffed_decoder_supported -> 0, the self-fed decoder's unroll stays a host loop (tests / A-B timing)
+    int no_stacked_train;      // FOV_NO_STACKED_TRAIN=1: fov_stacked_seq2seq_train_supported -> 0, the stacked model trains and predicts layer by layer (tests / A-B timing)
 };
 const EnvKnobs& env_knobs();
 void env_reload();
@@ -284,6 +285,11 @@ bool lstm_seq_wgrad_pair_one_launch(int B, int T1, int T2, int H);
 int lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1, const float* dz1, float* dK1, float* dR1, float* db1, int T1, int F1,
                         const float* x2, const float* hs2, const float* h0_2, const float* dz2, float* dK2, float* dR2, float* db2, int T2, int F2,
                         int B, int H, int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream);
+// all weight gradients of up to four layers that share the batch and the width (a stack): one launch where the few-row form takes
+// every layer, else one lstm_seq_wgrad per layer - the same bits either way
+int lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
+                          const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
+                          float* scratch, size_t scratch_floats, hipStream_t stream);
 bool wgrad_group_takes(int B, int T, int H);   // wgrad_group.hip: few rows - every (product, output tile) one workgroup, one launch
 int wgrad_group_layers(int L, const float* const* x, const int* F, const float* const* hs, const float* const* h0, const float* const* dz,
                        float* const* dK, float* const* dR, float* const* db, int B, int T, int H, int accumulate, hipStream_t stream);

@@ -300,6 +300,22 @@ int lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1, co
     return lstm_seq_wgrad(x2, hs2, h0_2, dz2, dK2, dR2, db2, B, T2, F2, H, accumulate, 0, scratch, scratch_floats, stream);
 }
 
+// Weight gradients of the layers of a STACK (Fov_seq2seq_2layers.py:232-272: up to four layers that share the batch and the width,
+// each with its own input width and time length) from their dz tapes.  One launch (wgrad_rows_kernel) when the few-row form takes
+// every layer; else a lstm_seq_wgrad per layer.  A workgroup of that kernel owns one output tile of one problem whatever else
+// shares the launch, so both ways give the bits of the per-layer calls.
+int lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
+                          const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
+                          float* scratch, size_t scratch_floats, hipStream_t stream) {
+    bool rows_form = B > 0;
+    for (int l = 0; l < L && rows_form; ++l) rows_form = T[l] > 0 && lstm_seq_wgrad_rows(0, B, T[l], F[l], H, dz[l], dK[l], dR[l], db[l]);
+    if (rows_form) return wgrad_rows_layers(L, x, F, T, hs, h0, dz, dK, dR, db, B, H, accumulate, stream);
+    for (int l = 0; l < L; ++l)
+        if (int rc = lstm_seq_wgrad(x[l], hs[l], h0[l], dz[l], dK[l], dR[l], db[l], B, T[l], F[l], H, accumulate, 0, scratch, scratch_floats, stream))
+            return rc;
+    return FOV_OK;
+}
+
 // BPTT of one layer.  dz:(B,T,4H) is an output (kept: the caller may need it for dx of the layer
 // below).  dK,dR,db are overwritten (accumulate = 0) or added to (accumulate = 1).
 int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0, const float* c0, const float* hs,

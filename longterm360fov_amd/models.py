@@ -1006,6 +1006,7 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
                  seed=None, impl="auto", device="cuda"):
         from .training import stacked_weight_order
         self.F, self.O, self.H, self.L = int(num_encoder_tokens), int(num_decoder_tokens), int(latent_dim), int(num_layers)
+        self.num_encoder_tokens, self.num_decoder_tokens = self.F, self.O      # (the names the dataset methods read)
         self.recurrent_activation = recurrent_activation or cfg.recurrent_activation
         rng = np.random.default_rng(seed)
         w = {}
@@ -1034,21 +1035,42 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
     def predict(self, x, batch_size=None, verbose=0):
         """[encoder_input (N,T_in,F), decoder_input (N,T_out,O)] -> (N,T_out,O), teacher-forced graph (:332)."""
         enc, dec_in = _as_f32(x[0]), _as_f32(x[1])
-        ops, dw = self._device()
-
-        def run(e, inp):
-            states = self._encode(ops, dw, e)
-            for l in range(self.L):
-                inp, _, _ = ops.lstm_seq(inp, dw["dec%d_K" % l], dw["dec%d_R" % l], dw["dec%d_b" % l], states[l][0], states[l][1],
-                                         act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
-            return ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
-        y = self._predict_chunks([enc, dec_in], batch_size, run, (dec_in.shape[1], self.O))
+        self._device()
+        y = self._predict_chunks([enc, dec_in], batch_size, self.predict_device, (dec_in.shape[1], self.O))
         self._ws.check()
         return y
 
     predict_on_batch = predict
 
-    FUSED_WIDTHS = (32, 64)      # run widths of the one-launch decode (lstm_stacked_s2s.hip)
+    # One workgroup per 16-sequence tile loses to the per-layer kernels' several per tile at large batches: from this many
+    # sequences on predict and the trainer keep the per-layer path (profiles/stacked_train_time.jsonl: ahead 4x to 6x at B = 64,
+    # behind by up to 8 % at B = 1024; nothing in between was measured)
+    FUSED_MAX_BATCH = 1024
+
+    def predict_device(self, e, d, fused=None):
+        """predict on device tensors: e (B,T_in,F), d (B,T_out,O) -> (B,T_out,O) device tensor.  Both stacks in ONE launch
+        (ops.stacked_seq2seq_train_fwd without tapes) plus the Dense head when the padded width is at most 64, the batch is below
+        FUSED_MAX_BATCH and the library supports the shape; a launch per layer for wider models, other depths, impl != 'auto',
+        empty sequences and under FOV_NO_STACKED_TRAIN=1.  fused True / False is the timing tool's A/B switch: the one launch
+        at any batch it supports / the per-layer loop."""
+        ops, dw = self._device()
+        B, T_in, T_out = e.shape[0], e.shape[1], d.shape[1]
+        want = B < self.FUSED_MAX_BATCH if fused is None else bool(fused)
+        fw, Hp = self._fused_weights(ops, dw) if (want and self.impl == "auto") else (None, None)
+        if fw is not None and T_in > 0 and T_out > 0 and ops.stacked_seq2seq_train_supported(B, T_in, T_out, e.shape[2], self.O, Hp, self.L):
+            top = ops.stacked_seq2seq_train_fwd(e, d, fw, self.L, act=self.recurrent_activation, tape=False)["top"]
+            return ops.dense(top, fw["dense_W"], fw["dense_b"], activation="tanh")
+        states, inp = self._encode(ops, dw, e), d
+        for l in range(self.L):
+            inp, _, _ = ops.lstm_seq(inp, dw["dec%d_K" % l], dw["dec%d_R" % l], dw["dec%d_b" % l], states[l][0], states[l][1],
+                                     act=self.recurrent_activation, impl=self.impl, workspace=self._ws)
+        return ops.dense(inp, dw["dense_W"], dw["dense_b"], activation="tanh")
+
+    # ---- fed from a TrajectoryDataset: the inputs Seq2SeqLSTM reads ----
+    _dataset_pick_user = False
+    _dataset_inputs = Seq2SeqLSTM._dataset_inputs
+
+    FUSED_WIDTHS = (32, 64)      # run widths of the one-launch kernels (lstm_stacked_s2s.hip, lstm_stacked_train.hip)
 
     def _fused_weights(self, ops, dw):
         """The weights at the one-launch decode's run width (zero-padded - exact, see pad_lstm), on the device; None when the
@@ -1107,9 +1129,16 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
         return y
 
     def _make_trainer(self, optimizer):
-        from .training import StackedSeq2SeqTrainer
-        return StackedSeq2SeqTrainer(self._w, self.L, act=self.recurrent_activation, impl=self.impl, optimizer=optimizer,
-                                     lr=self._lr, device=self.device)
+        """Up to width 64 a width that is neither 32 nor 64 trains zero-padded to the next of the two (exact: PaddedTrainer), where
+        the one-launch kernels run; wider models train as they are."""
+        from .training import PaddedTrainer, StackedSeq2SeqTrainer
+        make = lambda w: StackedSeq2SeqTrainer(w, self.L, act=self.recurrent_activation, impl=self.impl, optimizer=optimizer,
+                                               lr=self._lr, device=self.device)
+        Hp = padded_width(self.H, self.FUSED_WIDTHS)
+        if Hp is None or Hp == self.H:
+            return make(self._w)
+        hidden = tuple("%s%d_K" % (side, l) for side in ("enc", "dec") for l in range(1, self.L))
+        return PaddedTrainer(make, self._w, self.H, Hp, hidden_inputs=hidden)
 
 
 class OthersContextSeq2Seq(KerasModelSurface):

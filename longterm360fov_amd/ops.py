@@ -53,7 +53,7 @@ def _stream():
 _ENV_KNOBS = ("FOV_FORCE_SAFE_EXCHANGE", "FOV_TWO_LAUNCHES", "FOV_DBG_RESIDENT_LIMIT", "FOV_NO_CELL_PATCH", "FOV_NO_CONV_PATCH", "FOV_NO_WIDE16", "FOV_BWD_STEPPED",
               "FOV_NO_WGRAD_FUSION", "FOV_NO_DX_FUSION", "FOV_BWD_GROUPS4", "FOV_GEMM_BF16_NOREMAP", "FOV_GEMM_BF16_SPLIT", "FOV_GEMM_BF16_SHALLOW", "FOV_NO_WGRAD_GROUP", "FOV_NO_WIDE16_TRIO", "FOV_DBG_TRACE", "FOV_GEMM_VARIANT",
               "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES", "FOV_NO_STACKED_DECODE",
-              "FOV_NO_SELFFED_FUSED")
+              "FOV_NO_SELFFED_FUSED", "FOV_NO_STACKED_TRAIN")
 _env_seen = None
 # os.environ.get costs 0.7 us per key (encode, lookup, decode): 9 us for the knob list, paid at every workspace / scratch
 # fetch - 0.15 ms of a 0.3 ms training step at batch 32.  The mapping underneath (bytes -> bytes on POSIX) answers the
@@ -346,6 +346,73 @@ def selffed_decoder_bwd(tp, dloss, K, R, W, act="sigmoid", dense_activation="tan
     return o
 
 
+def stacked_seq2seq_train_supported(B, T_in, T_out, F_enc, F_dec, H, num_layers):
+    """Shapes fov_stacked_seq2seq_train_fwd / _bwd take (H = 32 or 64 at the run width, 2 or 3 layers, F_enc <= 96, F_dec <= 8, any
+    batch and lengths); False under FOV_NO_STACKED_TRAIN=1.  Arithmetic only: answers on a machine without a GPU."""
+    _sync_env()
+    return bool(_lib.lib().fov_stacked_seq2seq_train_supported(B, T_in, T_out, F_enc, F_dec, H, num_layers))
+
+
+def _stack_ptrs(w, side, L_, part):
+    return _PTR3(*([_ptr(_dev(w["%s%d_%s" % (side, l, part)], "%s%d_%s" % (side, l, part))) for l in range(L_)] + [None] * (3 - L_)))
+
+
+def stacked_seq2seq_train_fwd(enc_in, dec_in, w, num_layers, act="sigmoid", tape=True, out=None):
+    """The L-layer encoder and the L-layer teacher-forced decoder of Fov_seq2seq_2layers.py:232-272 / 3layers.py in one launch
+    (the Dense head is the caller's).  w: enc{l}_K/R/b, dec{l}_K/R/b at the run width.  tape=True -> dict enc_hs (L,B,T_in,H),
+    enc_res (L,B,T_in,5,H), dec_hs (L,B,T_out,H), dec_res (L,B,T_out,5,H), hT, cT (L,B,H); its `top` is dec_hs[L-1].  tape=False
+    -> dict with `top` (B,T_out,H) alone: the inference forward.  out: a dict of preallocated tensors under the same names.
+    No workspace."""
+    enc_in, dec_in = _dev(enc_in, "enc_in"), _dev(dec_in, "dec_in")
+    L_ = int(num_layers)
+    B, T_in, F_enc = enc_in.shape
+    B2, T_out, F_dec = dec_in.shape
+    H = w["enc0_R"].shape[0]
+    assert B2 == B
+    for side, f0 in (("enc", F_enc), ("dec", F_dec)):
+        for l in range(L_):
+            assert w["%s%d_K" % (side, l)].shape == (f0 if l == 0 else H, 4 * H) and w["%s%d_R" % (side, l)].shape == (H, 4 * H) \
+                and w["%s%d_b" % (side, l)].shape == (4 * H,), "%s%d" % (side, l)
+    shapes = {"enc_hs": (L_, B, T_in, H), "enc_res": (L_, B, T_in, 5, H), "dec_hs": (L_, B, T_out, H), "dec_res": (L_, B, T_out, 5, H),
+              "hT": (L_, B, H), "cT": (L_, B, H)} if tape else {"top": (B, T_out, H)}
+    t = {}
+    for k, s_ in shapes.items():
+        t[k] = torch.empty(s_, dtype=torch.float32, device=enc_in.device) if out is None or out.get(k) is None else out[k]
+        assert _dev(t[k], k).shape == s_, k
+    g = lambda k: _ptr(t.get(k))
+    check(_lib.lib().fov_stacked_seq2seq_train_fwd(_ptr(enc_in), _ptr(dec_in), _stack_ptrs(w, "enc", L_, "K"), _stack_ptrs(w, "enc", L_, "R"),
+                                                   _stack_ptrs(w, "enc", L_, "b"), _stack_ptrs(w, "dec", L_, "K"), _stack_ptrs(w, "dec", L_, "R"),
+                                                   _stack_ptrs(w, "dec", L_, "b"), g("enc_hs"), g("enc_res"), g("dec_hs"), g("dec_res"),
+                                                   g("top"), g("hT"), g("cT"), B, T_in, T_out, F_enc, F_dec, H, L_, act_code(act), _stream()))
+    if tape:
+        t["top"] = t["dec_hs"][L_ - 1]
+    return t
+
+
+def stacked_seq2seq_train_bwd(tp, dhs_top, w, num_layers, act="sigmoid", scratch=None, out=None):
+    """BPTT of stacked_seq2seq_train_fwd through both stacks in one launch.  tp: its tapes (enc_res, dec_res, cT); dhs_top
+    (B,T_out,H): the head's input gradient.  -> dict enc_dz (L,B,T_in,4H), dec_dz (L,B,T_out,4H) (out: preallocated ones).  The
+    weight gradients are lstm_seq_wgrad_layers products over these tapes.  scratch: plain memory, nothing is kept in it."""
+    dhs_top = _dev(dhs_top, "dhs_top")
+    L_ = int(num_layers)
+    enc_res, dec_res, cT = _dev(tp["enc_res"], "enc_res"), _dev(tp["dec_res"], "dec_res"), _dev(tp["cT"], "cT")
+    _, B, T_in, _, H = enc_res.shape
+    T_out = dec_res.shape[2]
+    assert enc_res.shape == (L_, B, T_in, 5, H) and dec_res.shape == (L_, B, T_out, 5, H) and cT.shape == (L_, B, H)
+    assert dhs_top.shape == (B, T_out, H)
+    o = {}
+    for k, s_ in (("enc_dz", (L_, B, T_in, 4 * H)), ("dec_dz", (L_, B, T_out, 4 * H))):
+        o[k] = torch.empty(s_, dtype=torch.float32, device=dhs_top.device) if out is None or out.get(k) is None else out[k]
+        assert _dev(o[k], k).shape == s_, k
+    L = _lib.lib()
+    buf = (scratch or _default_scratch).get(L.fov_stacked_seq2seq_train_bwd_scratch_bytes(B, T_in, T_out, H), dhs_top.device)
+    check(L.fov_stacked_seq2seq_train_bwd(_ptr(enc_res), _ptr(dec_res), _ptr(cT), _ptr(dhs_top), _stack_ptrs(w, "enc", L_, "R"),
+                                          _stack_ptrs(w, "enc", L_, "K"), _stack_ptrs(w, "dec", L_, "R"), _stack_ptrs(w, "dec", L_, "K"),
+                                          _ptr(o["enc_dz"]), _ptr(o["dec_dz"]), B, T_in, T_out, H, L_, act_code(act), buf.data_ptr(),
+                                          buf.numel(), _stream()))
+    return o
+
+
 def seq2seq_teacher_forced(enc_in, dec_in, w, act="sigmoid", impl="auto", workspace=None, dtype="f32"):
     """Training-graph forward (FoV_seq2seq.py:82-101) -> (B,T_out,F_dec).  dtype 'bf16': the encoder and the decoder as
     bf16 layers (lstm_seq_bf16, the decoder from the encoder's state), then dense_bf16 - the arithmetic of the bf16
@@ -617,6 +684,28 @@ def lstm_seq_wgrad_pair(layer1, layer2, accumulate=False, scratch=None):
                                     B, H, 1 if accumulate else 0, buf.data_ptr(), buf.numel(), _stream()))
 
 
+def lstm_seq_wgrad_layers(layers, accumulate=False, scratch=None):
+    """All weight gradients of a stack of up to four layers that share the batch and the width, from their dz tapes
+    (fov_lstm_seq_wgrad_layers): one launch at few rows, else a lstm_seq_wgrad per layer; the per-layer calls' bits either way.
+    layers: [(x (B,T,F), hs (B,T,H), h0 or None, dz (B,T,4H), dK, dR, db)], any of dK / dR / db may be None."""
+    n = len(layers)
+    assert 1 <= n <= 4
+    B, H = layers[0][0].shape[0], layers[0][1].shape[-1]
+    Ts, Fs = [], []
+    for i, (x, hs, h0, dz, dK, dR, db) in enumerate(layers):
+        _dev(x, "x%d" % i); _dev(hs, "hs%d" % i); _dev(h0, "h0_%d" % i); _dev(dz, "dz%d" % i)
+        T, F = x.shape[1], x.shape[2]
+        assert x.shape[0] == B and hs.shape == (B, T, H) and dz.shape == (B, T, 4 * H) and (h0 is None or h0.shape == (B, H))
+        assert (dK is None or dK.shape == (F, 4 * H)) and (dR is None or dR.shape == (H, 4 * H)) and (db is None or db.shape == (4 * H,))
+        Ts.append(T); Fs.append(F)
+    L = _lib.lib()
+    need = max(L.fov_lstm_seq_bwd_workspace_bytes(B, T, F, H) for T, F in zip(Ts, Fs))
+    buf = (scratch or _default_scratch).get(need, layers[0][0].device)
+    col = lambda j: _PTR4(*([_ptr(lay[j]) for lay in layers] + [None] * (4 - n)))
+    check(L.fov_lstm_seq_wgrad_layers(n, col(0), _INT4(*(Fs + [0] * (4 - n))), _INT4(*(Ts + [0] * (4 - n))), col(1), col(2), col(3), col(4),
+                                      col(5), col(6), B, H, 1 if accumulate else 0, buf.data_ptr(), buf.numel(), _stream()))
+
+
 _side_streams = {}
 
 
@@ -693,6 +782,7 @@ def tf_head_bwd(h, w, head, dmu, dvar, g, accumulate=False):
 
 import ctypes as _ct
 
+_PTR3 = _ct.c_void_p * 3
 _PTR4 = _ct.c_void_p * 4
 _INT4 = _ct.c_int * 4
 _INT5 = _ct.c_int * 5

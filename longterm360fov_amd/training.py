@@ -824,16 +824,84 @@ class StackedSeq2SeqTrainer(FlatParamTrainer):
     """Teacher-forced training step of the L-layer target-only seq2seq (mycode/Fov_seq2seq_2layers.py:232-272,332-343 and
     3layers.py:222-300): encoder layer l hands its final (h, c) to decoder layer l, every layer returns its sequence to
     the next, Dense(6, tanh) on the top decoder layer; Adam + MSE.  Same layer kernels as the one-layer trainer, one
-    forward-with-reserve and one BPTT launch per layer."""
+    forward-with-reserve and one BPTT launch per layer - or, up to width 64 (`fused_stack`, lstm_stacked_train.hip), ONE forward
+    launch and ONE BPTT launch for both stacks, the head as one launch and each stack's weight gradients as one."""
 
     defer_reduces = True   # gradients are written by the library's weight-gradient entry points only
-
+    fused_stack = True     # A/B switch: both stacks' forward / BPTT as one launch each where the shape allows it; False keeps the
+                           # per-layer path
+    # One workgroup per 16-sequence tile against the per-layer kernels' several per tile: from this many sequences on the per-layer
+    # path is kept (None: no bound).  tools/stacked_train_time.py measures the two paths side by side
+    # (profiles/stacked_train_time.jsonl: ahead 5.4x / 5.9x at B = 64, behind by 5 % / 8 % at B = 1024, level at 4096; nothing
+    # between 64 and 1024 was measured).
+    fused_stack_max_batch = 1024
 
     def __init__(self, weights, num_layers, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda"):
         self.L, self.act, self.impl = int(num_layers), act, impl
         self._alloc(weights, stacked_weight_order(self.L), optimizer, lr, device)
+        self._bufs = {}
+
+    def _fused_ok(self, enc, dec_in):
+        B, T_in, F = enc.shape
+        T_out, O = dec_in.shape[1], dec_in.shape[2]
+        if not self.fused_stack or self.impl != "auto" or T_in < 1 or T_out < 1:
+            return False
+        if self.fused_stack_max_batch is not None and B >= self.fused_stack_max_batch:
+            return False
+        return ops.stacked_seq2seq_train_supported(B, T_in, T_out, F, O, self.w["enc0_R"].shape[0], self.L)
+
+    def _buffers(self, B, T_in, T_out):
+        key = (B, T_in, T_out)
+        if key not in self._bufs:
+            H, O, L = self.w["enc0_R"].shape[0], self.w["dense_W"].shape[1], self.L
+            e = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+            self._bufs[key] = {
+                "tape": {"enc_hs": e(L, B, T_in, H), "enc_res": e(L, B, T_in, 5, H), "dec_hs": e(L, B, T_out, H),
+                         "dec_res": e(L, B, T_out, 5, H), "hT": e(L, B, H), "cT": e(L, B, H)},
+                "dz": {"enc_dz": e(L, B, T_in, 4 * H), "dec_dz": e(L, B, T_out, 4 * H)},
+                "top": {"top": e(B, T_out, H)}, "d_hs": e(B, T_out, H), "y": e(B, T_out, O), "dpre": e(B, T_out, O),
+            }
+        return self._bufs[key]
+
+    def _forward_backward_fused(self, enc, dec_in, target, grad_weight):
+        """The step in six launches: forward, head, BPTT, two grouped weight-gradient calls (and the optimizer behind them)."""
+        w, g, act, L = self.w, self.g, self.act, self.L
+        B, T_in, _ = enc.shape
+        T_out = dec_in.shape[1]
+        H, O = w["enc0_R"].shape[0], w["dense_W"].shape[1]
+        bufs = self._buffers(B, T_in, T_out)
+        tp = ops.stacked_seq2seq_train_fwd(enc, dec_in, w, L, act=act, out=bufs["tape"])
+        top = tp["top"]
+        if ops.dense_mse_head_supported(B * T_out, H, O):
+            y, d_hs, loss = ops.dense_mse_head(top, w["dense_W"], w["dense_b"], target, "tanh", dW=g["dense_W"], db=g["dense_b"],
+                                               loss=self.loss_slot, weight=grad_weight, scratch=self.scratch, dx=bufs["d_hs"], y=bufs["y"])
+        else:
+            y = ops.dense(top, w["dense_W"], w["dense_b"], activation="tanh", out=bufs["y"])
+            dpre, loss = ops.mse_dense_grad(y, target, "tanh", scratch=self.scratch, dpre=bufs["dpre"], loss=self.loss_slot,
+                                            weight=grad_weight)
+            d_hs, _, _ = ops.dense_bwd(top, w["dense_W"], dpre, dW=g["dense_W"], db=g["dense_b"], scratch=self.scratch)
+        # (the dx hand-off is plain scratch: not bwd_scratch, whose head is the persistent BPTT kernels' status header)
+        dz = ops.stacked_seq2seq_train_bwd(tp, d_hs, w, L, act=act, scratch=self.scratch, out=bufs["dz"])
+        for side, x0, hs, dzs, h0 in (("dec", dec_in, tp["dec_hs"], dz["dec_dz"], tp["hT"]), ("enc", enc, tp["enc_hs"], dz["enc_dz"], None)):
+            ops.lstm_seq_wgrad_layers([(x0 if l == 0 else hs[l - 1], hs[l], None if h0 is None else h0[l], dzs[l],
+                                        g["%s%d_K" % (side, l)], g["%s%d_R" % (side, l)], g["%s%d_b" % (side, l)]) for l in range(L)],
+                                      scratch=self.scratch)
+        return loss, y
+
+    def _eval_forward(self, enc, dec_in, target):
+        """Validation: the fused forward without tapes, the head and the loss - no backward.  The per-layer path keeps the
+        training forward (FlatParamTrainer._eval_forward)."""
+        if not self._fused_ok(enc, dec_in):
+            return super()._eval_forward(enc, dec_in, target)
+        bufs = self._buffers(enc.shape[0], enc.shape[1], dec_in.shape[1])
+        top = ops.stacked_seq2seq_train_fwd(enc, dec_in, self.w, self.L, act=self.act, tape=False, out=bufs["top"])["top"]
+        y = ops.dense(top, self.w["dense_W"], self.w["dense_b"], activation="tanh", out=bufs["y"])
+        _, loss = ops.mse_dense_grad(y, target, None, scratch=self.scratch, dpre=bufs["dpre"])
+        return loss, y
 
     def forward_backward(self, enc, dec_in, target, grad_weight=1.0):
+        if self._fused_ok(enc, dec_in):
+            return self._forward_backward_fused(enc, dec_in, target, grad_weight)
         w, g, act, impl, ws, L = self.w, self.g, self.act, self.impl, self.ws, self.L
         etape, dtape = [], []
         inp = enc
