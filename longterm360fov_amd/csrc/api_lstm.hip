@@ -265,20 +265,18 @@ size_t fov_lstm_seq_bwd_workspace_bytes(int B, int T, int F, int H) {
     return sizeof(float) * lstm_bwd_workspace_floats(B, T, F, H);
 }
 
-// fp32 (any width) and bf16-operand (H = 256) BPTT of one layer: one body behind the two entry points
-static int lstm_seq_bwd_entry(const float* x, const float* K, const float* R, const float* h0, const float* c0, const float* hs,
-                              const float* reserve, const float* dhs, const float* dhT, const float* dcT, float* dz, float* dx,
-                              float* dK, float* dR, float* db, float* dh0, float* dc0, int B, int T, int F, int H, int act,
-                              int accumulate, void* workspace, size_t workspace_bytes, fov_stream_t stream, int bf16) {
-    if (B < 0 || T < 0 || F <= 0 || (bf16 ? H != 256 : H <= 0) || !K || !R ||
-        (B > 0 && T > 0 && (!x || !hs || !reserve || !dz)) || !valid_act(act)) {
-        set_error(bf16 ? "fov_lstm_seq_bwd_bf16: invalid argument (H = 256 only)" : "fov_lstm_seq_bwd: invalid argument");
+// fp32 (any width) and bf16-operand (H = 256) BPTT of one layer: one body behind the two entry points, which fill the layer
+// (LstmBwdLayer: the recurrence's operands, the weight-gradient problem, K, dx, the shape)
+static int lstm_seq_bwd_entry(const LstmBwdLayer& l, void* workspace, size_t workspace_bytes, fov_stream_t stream) {
+    const int B = l.B, T = l.T, F = l.F, H = l.H;
+    if (B < 0 || T < 0 || F <= 0 || (l.bf16 ? H != 256 : H <= 0) || !l.K || !l.rec.R ||
+        (B > 0 && T > 0 && (!l.wg.x || !l.wg.hs || !l.rec.reserve || !l.rec.dz)) || !valid_act(l.act)) {
+        set_error(l.bf16 ? "fov_lstm_seq_bwd_bf16: invalid argument (H = 256 only)" : "fov_lstm_seq_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
-    if (B == 0) return accumulate ? FOV_OK : zero_lstm_wgrads(dK, dR, db, F, H, (hipStream_t)stream);
+    if (B == 0) return l.accumulate ? FOV_OK : zero_lstm_wgrads(l.wg.dK, l.wg.dR, l.wg.db, F, H, (hipStream_t)stream);
     if (int rc = check_ws(workspace, workspace_bytes, fov_lstm_seq_bwd_workspace_bytes(B, T, F, H))) return rc;
-    return lstm_seq_bwd(x, K, R, h0, c0, hs, reserve, dhs, dhT, dcT, dz, dx, dK, dR, db, dh0, dc0, B, T, F, H, act,
-                        accumulate, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream, bf16);
+    return lstm_seq_bwd(l, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 int fov_lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0, const float* c0,
@@ -286,8 +284,9 @@ int fov_lstm_seq_bwd(const float* x, const float* K, const float* R, const float
                      float* dz, float* dx, float* dK, float* dR, float* db, float* dh0, float* dc0, int B, int T,
                      int F, int H, int act, int accumulate, void* workspace, size_t workspace_bytes,
                      fov_stream_t stream) {
-    return lstm_seq_bwd_entry(x, K, R, h0, c0, hs, reserve, dhs, dhT, dcT, dz, dx, dK, dR, db, dh0, dc0, B, T, F, H, act, accumulate,
-                              workspace, workspace_bytes, stream, 0);
+    const LstmBwdLayer l = {{R, reserve, c0, dhs, dhT, dcT, dz, dh0, dc0, nullptr}, {x, hs, h0, dz, dK, dR, db, F, T}, K, dx,
+                            B, T, F, H, act, accumulate, /*bf16=*/0};
+    return lstm_seq_bwd_entry(l, workspace, workspace_bytes, stream);
 }
 
 int fov_lstm_seq_bwd_bf16(const float* x, const float* K, const float* R, const float* h0, const float* c0,
@@ -295,8 +294,9 @@ int fov_lstm_seq_bwd_bf16(const float* x, const float* K, const float* R, const 
                           float* dz, float* dx, float* dK, float* dR, float* db, float* dh0, float* dc0, int B, int T,
                           int F, int H, int act, int accumulate, void* workspace, size_t workspace_bytes,
                           fov_stream_t stream) {
-    return lstm_seq_bwd_entry(x, K, R, h0, c0, hs, reserve, dhs, dhT, dcT, dz, dx, dK, dR, db, dh0, dc0, B, T, F, H, act, accumulate,
-                              workspace, workspace_bytes, stream, 1);
+    const LstmBwdLayer l = {{R, reserve, c0, dhs, dhT, dcT, dz, dh0, dc0, nullptr}, {x, hs, h0, dz, dK, dR, db, F, T}, K, dx,
+                            B, T, F, H, act, accumulate, /*bf16=*/1};
+    return lstm_seq_bwd_entry(l, workspace, workspace_bytes, stream);
 }
 
 int fov_lstm_stack2_bwd_supported(int B, int T, int F, int H) { return (F > 0 && bwd16_pair_shape(B, T, H)) ? 1 : 0; }
@@ -337,9 +337,12 @@ int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const 
         return FOV_ERR_UNSUPPORTED;
     }
     if (int rc = check_ws(workspace, workspace_bytes, fov_lstm_stack2_bwd_workspace_bytes(B, T, F, H))) return rc;
-    return lstm_stack2_bwd(x, R1, K2, R2, h0_1, c0_1, h0_2, c0_2, hs1, reserve1, hs2, reserve2, dhs2, dhT2, dcT2, dhT1, dcT1, dz1, dz2, dK1,
-                           dR1, db1, dK2, dR2, db2, dh0_1, dc0_1, dh0_2, dc0_2, B, T, F, H, act, accumulate, (float*)workspace,
-                           workspace_bytes / sizeof(float), (hipStream_t)stream);
+    // the upper layer reads the lower one's hs; its dx stays inside the kernel, which needs no K1
+    const LstmBwdLayer low = {{R1, reserve1, c0_1, nullptr, dhT1, dcT1, dz1, dh0_1, dc0_1, nullptr}, {x, hs1, h0_1, dz1, dK1, dR1, db1, F, T},
+                              nullptr, nullptr, B, T, F, H, act, accumulate, 0};
+    const LstmBwdLayer up = {{R2, reserve2, c0_2, dhs2, dhT2, dcT2, dz2, dh0_2, dc0_2, nullptr}, {hs1, hs2, h0_2, dz2, dK2, dR2, db2, H, T},
+                             K2, nullptr, B, T, H, H, act, accumulate, 0};
+    return lstm_stack2_bwd(low, up, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 size_t fov_mix_decoder_workspace_bytes(int B, int H) {

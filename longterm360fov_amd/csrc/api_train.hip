@@ -16,8 +16,8 @@ int fov_lstm_seq_wgrad(const float* x, const float* hs, const float* h0, const f
         return FOV_ERR_INVALID;
     }
     if (int rc = check_ws(workspace, workspace_bytes, fov_lstm_seq_bwd_workspace_bytes(B, T, F, H))) return rc;
-    return lstm_seq_wgrad(x, hs, h0, dz, dK, dR, db, B, T, F, H, accumulate, bf16 ? 1 : 0, (float*)workspace,
-                          workspace_bytes / sizeof(float), (hipStream_t)stream);
+    const LayerWgrad layer = {x, hs, h0, dz, dK, dR, db, F, T};
+    return lstm_seq_wgrad(layer, B, H, accumulate, bf16 ? 1 : 0, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 int fov_lstm_seq_wgrad_pair_one_launch(int B, int T1, int T2, int H) {
@@ -35,24 +35,26 @@ int fov_lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1
     }
     const size_t n1 = fov_lstm_seq_bwd_workspace_bytes(B, T1, F1, H), n2 = fov_lstm_seq_bwd_workspace_bytes(B, T2, F2, H);
     if (int rc = check_ws(workspace, workspace_bytes, n1 > n2 ? n1 : n2)) return rc;
-    return lstm_seq_wgrad_pair(x1, hs1, h0_1, dz1, dK1, dR1, db1, T1, F1, x2, hs2, h0_2, dz2, dK2, dR2, db2, T2, F2, B, H, accumulate,
-                               (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
+    const LayerWgrad layers[2] = {{x1, hs1, h0_1, dz1, dK1, dR1, db1, F1, T1}, {x2, hs2, h0_2, dz2, dK2, dR2, db2, F2, T2}};
+    return lstm_seq_wgrad_layers(2, layers, B, H, accumulate, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 int fov_lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
                               const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
                               void* workspace, size_t workspace_bytes, fov_stream_t stream) {
-    if (L < 1 || L > 4) {
+    if (L < 1 || L > kMaxWgradLayers) {
         set_error("fov_lstm_seq_wgrad_layers: 1 to 4 layers (got %d)", L);
         return FOV_ERR_UNSUPPORTED;
     }
     bool ok = B >= 0 && H > 0 && x && F && T && hs && h0 && dz && dK && dR && db;
     size_t need = 0;
+    LayerWgrad layers[kMaxWgradLayers];
     for (int l = 0; ok && l < L; ++l) {
         ok = T[l] >= 0 && F[l] > 0 && !(B > 0 && T[l] > 0 && (!dz[l] || (dK[l] && !x[l]) || (dR[l] && !hs[l])));
         if (ok) {
             const size_t n = fov_lstm_seq_bwd_workspace_bytes(B, T[l], F[l], H);
             need = n > need ? n : need;
+            layers[l] = {x[l], hs[l], h0[l], dz[l], dK[l], dR[l], db[l], F[l], T[l]};
         }
     }
     if (!ok) {
@@ -60,8 +62,7 @@ int fov_lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const 
         return FOV_ERR_INVALID;
     }
     if (int rc = check_ws(workspace, workspace_bytes, need)) return rc;
-    return lstm_seq_wgrad_layers(L, x, F, T, hs, h0, dz, dK, dR, db, B, H, accumulate, (float*)workspace, workspace_bytes / sizeof(float),
-                                 (hipStream_t)stream);
+    return lstm_seq_wgrad_layers(L, layers, B, H, accumulate, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
 }
 
 size_t fov_dense_bwd_workspace_bytes(int N, int In, int Out) {

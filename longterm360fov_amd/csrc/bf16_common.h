@@ -435,11 +435,6 @@ bool stack2_bf16_shape_ok(int B, int T, int F, int H);
 int launch_stack2_bf16(const float* x, const float* K1, const float* R1, const float* b1, const float* K2, const float* R2,
                        const float* b2, float* hs1, float* hT1, float* cT1, float* res1, float* hs2, float* hT2, float* cT2,
                        float* res2, int B, int T, int F, int act, void* workspace, hipStream_t stream);
-// lstm_bwd8.hip: BPTT recurrence in groups of eight workgroups (H = 256), fp32 or bf16 operands
-bool bwd8_preferred(int B, int H);
-int launch_bwd8(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT, const float* dcT,
-                float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int act, int bf16, void* xch_ws, hipStream_t stream,
-                const float* K_dx = nullptr, float* dx = nullptr);
 // gemm_bf16.hip
 size_t gemm_bf16_tn_scratch_floats(int M, int N);
 int gemm_bf16_tn_fused(const float* a1, long lda1, long a1_so, int M1, int shift1, const float* a2, long lda2, long a2_so, int M2,

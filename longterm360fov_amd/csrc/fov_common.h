@@ -272,45 +272,58 @@ size_t mix_decoder_bwd_workspace_bytes(int B);
 int mix_decoder_bwd_launch(MixDecBwdParams p, const float* K2, int act, void* workspace, hipStream_t stream);
 int mix_decoder_bwd_bf16_launch(MixDecBwdParams p, const float* K2, int act, void* workspace, hipStream_t stream);   // mix_decoder_bwd_bf16.hip
 
-// persistent BPTT recurrence (lstm_bwd_cluster.hip)
-bool bwd_cluster_shape_ok(int H);
 // lstm_wide16.hip: two stacked width-512 layers as one launch (layer 2 a few steps behind layer 1 on other CUs)
 bool wide16_pair_shape(int B, int T, int F, int H);
 int launch_wide16_pair(const LstmParams& a, const LstmParams& b, hipStream_t stream);
-// lstm_bwd16.hip: BPTT recurrence with 16 / 32 units per workgroup (fp32): width 512, and 128 / 256 at small batches
-bool wgrad_rows_takes(long rows, int H);       // wgrad_group.hip: few rows AND narrow layers - 16 x 64 tiles, rows split over a workgroup's waves
-int wgrad_rows_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
-                      const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate, hipStream_t stream);
-bool lstm_seq_wgrad_pair_one_launch(int B, int T1, int T2, int H);
-int lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1, const float* dz1, float* dK1, float* dR1, float* db1, int T1, int F1,
-                        const float* x2, const float* hs2, const float* h0_2, const float* dz2, float* dK2, float* dR2, float* db2, int T2, int F2,
-                        int B, int H, int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream);
-// all weight gradients of up to four layers that share the batch and the width (a stack): one launch where the few-row form takes
-// every layer, else one lstm_seq_wgrad per layer - the same bits either way
-int lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
-                          const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
-                          float* scratch, size_t scratch_floats, hipStream_t stream);
-bool wgrad_group_takes(int B, int T, int H);   // wgrad_group.hip: few rows - every (product, output tile) one workgroup, one launch
-int wgrad_group_layers(int L, const float* const* x, const int* F, const float* const* hs, const float* const* h0, const float* const* dz,
-                       float* const* dK, float* const* dR, float* const* db, int B, int T, int H, int accumulate, hipStream_t stream);
-bool bwd16_pair_shape(int B, int T, int H);
-int launch_bwd16_pair(const float* R2, const float* K2, const float* reserve2, const float* c0_2, const float* dhs2, const float* dhT2,
-                      const float* dcT2, float* dz2, float* dh0_2, float* dc0_2, float* db_part2, const float* R1, const float* reserve1,
-                      const float* c0_1, const float* dhT1, const float* dcT1, float* dz1, float* dh0_1, float* dc0_1, float* db_part1,
-                      int B, int T, int act, void* xch_ws, hipStream_t stream);
-size_t lstm_stack2_bwd_workspace_floats(int B, int T, int F, int H);
-int lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const float* R2, const float* h0_1, const float* c0_1,
-                    const float* h0_2, const float* c0_2, const float* hs1, const float* res1, const float* hs2, const float* res2,
-                    const float* dhs2, const float* dhT2, const float* dcT2, const float* dhT1, const float* dcT1, float* dz1, float* dz2,
-                    float* dK1, float* dR1, float* db1, float* dK2, float* dR2, float* db2, float* dh0_1, float* dc0_1, float* dh0_2,
-                    float* dc0_2, int B, int T, int F, int H, int act, int accumulate, float* ws, size_t ws_floats, hipStream_t stream);
+
+// A layer's BPTT as plain aggregates: the entry points fill them once, lstm_train.hip plans and runs them.
+// The recurrence's operands: the ten fields every BPTT kernel's own parameter struct starts with (set_rec copies them over)
+struct BwdRec {
+    const float *R, *reserve, *c0, *dhs, *dhT, *dcT;   // (H,4H), (B,T,5,H), then (B,H) / (B,T,H) / (B,H) / (B,H) or NULL
+    float *dz, *dh0, *dc0, *db_part;                   // (B,T,4H), (B,H), (B,H), per-tile bias partials (tiles,4H) or NULL
+};
+template <class KernelParams>
+inline void set_rec(KernelParams& p, const BwdRec& r) {
+    p.R = r.R; p.reserve = r.reserve; p.c0 = r.c0; p.dhs = r.dhs; p.dhT = r.dhT; p.dcT = r.dcT; p.dz = r.dz; p.dh0 = r.dh0; p.dc0 = r.dc0; p.db_part = r.db_part;
+}
+// A layer's weight-gradient problem: dK (F,4H) = x^T dz, dR (H,4H) = h_{t-1}^T dz (h_{-1} = h0 or 0), db (4H) = colsum(dz);
+// any of dK / dR / db may be NULL
+struct LayerWgrad {
+    const float *x, *hs, *h0, *dz;                     // (B,T,F), (B,T,H), (B,H) or NULL, (B,T,4H)
+    float *dK, *dR, *db;
+    int F, T;
+};
+// A layer's whole backward; rec.dz and wg.dz are the same tape, rec.db_part belongs to lstm_seq_bwd
+struct LstmBwdLayer {
+    BwdRec rec;
+    LayerWgrad wg;
+    const float* K;                                    // (F,4H)
+    float* dx;                                         // (B,T,F) or NULL
+    int B, T, F, H, act, accumulate, bf16;
+};
+
+// The persistent BPTT recurrences; the status word and the granule buffers live at `xch_ws` (kStatusBytes + kXchBytes)
+// lstm_bwd16.hip: 16 / 32 units per workgroup (fp32): width 512, and 128 / 256 at small batches
 bool bwd16_takes(int B, int H);
-int launch_bwd16(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT, const float* dcT,
-                 float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int H, int act, void* xch_ws, hipStream_t stream);
+int launch_bwd16(const BwdRec& r, int B, int T, int H, int act, void* xch_ws, hipStream_t stream);
+// ... two stacked width-512 layers as one launch: `low` takes its dhs from `up` through K2 inside the kernel (low.dhs is not read)
+bool bwd16_pair_shape(int B, int T, int H);
+int launch_bwd16_pair(const BwdRec& up, const BwdRec& low, const float* K2, int B, int T, int act, void* xch_ws, hipStream_t stream);
+// lstm_bwd8.hip: groups of eight workgroups (H = 256), fp32 or bf16 operands; K_dx and dx: dx = dz K^T inside the kernel
+// (fp32: dx = eight partial tapes [slice][B][T][256])
+bool bwd8_preferred(int B, int H);
+int launch_bwd8(const BwdRec& r, int B, int T, int act, int bf16, void* xch_ws, hipStream_t stream, const float* K_dx = nullptr,
+                float* dx = nullptr);
+// lstm_bwd_cluster.hip: groups of H / 64 workgroups
+bool bwd_cluster_shape_ok(int H);
 size_t bwd_cluster_xch_bytes(int B, int H);
-int launch_bwd_cluster(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT,
-                       const float* dcT, float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int H, int act,
-                       void* xch_ws, hipStream_t stream);
+int launch_bwd_cluster(const BwdRec& r, int B, int T, int H, int act, void* xch_ws, hipStream_t stream);
+
+// wgrad_group.hip: the weight gradients of up to four layers that share the batch and the width, in one launch
+bool wgrad_rows_takes(long rows, int H);       // few rows AND narrow layers - 16 x 64 tiles, rows split over a workgroup's waves
+int wgrad_rows_layers(int L, const LayerWgrad* layers, int B, int H, int accumulate, hipStream_t stream);
+bool wgrad_group_takes(int B, int T, int H);   // few rows - every (product, output tile) one workgroup; the layers share T too
+int wgrad_group_layers(int L, const LayerWgrad* layers, int B, int H, int accumulate, hipStream_t stream);
 
 // fp32 matrix-core GEMM (gemm_f32.hip; the strided forms: gemm_f32.h)
 int matmul_f32(const float* a, const float* b, float* c, int M, int K, int N, float* scratch, size_t scratch_floats,
@@ -318,12 +331,18 @@ int matmul_f32(const float* a, const float* b, float* c, int M, int K, int N, fl
 
 // a layer's training step: BPTT dispatch, weight-gradient products, Dense backward (lstm_train.hip)
 size_t lstm_bwd_workspace_floats(int B, int T, int F, int H);
-int lstm_seq_wgrad(const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db, int B, int T,
-                   int F, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream);
-int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0, const float* c0, const float* hs,
-                 const float* reserve, const float* dhs, const float* dhT, const float* dcT, float* dz, float* dx,
-                 float* dK, float* dR, float* db, float* dh0, float* dc0, int B, int T, int F, int H, int act,
-                 int accumulate, float* ws, size_t ws_floats, hipStream_t stream, int bf16 = 0);
+int lstm_seq_bwd(const LstmBwdLayer& layer, float* ws, size_t ws_floats, hipStream_t stream);
+// two stacked width-512 layers, both recurrences in one launch (bwd16_pair_shape): low.rec.dhs and up.dx are not used, the
+// upper layer's dx reaches the lower one inside the kernel
+size_t lstm_stack2_bwd_workspace_floats(int B, int T, int F, int H);
+int lstm_stack2_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up, float* ws, size_t ws_floats, hipStream_t stream);
+int lstm_seq_wgrad(const LayerWgrad& layer, int B, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream);
+// all weight gradients of up to four layers that share the batch and the width (a stack, an encoder / decoder pair): one launch
+// where the few-row form takes every layer, else one lstm_seq_wgrad per layer - the same bits either way
+constexpr int kMaxWgradLayers = 4;
+bool lstm_seq_wgrad_pair_one_launch(int B, int T1, int T2, int H);
+int lstm_seq_wgrad_layers(int L, const LayerWgrad* layers, int B, int H, int accumulate, float* scratch, size_t scratch_floats,
+                          hipStream_t stream);
 size_t mix_head_wgrad_scratch_floats(int B, int T, int H, int O, int n_oth);
 int mix_head_wgrad(const float* h2, const float* dpre_p, const float* others, const float* p, const float* dpre_m, float* out, int B,
                    int T, int H, int O, int n_oth, int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream);

@@ -528,14 +528,12 @@ static int launch_bwd16_t(Bwd16Params& p, int act, hipStream_t stream) {
     return launch_check("16-unit BPTT");
 }
 
-// status word + granule buffers live at `xch_ws` (kStatusBytes + kXchBytes)
-int launch_bwd16(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT, const float* dcT,
-                 float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int H, int act, void* xch_ws, hipStream_t stream) {
+int launch_bwd16(const BwdRec& r, int B, int T, int H, int act, void* xch_ws, hipStream_t stream) {
     if (B == 0 || T == 0) return FOV_OK;
-    if (((uintptr_t)R) & 15) { set_error("16-unit BPTT kernel: R must be 16-byte aligned"); return FOV_ERR_INVALID; }
+    if (((uintptr_t)r.R) & 15) { set_error("16-unit BPTT kernel: R must be 16-byte aligned"); return FOV_ERR_INVALID; }
     if (!bwd16_takes(B, H)) { set_error("16-unit BPTT kernel: unsupported shape B = %d, H = %d", B, H); return FOV_ERR_UNSUPPORTED; }
     Bwd16Params p = {};
-    p.R = R; p.reserve = reserve; p.c0 = c0; p.dhs = dhs; p.dhT = dhT; p.dcT = dcT; p.dz = dz; p.dh0 = dh0; p.dc0 = dc0; p.db_part = db_part;
+    set_rec(p, r);
     p.B = B; p.T = T;
     p.num_tiles = (B + XBT - 1) / XBT;
     p.status = (unsigned*)xch_ws;
@@ -561,17 +559,14 @@ bool bwd16_pair_shape(int B, int T, int H) {
     return granules * 8 <= kXchBytes - kHelloBytes;
 }
 
-int launch_bwd16_pair(const float* R2, const float* K2, const float* reserve2, const float* c0_2, const float* dhs2, const float* dhT2,
-                      const float* dcT2, float* dz2, float* dh0_2, float* dc0_2, float* db_part2, const float* R1, const float* reserve1,
-                      const float* c0_1, const float* dhT1, const float* dcT1, float* dz1, float* dh0_1, float* dc0_1, float* db_part1,
-                      int B, int T, int act, void* xch_ws, hipStream_t stream) {
+int launch_bwd16_pair(const BwdRec& up, const BwdRec& low, const float* K2, int B, int T, int act, void* xch_ws, hipStream_t stream) {
     if (B == 0 || T == 0) return FOV_OK;
     if (!bwd16_pair_shape(B, T, 512)) { set_error("two-layer BPTT launch: unsupported shape B = %d, T = %d", B, T); return FOV_ERR_UNSUPPORTED; }
-    if ((((uintptr_t)R1) | ((uintptr_t)R2) | ((uintptr_t)K2)) & 15) { set_error("two-layer BPTT launch: kernels must be 16-byte aligned"); return FOV_ERR_INVALID; }
+    if ((((uintptr_t)low.R) | ((uintptr_t)up.R) | ((uintptr_t)K2)) & 15) { set_error("two-layer BPTT launch: kernels must be 16-byte aligned"); return FOV_ERR_INVALID; }
     const int tiles = (B + XBT - 1) / XBT;
     Bwd16Pair pp = {};
     Bwd16Params& u = pp.up;
-    u.R = R2; u.reserve = reserve2; u.c0 = c0_2; u.dhs = dhs2; u.dhT = dhT2; u.dcT = dcT2; u.dz = dz2; u.dh0 = dh0_2; u.dc0 = dc0_2; u.db_part = db_part2;
+    set_rec(u, up);
     u.B = B; u.T = T; u.num_tiles = tiles; u.num_groups = tiles; u.epoch_span = T + 2; u.xcd_pad = 0;
     u.status = (unsigned*)xch_ws;
     u.xch = (unsigned long long*)((char*)xch_ws + kStatusBytes);
@@ -579,11 +574,11 @@ int launch_bwd16_pair(const float* R2, const float* K2, const float* reserve2, c
     u.ring_ax = u.xch + (size_t)tiles * 4 * xpar;                 // behind the two layers' parity areas
     u.ring_xb = u.ring_ax + (size_t)tiles * T * ax;
     pp.mid = u;
-    pp.mid.R = K2; pp.mid.reserve = nullptr; pp.mid.c0 = nullptr; pp.mid.dhs = nullptr; pp.mid.dhT = nullptr; pp.mid.dcT = nullptr;
-    pp.mid.dz = nullptr; pp.mid.dh0 = nullptr; pp.mid.dc0 = nullptr; pp.mid.db_part = nullptr;
+    set_rec(pp.mid, BwdRec{});
+    pp.mid.R = K2;
     pp.low = u;
-    pp.low.R = R1; pp.low.reserve = reserve1; pp.low.c0 = c0_1; pp.low.dhs = nullptr; pp.low.dhT = dhT1; pp.low.dcT = dcT1;
-    pp.low.dz = dz1; pp.low.dh0 = dh0_1; pp.low.dc0 = dc0_1; pp.low.db_part = db_part1;
+    set_rec(pp.low, low);
+    pp.low.dhs = nullptr;
     if (int rc_ = xch_account(u.status, u.epoch_span, stream)) return rc_;
     void (*kern)(Bwd16Pair) = act == FOV_ACT_HARD_SIGMOID ? lstm_bwd16_pair_kernel<FOV_ACT_HARD_SIGMOID> : lstm_bwd16_pair_kernel<FOV_ACT_SIGMOID>;
     hipLaunchKernelGGL(kern, dim3(8 * 16), dim3(256), 0, stream, pp);

@@ -542,25 +542,22 @@ extern "C" int fov_debug_read_b8_stamps(unsigned long long* out) {
 // one workgroup per CU: groups of eight fill the chip up to 32 tiles; beyond that the 4-group kernel is as good
 bool bwd8_preferred(int B, int H) { return H == QH && B > 0 && B <= 32 * QBT; }
 
-// status word + granule buffers live at `xch_ws` (kStatusBytes + kXchBytes)
-int launch_bwd8(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT, const float* dcT,
-                float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int act, int bf16, void* xch_ws, hipStream_t stream,
-                const float* K_dx, float* dx) {
+int launch_bwd8(const BwdRec& r, int B, int T, int act, int bf16, void* xch_ws, hipStream_t stream, const float* K_dx, float* dx) {
     if (B == 0 || T == 0) return FOV_OK;
     Bwd8Params p = {};
     p.K = K_dx; p.dx = dx;
     const bool with_dx = K_dx && dx;      // (fp32: dx = eight partial tapes [slice][B][T][256])
     if (with_dx && (((uintptr_t)K_dx) & 15)) { set_error("8-group BPTT kernel: K must be 16-byte aligned"); return FOV_ERR_INVALID; }
-    p.R = R; p.reserve = reserve; p.c0 = c0; p.dhs = dhs; p.dhT = dhT; p.dcT = dcT; p.dz = dz; p.dh0 = dh0; p.dc0 = dc0; p.db_part = db_part;
+    set_rec(p, r);
     p.B = B; p.T = T;
     p.num_tiles = (B + QBT - 1) / QBT;
     const int max_groups = device_cu_count() / QG;
     if (max_groups < 1) { set_error("8-group BPTT kernel needs at least %d CUs", QG); return FOV_ERR_UNSUPPORTED; }
     p.num_groups = p.num_tiles < max_groups ? p.num_tiles : max_groups;
     if ((size_t)p.num_groups * 2 * (bf16 ? (size_t)Q_DZ_BYTES : B8_PAR * 8) > kXchBytes - kHelloBytes) { set_error("8-group BPTT kernel: granule area too small"); return FOV_ERR_WORKSPACE; }
-    if (bf16 && (((uintptr_t)R) & 15)) { set_error("8-group BPTT kernel: R must be 16-byte aligned"); return FOV_ERR_INVALID; }
-    if (bf16 && ((((uintptr_t)reserve) | ((uintptr_t)c0) | ((uintptr_t)dhs) | ((uintptr_t)dhT) | ((uintptr_t)dcT) | ((uintptr_t)dz) |
-                  ((uintptr_t)dh0) | ((uintptr_t)dc0) | ((uintptr_t)dx)) & 7)) {   // 8-byte tape accesses (two adjacent units per lane)
+    if (bf16 && (((uintptr_t)r.R) & 15)) { set_error("8-group BPTT kernel: R must be 16-byte aligned"); return FOV_ERR_INVALID; }
+    if (bf16 && ((((uintptr_t)r.reserve) | ((uintptr_t)r.c0) | ((uintptr_t)r.dhs) | ((uintptr_t)r.dhT) | ((uintptr_t)r.dcT) | ((uintptr_t)r.dz) |
+                  ((uintptr_t)r.dh0) | ((uintptr_t)r.dc0) | ((uintptr_t)dx)) & 7)) {   // 8-byte tape accesses (two adjacent units per lane)
         set_error("8-group bf16 BPTT kernel: tapes and state gradients must be 8-byte aligned");
         return FOV_ERR_INVALID;
     }

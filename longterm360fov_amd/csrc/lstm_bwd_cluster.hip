@@ -337,12 +337,10 @@ static int launch_bwd_h(const BwdParams& p, int act, hipStream_t stream) {
 }
 
 // status word + granule buffers live at `xch_ws` (kStatusBytes + bwd_cluster_xch_bytes)
-int launch_bwd_cluster(const float* R, const float* reserve, const float* c0, const float* dhs, const float* dhT,
-                       const float* dcT, float* dz, float* dh0, float* dc0, float* db_part, int B, int T, int H, int act,
-                       void* xch_ws, hipStream_t stream) {
+int launch_bwd_cluster(const BwdRec& r, int B, int T, int H, int act, void* xch_ws, hipStream_t stream) {
     if (B == 0 || T == 0) return FOV_OK;
     BwdParams p = {};
-    p.R = R; p.reserve = reserve; p.c0 = c0; p.dhs = dhs; p.dhT = dhT; p.dcT = dcT; p.dz = dz; p.dh0 = dh0; p.dc0 = dc0; p.db_part = db_part;
+    set_rec(p, r);
     p.B = B; p.T = T; p.H = H;
     p.num_tiles = (B + BBT - 1) / BBT;
     p.num_groups = cluster_num_groups(B, H);

@@ -1,7 +1,8 @@
 // Host dispatch of a layer's training step (a6: mycode/FoV_seq2seq.py:103,112-117 leave it to Keras autodiff):
 // lstm_seq_bwd / lstm_stack2_bwd run the recurrence on a persistent BPTT kernel (lstm_bwd_cluster / lstm_bwd8 /
 // lstm_bwd16.hip) or, for other widths and under FOV_BWD_STEPPED, step it from the host, then form dK / dR / db / dx
-// through wgrad_group.hip, the fused [x | h_prev | 1]^T dz product or single GEMMs; dense_bwd and mix_head_wgrad do the
+// through wgrad_group.hip, the fused [x | h_prev | 1]^T dz product or single GEMMs - which of these, decided once per call by
+// plan_lstm_bwd on the workspace that bwd_carve cuts up; dense_bwd and mix_head_wgrad do the
 // same for the heads.  launch_stepwise is the step-wise forward of layers wider than the persistent kernels take.
 // The only kernels here are the pointwise halves of the two stepped recurrences and mix_head_wgrad_kernel.
 #include "xch_common.h"
@@ -38,19 +39,38 @@ __global__ __launch_bounds__(256) void lstm_bwd_pointwise(const float* __restric
     dc[idx] = dcv * f;
 }
 
-size_t lstm_bwd_workspace_floats(int B, int T, int F, int H) {
-    // dh_rec (B,H) + dc (B,H) + split-K scratch for the largest weight-gradient GEMM / colsum
-    size_t wg = (size_t)64 * (size_t)(F > H ? F : H) * 4 * H;   // split-K partials of dK / dR (<= 64 slices)
-    size_t cs = (size_t)256 * 4 * H + (size_t)((B + 15) / 16) * 4 * H;   // colsum partials + per-tile db partials
-    size_t st = (size_t)8 * B * H;                               // split-K partials of the per-step dh GEMM
-    size_t m = wg > cs ? wg : cs;
-    // fp32, 256 -> 256 on the eight-workgroup BPTT kernel: the eight partial tapes of dx = dz K^T behind the per-tile db partials
-    const size_t dxp = (F == 256 && H == 256) ? (size_t)8 * B * T * 256 + (size_t)((B + 15) / 16) * 4 * H + 64 : 0;
-    if (dxp > m) m = dxp;
-    // head: status word + granule buffers of the persistent BPTT kernel (when the shape allows it)
-    size_t head = (kStatusBytes + kXchBytes) / sizeof(float);   // header + the fixed granule area (xch_common.h)
-    return head + (size_t)2 * B * H + (m > st ? m : st) + 64;
+// The workspace of lstm_seq_bwd, cut up in one place: the size function answers `total`, the launch side reads the offsets
+// (floats from the workspace's start), so whatever has an offset here fits a workspace that passed the size check.
+struct BwdCarve {
+    size_t dh_rec, dc;   // (B,H) each, behind the header and the fixed granule area (xch_common.h): the stepped recurrence's
+                         // carries; the persistent kernels' state gradients when the caller asks for none
+    size_t scratch;      // split-K partials of the products and column sums; at its start, while the recurrence runs:
+    size_t db_part;      //   the persistent kernels' per-tile bias partials (tiles,4H), with colsum's partials behind them
+    size_t dx_parts;     //   fp32, 256 -> 256 on the eight-workgroup kernel: the eight partial tapes of dx = dz K^T behind the
+                         //   bias partials; 0 for every other shape
+    size_t total;
+};
+static constexpr size_t kDxTapeFloats = 8 * 256;   // per (sequence, step)
+
+static BwdCarve bwd_carve(int B, int T, int F, int H) {
+    BwdCarve c = {};
+    const size_t bh = (size_t)B * H, db_floats = (size_t)((B + 15) / 16) * 4 * H;
+    c.dh_rec = (kStatusBytes + kXchBytes) / sizeof(float);
+    c.dc = c.dh_rec + bh;
+    c.scratch = c.db_part = c.dc + bh;
+    size_t m = (size_t)64 * (size_t)(F > H ? F : H) * 4 * H;   // split-K partials of dK / dR (<= 64 slices)
+    auto at_least = [&m](size_t floats) { if (floats > m) m = floats; };
+    at_least(db_floats + (size_t)256 * 4 * H);
+    at_least((size_t)8 * bh);                                   // split-K partials of the stepped recurrence's dh GEMM
+    if (F == 256 && H == 256) {
+        c.dx_parts = c.scratch + ((db_floats + 63) & ~(size_t)63);
+        at_least(c.dx_parts - c.scratch + kDxTapeFloats * B * T + 64);
+    }
+    c.total = c.scratch + m + 64;
+    return c;
 }
+
+size_t lstm_bwd_workspace_floats(int B, int T, int F, int H) { return bwd_carve(B, T, F, H).total; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Step-wise layer forward on the matrix-core GEMM, for hidden widths the persistent kernels do not take (H > 256: the
@@ -182,12 +202,47 @@ static int h0_dz0_product(const float* h0, const float* dz, float* dR, int B, in
                 : gemm_f32(gemm_tn(h0, H, dz, (long)T * 4 * H, dR, H, 4 * H, 1, B), 1, scratch, scratch_floats, stream);
 }
 
-// The weight-gradient half of a layer's BPTT, from its dz tape: dK = x^T dz, dR = h_{t-1}^T dz (h_{-1} = h0 or 0), db = colsum(dz).
-// fuse_kr / fuse_r: the adjacent-in-memory forms (one product for all three / for dR and db); db_done: the caller's persistent
-// kernel has produced db already (unfused forms only).
-static int lstm_seq_weight_products(const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db,
-                                    int B, int T, int F, int H, int accumulate, int bf16, bool fuse_kr, bool fuse_r, bool db_done,
-                                    float* scratch, size_t scratch_floats, hipStream_t stream) {
+// The form a layer's weight gradients take, in the order of precedence.  Rows, Grouped: fp32 at few rows, all of a layer's (or of
+// several layers') gradients in one launch of wgrad_group.hip, no split, no reduce.  FusedKR, FusedR: dK, dR, db (dR, db) adjacent
+// in memory - a trainer's flat gradient buffer - as ONE product [x | h_{t-1} | 1]^T dz ([h_{t-1} | 1]^T dz plus dK on its own).
+// Separate: a product each and a column sum.
+enum class WgradForm { Rows, Grouped, FusedKR, FusedR, Separate };
+
+static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Rows: few rows (batch x time <= 640) AND narrow layers (the reference's batch of 32 at H <= 512): wgrad_rows_kernel, 16 x 64
+// tiles, rows split over the waves.  Grouped: batch x time <= 1024 at H >= 512.  Separate: neither.  (db alone rides on neither.)
+static WgradForm plan_few_rows(const LayerWgrad& w, int B, int H, int bf16) {
+    if (bf16 || !(w.dK || w.dR)) return WgradForm::Separate;
+    if (wgrad_rows_takes((long)B * w.T, H) && w.F <= 2048 &&
+        ((((uintptr_t)w.dz) | ((uintptr_t)w.dK) | ((uintptr_t)w.dR) | ((uintptr_t)w.db)) & 15) == 0)
+        return WgradForm::Rows;
+    return wgrad_group_takes(B, w.T, H) && aligned16(w.dz) ? WgradForm::Grouped : WgradForm::Separate;
+}
+
+static WgradForm plan_products(const LayerWgrad& w, int H) {
+    const int F = w.F, N4 = 4 * H;
+    const long T = w.T;
+    if (!w.dR || !w.db || T <= 1 || w.db != w.dR + (size_t)H * N4 || env_knobs().no_wgrad_fusion) return WgradForm::Separate;
+    if (w.dK && w.dR == w.dK + (size_t)F * N4 && wgrad_fusable(w.x, F, T * F, F, w.hs, H, T * H, H, w.dz, N4, T * N4, w.dK, N4))
+        return WgradForm::FusedKR;
+    // F too narrow for a row tile, or dK elsewhere
+    return wgrad_fusable(w.hs, H, T * H, H, nullptr, 0, 0, 0, w.dz, N4, T * N4, w.dR, N4) ? WgradForm::FusedR : WgradForm::Separate;
+}
+
+static WgradForm plan_wgrad(const LayerWgrad& w, int B, int H, int bf16) {
+    const WgradForm few = plan_few_rows(w, B, H, bf16);
+    return few != WgradForm::Separate ? few : plan_products(w, H);
+}
+
+// A layer's products from its dz tape in the form FusedKR, FusedR or Separate; a NULL gradient is skipped (db: the caller's
+// persistent kernel has produced it already).  h_{-1} = 0 in the fused product: a given initial state adds its h0^T dz_0 afterwards.
+static int lstm_seq_weight_products(const LayerWgrad& w, WgradForm form, int B, int H, int accumulate, int bf16, float* scratch,
+                                    size_t scratch_floats, hipStream_t stream) {
+    const float *x = w.x, *hs = w.hs, *h0 = w.h0, *dz = w.dz;
+    float *dK = w.dK, *dR = w.dR, *db = w.db;
+    const int T = w.T, F = w.F;
+    const bool fuse_kr = form == WgradForm::FusedKR, fuse_r = form == WgradForm::FusedR;
     int rc;
     const long BT = (long)B * T;
     if (fuse_kr || fuse_r) {
@@ -219,33 +274,7 @@ static int lstm_seq_weight_products(const float* x, const float* hs, const float
         }
         if (h0 && T > 0 && (rc = h0_dz0_product(h0, dz, dR, B, T, H, bf16, scratch, scratch_floats, stream)) != 0) return rc;
     }
-    return (db && !db_done) ? colsum(dz, db, BT, 4 * H, accumulate, scratch, scratch_floats, stream) : FOV_OK;
-}
-
-// few rows (batch x time <= ~1000), fp32: all of a layer's weight gradients by wgrad_group.hip - one launch, no split, no reduce
-static bool lstm_seq_wgrad_grouped(int bf16, int B, int T, int H, const float* dz, float* dK, float* dR, float* db) {
-    return !bf16 && wgrad_group_takes(B, T, H) && (dK || dR) && (((uintptr_t)dz) & 15) == 0 && (!db || dK || dR);
-}
-
-// few rows AND narrow layers (the reference's batch of 32 at H <= 256): wgrad_rows_kernel, 16 x 64 tiles, rows split over the waves
-static bool lstm_seq_wgrad_rows(int bf16, int B, int T, int F, int H, const float* dz, float* dK, float* dR, float* db) {
-    return !bf16 && wgrad_rows_takes((long)B * T, H) && F <= 2048 && (dK || dR) && (!db || dK || dR) &&
-           ((((uintptr_t)dz) | ((uintptr_t)dK) | ((uintptr_t)dR) | ((uintptr_t)db)) & 15) == 0;
-}
-
-static int wgrad_few_rows(bool rows_form, const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db,
-                          int B, int T, int F, int H, int accumulate, hipStream_t stream) {
-    return rows_form ? wgrad_rows_layers(1, &x, &F, &T, &hs, &h0, &dz, &dK, &dR, &db, B, H, accumulate, stream)
-                     : wgrad_group_layers(1, &x, &F, &hs, &h0, &dz, &dK, &dR, &db, B, T, H, accumulate, stream);
-}
-
-static void lstm_seq_wgrad_fusion(const float* x, const float* hs, const float* dz, float* dK, float* dR, float* db, int T, int F, int H,
-                                  bool* fuse_kr, bool* fuse_r) {
-    const int N4 = 4 * H;
-    *fuse_kr = dK && dR && db && T > 1 && dR == dK + (size_t)F * N4 && db == dR + (size_t)H * N4 &&
-               wgrad_fusable(x, F, (long)T * F, F, hs, H, (long)T * H, H, dz, N4, (long)T * N4, dK, N4) && !env_knobs().no_wgrad_fusion;
-    *fuse_r = !*fuse_kr && dR && db && T > 1 && db == dR + (size_t)H * N4 &&
-              wgrad_fusable(hs, H, (long)T * H, H, nullptr, 0, 0, 0, dz, N4, (long)T * N4, dR, N4) && !env_knobs().no_wgrad_fusion;
+    return db ? colsum(dz, db, BT, 4 * H, accumulate, scratch, scratch_floats, stream) : FOV_OK;
 }
 
 // accumulate = 0 on an empty batch or sequence: dK (F,4H), dR (H,4H), db (4H) = 0 (NULL ones are skipped)
@@ -256,162 +285,159 @@ int zero_lstm_wgrads(float* dK, float* dR, float* db, int F, int H, hipStream_t 
     return rc;
 }
 
-// Weight gradients of one layer from a dz tape its BPTT left behind (fov_lstm_seq_bwd* with dK = dR = db = NULL): lets a trainer
-// put a layer's products on another stream than the next layer's recurrence.  Same arithmetic, same order as inside lstm_seq_bwd.
-int lstm_seq_wgrad(const float* x, const float* hs, const float* h0, const float* dz, float* dK, float* dR, float* db, int B, int T,
-                   int F, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream) {
-    if (bf16 && H != 256) { set_error("lstm_seq_wgrad: the bf16 path is built for H = 256"); return FOV_ERR_UNSUPPORTED; }
-    if (T == 0 || B == 0) {
-        if (!accumulate)
-            if (int rc = zero_lstm_wgrads(dK, dR, db, F, H, stream)) return rc;
-        return FOV_OK;
-    }
-    const bool rows_form = lstm_seq_wgrad_rows(bf16, B, T, F, H, dz, dK, dR, db);
-    if (rows_form || lstm_seq_wgrad_grouped(bf16, B, T, H, dz, dK, dR, db))
-        return wgrad_few_rows(rows_form, x, hs, h0, dz, dK, dR, db, B, T, F, H, accumulate, stream);
-    bool fuse_kr, fuse_r;
-    lstm_seq_wgrad_fusion(x, hs, dz, dK, dR, db, T, F, H, &fuse_kr, &fuse_r);
-    return lstm_seq_weight_products(x, hs, h0, dz, dK, dR, db, B, T, F, H, accumulate, bf16, fuse_kr, fuse_r, false, scratch,
-                                    scratch_floats, stream);
+// one layer's weight gradients in the form planned for it
+static int run_wgrad(const LayerWgrad& w, WgradForm form, int B, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats,
+                     hipStream_t stream) {
+    if (w.T == 0 || B == 0) return accumulate ? FOV_OK : zero_lstm_wgrads(w.dK, w.dR, w.db, w.F, H, stream);
+    if (form == WgradForm::Rows) return wgrad_rows_layers(1, &w, B, H, accumulate, stream);
+    if (form == WgradForm::Grouped) return wgrad_group_layers(1, &w, B, H, accumulate, stream);
+    return lstm_seq_weight_products(w, form, B, H, accumulate, bf16, scratch, scratch_floats, stream);
 }
 
-// Weight gradients of TWO layers that share the batch but not the time length (an encoder and its decoder: FoV_seq2seq.py:68-93)
-// from the dz tapes their BPTT calls left.  At the reference's batch all six gradients are ONE launch (wgrad_rows_kernel).
+// Weight gradients of one layer from a dz tape its BPTT left behind (fov_lstm_seq_bwd* with dK = dR = db = NULL): lets a trainer
+// put a layer's products on another stream than the next layer's recurrence.  Same arithmetic, same order as inside lstm_seq_bwd.
+int lstm_seq_wgrad(const LayerWgrad& w, int B, int H, int accumulate, int bf16, float* scratch, size_t scratch_floats, hipStream_t stream) {
+    if (bf16 && H != 256) { set_error("lstm_seq_wgrad: the bf16 path is built for H = 256"); return FOV_ERR_UNSUPPORTED; }
+    return run_wgrad(w, plan_wgrad(w, B, H, bf16), B, H, accumulate, bf16, scratch, scratch_floats, stream);
+}
+
+// TWO layers that share the batch but not the time length (an encoder and its decoder: FoV_seq2seq.py:68-93): at the reference's
+// batch all six gradients are ONE launch (wgrad_rows_kernel)
 bool lstm_seq_wgrad_pair_one_launch(int B, int T1, int T2, int H) {
     return T1 > 0 && T2 > 0 && wgrad_rows_takes((long)B * (T1 > T2 ? T1 : T2), H);
 }
 
-int lstm_seq_wgrad_pair(const float* x1, const float* hs1, const float* h0_1, const float* dz1, float* dK1, float* dR1, float* db1, int T1, int F1,
-                        const float* x2, const float* hs2, const float* h0_2, const float* dz2, float* dK2, float* dR2, float* db2, int T2, int F2,
-                        int B, int H, int accumulate, float* scratch, size_t scratch_floats, hipStream_t stream) {
-    if (B > 0 && T1 > 0 && T2 > 0 && lstm_seq_wgrad_rows(0, B, T1, F1, H, dz1, dK1, dR1, db1) && lstm_seq_wgrad_rows(0, B, T2, F2, H, dz2, dK2, dR2, db2)) {
-        const float* xs[2] = {x1, x2};
-        const int Fs[2] = {F1, F2}, Ts[2] = {T1, T2};
-        const float* hss[2] = {hs1, hs2};
-        const float* h0s[2] = {h0_1, h0_2};
-        const float* dzs[2] = {dz1, dz2};
-        float* dKs[2] = {dK1, dK2};
-        float* dRs[2] = {dR1, dR2};
-        float* dbs[2] = {db1, db2};
-        return wgrad_rows_layers(2, xs, Fs, Ts, hss, h0s, dzs, dKs, dRs, dbs, B, H, accumulate, stream);
+// Weight gradients of an encoder / decoder pair or of the layers of a STACK (Fov_seq2seq_2layers.py:232-272: up to four layers that
+// share the batch and the width, each with its own input width and time length) from their dz tapes, fp32.  One launch
+// (wgrad_rows_kernel) when the rows form takes every layer; else each layer in its own form.  A workgroup of that kernel owns one
+// output tile of one problem whatever else shares the launch, so both ways give the bits of the per-layer calls.
+int lstm_seq_wgrad_layers(int L, const LayerWgrad* w, int B, int H, int accumulate, float* scratch, size_t scratch_floats,
+                          hipStream_t stream) {
+    WgradForm form[kMaxWgradLayers];      // L <= kMaxWgradLayers: the entry points check
+    bool all_rows = true;
+    for (int l = 0; l < L; ++l) {
+        form[l] = plan_wgrad(w[l], B, H, 0);
+        all_rows = all_rows && form[l] == WgradForm::Rows;
     }
-    int rc = lstm_seq_wgrad(x1, hs1, h0_1, dz1, dK1, dR1, db1, B, T1, F1, H, accumulate, 0, scratch, scratch_floats, stream);
-    if (rc) return rc;
-    return lstm_seq_wgrad(x2, hs2, h0_2, dz2, dK2, dR2, db2, B, T2, F2, H, accumulate, 0, scratch, scratch_floats, stream);
+    if (all_rows) return wgrad_rows_layers(L, w, B, H, accumulate, stream);
+    for (int l = 0; l < L; ++l)
+        if (int rc = run_wgrad(w[l], form[l], B, H, accumulate, 0, scratch, scratch_floats, stream)) return rc;
+    return FOV_OK;
 }
 
-// Weight gradients of the layers of a STACK (Fov_seq2seq_2layers.py:232-272: up to four layers that share the batch and the width,
-// each with its own input width and time length) from their dz tapes.  One launch (wgrad_rows_kernel) when the few-row form takes
-// every layer; else a lstm_seq_wgrad per layer.  A workgroup of that kernel owns one output tile of one problem whatever else
-// shares the launch, so both ways give the bits of the per-layer calls.
-int lstm_seq_wgrad_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
-                          const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate,
-                          float* scratch, size_t scratch_floats, hipStream_t stream) {
-    bool rows_form = B > 0;
-    for (int l = 0; l < L && rows_form; ++l) rows_form = T[l] > 0 && lstm_seq_wgrad_rows(0, B, T[l], F[l], H, dz[l], dK[l], dR[l], db[l]);
-    if (rows_form) return wgrad_rows_layers(L, x, F, T, hs, h0, dz, dK, dR, db, B, H, accumulate, stream);
-    for (int l = 0; l < L; ++l)
-        if (int rc = lstm_seq_wgrad(x[l], hs[l], h0[l], dz[l], dK[l], dR[l], db[l], B, T[l], F[l], H, accumulate, 0, scratch, scratch_floats, stream))
-            return rc;
-    return FOV_OK;
+// How one layer's BPTT is executed, decided in one place from the layer's shape, its pointers and the knobs.
+enum class BwdRecurrence {
+    Bwd16,     // lstm_bwd16.hip (fp32, R 16-byte aligned): width 512, small batches at 128 / 256
+    Bwd8,      // lstm_bwd8.hip: H = 256 up to 32 tiles (groups of eight workgroups fill the chip where the 4-group kernel leaves
+               // half of it idle at 512 sequences) unless FOV_BWD_GROUPS4; bf16 operands exist in this kernel only
+    Cluster,   // lstm_bwd_cluster.hip: H = 64 / 128 / 256
+    Stepped    // other widths, a misaligned R at width 512, FOV_BWD_STEPPED: a pointwise launch and a GEMM per step
+};
+enum class DxSource {
+    None,            // the caller wants no dx
+    InKernel,        // bf16, 256-wide input (the stacked layer): the kernel forms dx = dz K^T from the dz tile it has gathered anyway
+    InKernelParts,   // fp32 on the eight-workgroup kernel, 256 -> 256: every workgroup forms its gate columns' share of dx in the
+                     // shadow of the exchange - eight partial tapes in the scratch, one reduce launch
+    Gemm             // a product behind the weight gradients
+};
+struct BwdPlan {
+    BwdRecurrence rec;
+    WgradForm wgrad;   // a stepped recurrence takes the separate products; Rows and Grouped go before the fusions
+    bool db_part;      // the persistent kernel writes per-tile bias partials and a column sum follows: db wanted, form Separate
+    DxSource dx;
+    BwdCarve carve;
+};
+
+static BwdPlan plan_lstm_bwd(const LstmBwdLayer& l) {
+    const EnvKnobs& knobs = env_knobs();
+    BwdPlan p = {};
+    p.carve = bwd_carve(l.B, l.T, l.F, l.H);
+    const bool wide16 = !l.bf16 && bwd16_takes(l.B, l.H) && aligned16(l.rec.R);
+    p.rec = (knobs.bwd_stepped || !(wide16 || bwd_cluster_shape_ok(l.H))) ? BwdRecurrence::Stepped
+            : wide16                                                       ? BwdRecurrence::Bwd16
+            : (l.bf16 || (bwd8_preferred(l.B, l.H) && !knobs.bwd_groups4)) ? BwdRecurrence::Bwd8
+                                                                           : BwdRecurrence::Cluster;
+    const bool persistent = p.rec != BwdRecurrence::Stepped;
+    p.wgrad = persistent ? plan_wgrad(l.wg, l.B, l.H, l.bf16) : WgradForm::Separate;
+    p.db_part = persistent && l.wg.db && p.wgrad == WgradForm::Separate;
+    const bool dx_in_bwd8 = p.rec == BwdRecurrence::Bwd8 && l.F == 256 && aligned16(l.K) && !knobs.no_dx_fusion;
+    p.dx = !l.dx                                                 ? DxSource::None
+           : dx_in_bwd8 && l.bf16                                ? DxSource::InKernel
+           : dx_in_bwd8 && p.carve.dx_parts && aligned16(l.dx)   ? DxSource::InKernelParts
+                                                                 : DxSource::Gemm;
+    return p;
 }
 
 // BPTT of one layer.  dz:(B,T,4H) is an output (kept: the caller may need it for dx of the layer
 // below).  dK,dR,db are overwritten (accumulate = 0) or added to (accumulate = 1).
-int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0, const float* c0, const float* hs,
-                 const float* reserve, const float* dhs, const float* dhT, const float* dcT, float* dz, float* dx,
-                 float* dK, float* dR, float* db, float* dh0, float* dc0, int B, int T, int F, int H, int act,
-                 int accumulate, float* ws, size_t ws_floats, hipStream_t stream, int bf16) {
+int lstm_seq_bwd(const LstmBwdLayer& l, float* ws, size_t ws_floats, hipStream_t stream) {
+    const int B = l.B, T = l.T, F = l.F, H = l.H, accumulate = l.accumulate, bf16 = l.bf16;
     if (bf16 && H != 256) { set_error("lstm_seq_bwd: the bf16 path is built for H = 256"); return FOV_ERR_UNSUPPORTED; }
-    if (ws_floats < lstm_bwd_workspace_floats(B, T, F, H)) { set_error("lstm_seq_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    const BwdPlan plan = plan_lstm_bwd(l);
+    if (ws_floats < plan.carve.total) { set_error("lstm_seq_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    BwdRec r = l.rec;
+    LayerWgrad wg = l.wg;
+    const size_t bh = sizeof(float) * (size_t)B * H;
     if (T == 0) {
         if (!accumulate)
-            if (int rc = zero_lstm_wgrads(dK, dR, db, F, H, stream)) return rc;
-        const size_t bh0 = sizeof(float) * (size_t)B * H;
-        if (dh0) (void)(dhT ? hipMemcpyAsync(dh0, dhT, bh0, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dh0, 0, bh0, stream));
-        if (dc0) (void)(dcT ? hipMemcpyAsync(dc0, dcT, bh0, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dc0, 0, bh0, stream));
+            if (int rc = zero_lstm_wgrads(wg.dK, wg.dR, wg.db, F, H, stream)) return rc;
+        if (r.dh0) (void)(r.dhT ? hipMemcpyAsync(r.dh0, r.dhT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(r.dh0, 0, bh, stream));
+        if (r.dc0) (void)(r.dcT ? hipMemcpyAsync(r.dc0, r.dcT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(r.dc0, 0, bh, stream));
         return FOV_OK;
     }
-    const bool wide16 = !bf16 && bwd16_takes(B, H) && (((uintptr_t)R) & 15) == 0;   // width 512, small batches at 128 / 256: lstm_bwd16.hip
-    const bool persistent = (bwd_cluster_shape_ok(H) || wide16) && !env_knobs().bwd_stepped;
-    bool fuse_kr = false, fuse_r = false, dx_in_kernel = false, grouped = false, rows_form = false;
-    const size_t head = (kStatusBytes + kXchBytes) / sizeof(float);
-    float* dh_rec = ws + head;
-    float* dc = dh_rec + (size_t)B * H;
-    float* scratch = dc + (size_t)B * H;
-    const size_t scratch_floats = ws_floats - head - (size_t)2 * B * H;
-    const size_t bh = sizeof(float) * (size_t)B * H;
-    hipError_t e = hipSuccess;
-    if (persistent) {
+    float *dh_rec = ws + plan.carve.dh_rec, *dc = ws + plan.carve.dc, *scratch = ws + plan.carve.scratch;
+    const size_t scratch_floats = ws_floats - plan.carve.scratch;
+    int rc;
+    if (plan.rec != BwdRecurrence::Stepped) {
         // one launch for the whole recurrence: dz (B,T,4H), dh0, dc0
-        // bias gradient: per-tile partials from the kernel (db_part lives in the split-K scratch), summed below
-        // dK, dR, db adjacent (a trainer's flat gradient buffer): ONE product [x | h_{t-1} | 1]^T dz (h_{-1} = 0; a given initial
-        // state adds its h0^T dz_0 afterwards)
-        // below gives all three (no bias partials from the kernel, no column-sum launches); F too narrow for a row tile:
-        // [h_{t-1} | 1]^T dz gives dR and db
-        lstm_seq_wgrad_fusion(x, hs, dz, dK, dR, db, T, F, H, &fuse_kr, &fuse_r);
-        rows_form = lstm_seq_wgrad_rows(bf16, B, T, F, H, dz, dK, dR, db);
-        grouped = rows_form || lstm_seq_wgrad_grouped(bf16, B, T, H, dz, dK, dR, db);
-        if (grouped) fuse_kr = fuse_r = false;
-        float* db_part = (db && !fuse_kr && !fuse_r && !grouped) ? scratch : nullptr;
-        // bf16, 256-wide input (the stacked layer): the BPTT kernel forms dx = dz K^T from the dz tile it has gathered anyway
-        dx_in_kernel = bf16 && dx && F == 256 && (((uintptr_t)K) & 15) == 0 && !env_knobs().no_dx_fusion;
-        // fp32 on the eight-workgroup kernel (round 5): every workgroup forms its gate columns' share of dx in the shadow of the
-        // exchange; eight partial tapes in the scratch, one reduce launch (was: a GEMM + reduce behind the recurrence)
-        const bool on_bwd8 = !wide16 && !bf16 && bwd8_preferred(B, H) && !env_knobs().bwd_groups4;
-        float* dx_parts = nullptr;
-        if (on_bwd8 && dx && F == 256 && (((uintptr_t)K) & 15) == 0 && (((uintptr_t)dx) & 15) == 0 && !env_knobs().no_dx_fusion) {
-            const size_t off = ((size_t)((B + 15) / 16) * 4 * H + 63) & ~(size_t)63;      // behind the db partials
-            if (off + (size_t)8 * B * T * 256 <= scratch_floats) { dx_parts = scratch + off; dx_in_kernel = true; }
-        }
-        // H = 256: groups of eight workgroups fill the chip up to 32 tiles (the 4-group kernel leaves half of it idle
-        // at 512 sequences); bf16 operands exist in the 8-group kernel only
-        if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] lstm_seq_bwd B=%d T=%d F=%d H=%d wide16=%d fuse_kr=%d fuse_r=%d grouped=%d acc=%d: recurrence next\n", B, T, F, H, (int)wide16, (int)fuse_kr, (int)fuse_r, (int)grouped, accumulate);
-        int rc = wide16 ? launch_bwd16(R, reserve, c0, dhs, dhT, dcT, dz, dh0 ? dh0 : dh_rec, dc0 ? dc0 : dc, db_part, B, T, H, act, ws, stream)
-                 : (bf16 || (bwd8_preferred(B, H) && !env_knobs().bwd_groups4))
-                     ? launch_bwd8(R, reserve, c0, dhs, dhT, dcT, dz, dh0 ? dh0 : dh_rec, dc0 ? dc0 : dc, db_part, B, T, act, bf16, ws, stream,
-                                   dx_in_kernel ? K : nullptr, dx_in_kernel ? (dx_parts ? dx_parts : dx) : nullptr)
-                     : launch_bwd_cluster(R, reserve, c0, dhs, dhT, dcT, dz, dh0 ? dh0 : dh_rec, dc0 ? dc0 : dc, db_part, B, T, H,
-                                          act, ws, stream);
+        if (!r.dh0) r.dh0 = dh_rec;
+        if (!r.dc0) r.dc0 = dc;
+        r.db_part = plan.db_part ? ws + plan.carve.db_part : nullptr;
+        float* dx_parts = plan.dx == DxSource::InKernelParts ? ws + plan.carve.dx_parts : nullptr;
+        float* dx_out = dx_parts ? dx_parts : plan.dx == DxSource::InKernel ? l.dx : nullptr;
+        if (env_knobs().dbg_trace)
+            fprintf(stderr, "[fov trace] lstm_seq_bwd B=%d T=%d F=%d H=%d wide16=%d fuse_kr=%d fuse_r=%d grouped=%d acc=%d: recurrence next\n", B, T, F, H,
+                    plan.rec == BwdRecurrence::Bwd16, plan.wgrad == WgradForm::FusedKR, plan.wgrad == WgradForm::FusedR, plan.wgrad <= WgradForm::Grouped, accumulate);
+        rc = plan.rec == BwdRecurrence::Bwd16  ? launch_bwd16(r, B, T, H, l.act, ws, stream)
+             : plan.rec == BwdRecurrence::Bwd8 ? launch_bwd8(r, B, T, l.act, bf16, ws, stream, dx_out ? l.K : nullptr, dx_out)
+                                               : launch_bwd_cluster(r, B, T, H, l.act, ws, stream);
         if (rc) return rc;
         if (dx_parts) {      // dx = the eight workgroups' shares in slice order (before anything else touches the scratch)
-            rc = splitk_reduce(dx_parts, dx, (long)B * T * 256, 8, 0, stream);
+            rc = splitk_reduce(dx_parts, l.dx, (long)B * T * 256, 8, 0, stream);
             if (rc) return rc;
         }
         if (env_knobs().dbg_trace) fprintf(stderr, "[fov trace] lstm_seq_bwd: recurrence done\n");
-        if (db_part) {
+        if (r.db_part) {     // db = the column sum of the tiles' partials; colsum's own partials behind them
             const int tiles = (B + 15) / 16;
-            if ((size_t)tiles * 4 * H + (size_t)256 * 4 * H > scratch_floats) { set_error("lstm_seq_bwd: scratch too small for db"); return FOV_ERR_WORKSPACE; }
-            rc = colsum(db_part, db, tiles, 4 * H, accumulate, scratch + (size_t)tiles * 4 * H,
-                        scratch_floats - (size_t)tiles * 4 * H, stream);
+            const size_t part_floats = (size_t)tiles * 4 * H;
+            rc = colsum(r.db_part, wg.db, tiles, 4 * H, accumulate, scratch + part_floats, scratch_floats - part_floats, stream);
             if (rc) return rc;
+            wg.db = nullptr;
         }
     } else {
-        e = dhT ? hipMemcpyAsync(dh_rec, dhT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dh_rec, 0, bh, stream);
-        if (e == hipSuccess) e = dcT ? hipMemcpyAsync(dc, dcT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dc, 0, bh, stream);
+        hipError_t e = r.dhT ? hipMemcpyAsync(dh_rec, r.dhT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dh_rec, 0, bh, stream);
+        if (e == hipSuccess) e = r.dcT ? hipMemcpyAsync(dc, r.dcT, bh, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dc, 0, bh, stream);
         if (e != hipSuccess) { set_error("lstm_seq_bwd init: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
         const long nelem = (long)B * H;
         const dim3 pgrid((unsigned)((nelem + 255) / 256));
-        const auto pointwise = act == FOV_ACT_HARD_SIGMOID ? lstm_bwd_pointwise<FOV_ACT_HARD_SIGMOID> : lstm_bwd_pointwise<FOV_ACT_SIGMOID>;
+        const auto pointwise = l.act == FOV_ACT_HARD_SIGMOID ? lstm_bwd_pointwise<FOV_ACT_HARD_SIGMOID> : lstm_bwd_pointwise<FOV_ACT_SIGMOID>;
         for (int t = T - 1; t >= 0; --t) {
-            hipLaunchKernelGGL(pointwise, pgrid, dim3(256), 0, stream, reserve, c0, dhs, dh_rec, dc, dz, B, T, H, t);
-            int rc = launch_check("lstm_bwd_pointwise");
+            hipLaunchKernelGGL(pointwise, pgrid, dim3(256), 0, stream, r.reserve, r.c0, r.dhs, dh_rec, dc, r.dz, B, T, H, t);
+            rc = launch_check("lstm_bwd_pointwise");
             if (rc) return rc;
             // dh_rec (B,H) = dz_t (B,4H) . R^T :  A(m,k) = dz[m][t][k], B(k,n) = R[n][k]
-            rc = gemm_f32(gemm_nt(dz + (size_t)t * 4 * H, (long)T * 4 * H, R, 4 * H, dh_rec, H, B, H, 4 * H), 0, scratch, scratch_floats, stream);
+            rc = gemm_f32(gemm_nt(r.dz + (size_t)t * 4 * H, (long)T * 4 * H, r.R, 4 * H, dh_rec, H, B, H, 4 * H), 0, scratch, scratch_floats, stream);
             if (rc) return rc;
         }
-        if (dh0) { e = hipMemcpyAsync(dh0, dh_rec, bh, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { set_error("dh0 copy"); return FOV_ERR_LAUNCH; } }
-        if (dc0) { e = hipMemcpyAsync(dc0, dc, bh, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { set_error("dc0 copy"); return FOV_ERR_LAUNCH; } }
+        if (r.dh0) { e = hipMemcpyAsync(r.dh0, dh_rec, bh, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { set_error("dh0 copy"); return FOV_ERR_LAUNCH; } }
+        if (r.dc0) { e = hipMemcpyAsync(r.dc0, dc, bh, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { set_error("dc0 copy"); return FOV_ERR_LAUNCH; } }
     }
-    int rc = grouped ? wgrad_few_rows(rows_form, x, hs, h0, dz, dK, dR, db, B, T, F, H, accumulate, stream)
-                     : lstm_seq_weight_products(x, hs, h0, dz, dK, dR, db, B, T, F, H, accumulate, bf16, fuse_kr, fuse_r, /*db_done=*/persistent,
-                                                scratch, scratch_floats, stream);
+    rc = run_wgrad(wg, plan.wgrad, B, H, accumulate, bf16, scratch, scratch_floats, stream);
     if (rc) return rc;
-    if (dx && !dx_in_kernel) {   // dx (B*T,F) = dz . K^T : A(m,k) = dz[m][k], B(k,n) = K[n][k]
+    if (plan.dx == DxSource::Gemm) {   // dx (B*T,F) = dz . K^T : A(m,k) = dz[m][k], B(k,n) = K[n][k]
         const long BT = (long)B * T;
-        rc = (bf16 && (((uintptr_t)K) & 15) == 0) ? gemm_bf16_nt(dz, 4 * H, K, 4 * H, dx, F, (int)BT, F, 4 * H, stream)
-                                                 : gemm_f32(gemm_nt(dz, 4 * H, K, 4 * H, dx, F, (int)BT, F, 4 * H), 0, scratch, scratch_floats, stream);
+        rc = (bf16 && aligned16(l.K)) ? gemm_bf16_nt(r.dz, 4 * H, l.K, 4 * H, l.dx, F, (int)BT, F, 4 * H, stream)
+                                      : gemm_f32(gemm_nt(r.dz, 4 * H, l.K, 4 * H, l.dx, F, (int)BT, F, 4 * H), 0, scratch, scratch_floats, stream);
         if (rc) return rc;
     }
     return FOV_OK;
@@ -420,61 +446,57 @@ int lstm_seq_bwd(const float* x, const float* K, const float* R, const float* h0
 // BPTT of two stacked width-512 layers in ONE launch (lstm_bwd16.hip: both recurrences and dx = dz2 . K2^T between them as three
 // roles of one persistent kernel), then the two layers' weight-gradient products.  Same outputs as two lstm_seq_bwd calls
 // (upper layer first, its dx as the lower layer's dhs) except that the intermediate dx is not materialised.
-size_t lstm_stack2_bwd_workspace_floats(int B, int T, int F, int H) {
-    const size_t tiles = (size_t)(B + 15) / 16;
-    return lstm_bwd_workspace_floats(B, T, F > H ? F : H, H) + 2 * tiles * 4 * H + (size_t)4 * B * H + 64;
+// The workspace: behind the header and the granule area the two layers' bias partials and four (B,H) of state gradients the
+// caller does not ask for, then the scratch - what one layer's call with the wider of the two inputs has behind its header.
+struct Stack2Carve {
+    size_t db_part_up, db_part_low, spare, scratch, total;
+};
+static Stack2Carve stack2_carve(int B, int T, int F, int H) {
+    Stack2Carve c = {};
+    const size_t part_floats = (size_t)((B + 15) / 16) * 4 * H;
+    const BwdCarve one = bwd_carve(B, T, F > H ? F : H, H);
+    c.db_part_up = one.dh_rec;
+    c.db_part_low = c.db_part_up + part_floats;
+    c.spare = c.db_part_low + part_floats;
+    c.scratch = c.spare + (size_t)4 * B * H;
+    c.total = c.scratch + (one.total - one.dh_rec) + 64;
+    return c;
 }
 
-int lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const float* R2, const float* h0_1, const float* c0_1,
-                    const float* h0_2, const float* c0_2, const float* hs1, const float* res1, const float* hs2, const float* res2,
-                    const float* dhs2, const float* dhT2, const float* dcT2, const float* dhT1, const float* dcT1, float* dz1, float* dz2,
-                    float* dK1, float* dR1, float* db1, float* dK2, float* dR2, float* db2, float* dh0_1, float* dc0_1, float* dh0_2,
-                    float* dc0_2, int B, int T, int F, int H, int act, int accumulate, float* ws, size_t ws_floats, hipStream_t stream) {
+size_t lstm_stack2_bwd_workspace_floats(int B, int T, int F, int H) { return stack2_carve(B, T, F, H).total; }
+
+int lstm_stack2_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up, float* ws, size_t ws_floats, hipStream_t stream) {
+    const int B = low.B, T = low.T, H = low.H, accumulate = low.accumulate;
     if (!bwd16_pair_shape(B, T, H)) { set_error("lstm_stack2_bwd: unsupported shape (H = 512, <= 32 sequences on 256 CUs)"); return FOV_ERR_UNSUPPORTED; }
-    if (ws_floats < lstm_stack2_bwd_workspace_floats(B, T, F, H)) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
-    const size_t head = (kStatusBytes + kXchBytes) / sizeof(float);
-    const size_t tiles = (size_t)(B + 15) / 16, bh = (size_t)B * H;
-    float* dbp2 = ws + head;
-    float* dbp1 = dbp2 + tiles * 4 * H;
-    float* spare = dbp1 + tiles * 4 * H;          // state gradients the caller does not ask for
-    float* scratch = spare + 4 * bh;
-    const size_t scratch_floats = ws_floats - head - 2 * tiles * 4 * H - 4 * bh;
-    bool kr1, r1, kr2, r2;
-    lstm_seq_wgrad_fusion(x, hs1, dz1, dK1, dR1, db1, T, F, H, &kr1, &r1);
-    lstm_seq_wgrad_fusion(hs1, hs2, dz2, dK2, dR2, db2, T, H, H, &kr2, &r2);
-    // few rows: ALL weight gradients of both layers in one launch behind the recurrences (wgrad_group.hip)
-    const bool rows_form = lstm_seq_wgrad_rows(0, B, T, F, H, dz1, dK1, dR1, db1) && lstm_seq_wgrad_rows(0, B, T, H, H, dz2, dK2, dR2, db2);
-    const bool grouped = rows_form || (lstm_seq_wgrad_grouped(0, B, T, H, dz1, dK1, dR1, db1) && lstm_seq_wgrad_grouped(0, B, T, H, dz2, dK2, dR2, db2));
-    if (grouped) kr1 = r1 = kr2 = r2 = true;      // (no bias partials from the kernel)
-    float* db_part1 = (db1 && !kr1 && !r1) ? dbp1 : nullptr;
-    float* db_part2 = (db2 && !kr2 && !r2) ? dbp2 : nullptr;
-    int rc = launch_bwd16_pair(R2, K2, res2, c0_2, dhs2, dhT2, dcT2, dz2, dh0_2 ? dh0_2 : spare, dc0_2 ? dc0_2 : spare + bh, db_part2, R1,
-                               res1, c0_1, dhT1, dcT1, dz1, dh0_1 ? dh0_1 : spare + 2 * bh, dc0_1 ? dc0_1 : spare + 3 * bh, db_part1, B,
-                               T, act, ws, stream);
-    if (rc) return rc;
-    if (grouped) {
-        const float* xs[2] = {x, hs1};
-        const int Fs[2] = {F, H};
-        const float* hss[2] = {hs1, hs2};
-        const float* h0s[2] = {h0_1, h0_2};
-        const float* dzs[2] = {dz1, dz2};
-        float* dKs[2] = {dK1, dK2};
-        float* dRs[2] = {dR1, dR2};
-        float* dbs[2] = {db1, db2};
-        const int Ts[2] = {T, T};
-        return rows_form ? wgrad_rows_layers(2, xs, Fs, Ts, hss, h0s, dzs, dKs, dRs, dbs, B, H, accumulate, stream)
-                         : wgrad_group_layers(2, xs, Fs, hss, h0s, dzs, dKs, dRs, dbs, B, T, H, accumulate, stream);
+    const Stack2Carve carve = stack2_carve(B, T, low.F, H);
+    if (ws_floats < carve.total) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    const size_t bh = (size_t)B * H;
+    float *spare = ws + carve.spare, *scratch = ws + carve.scratch;
+    const size_t scratch_floats = ws_floats - carve.scratch;
+    LayerWgrad wg[2] = {low.wg, up.wg};
+    // few rows: ALL weight gradients of both layers in one launch behind the recurrences (wgrad_group.hip; at this width a layer
+    // the rows form takes, the grouped form takes too); else each layer's products, no few-row form for one layer alone
+    WgradForm form[2] = {plan_few_rows(wg[0], B, H, 0), plan_few_rows(wg[1], B, H, 0)};
+    const bool rows_form = form[0] == WgradForm::Rows && form[1] == WgradForm::Rows;
+    const bool grouped = form[0] != WgradForm::Separate && form[1] != WgradForm::Separate;
+    if (!grouped)
+        for (int i = 0; i < 2; ++i) form[i] = plan_products(wg[i], H);
+    BwdRec r[2] = {low.rec, up.rec};
+    for (int i = 0; i < 2; ++i) {
+        if (!r[i].dh0) r[i].dh0 = spare + (size_t)(2 - 2 * i) * bh;
+        if (!r[i].dc0) r[i].dc0 = spare + (size_t)(3 - 2 * i) * bh;
+        r[i].db_part = (!grouped && wg[i].db && form[i] == WgradForm::Separate) ? ws + (i ? carve.db_part_up : carve.db_part_low) : nullptr;
     }
-    for (int l = 2; l >= 1; --l) {
-        float* part = l == 2 ? db_part2 : db_part1;
-        float* db = l == 2 ? db2 : db1;
-        if (part) {
-            if (tiles * 4 * H + (size_t)256 * 4 * H > scratch_floats) { set_error("lstm_stack2_bwd: scratch too small for db"); return FOV_ERR_WORKSPACE; }
-            rc = colsum(part, db, (long)tiles, 4 * H, accumulate, scratch, scratch_floats, stream);
+    int rc = launch_bwd16_pair(r[1], r[0], up.K, B, T, low.act, ws, stream);
+    if (rc) return rc;
+    if (grouped) return rows_form ? wgrad_rows_layers(2, wg, B, H, accumulate, stream) : wgrad_group_layers(2, wg, B, H, accumulate, stream);
+    for (int i = 1; i >= 0; --i) {
+        if (r[i].db_part) {
+            rc = colsum(r[i].db_part, wg[i].db, (long)((B + 15) / 16), 4 * H, accumulate, scratch, scratch_floats, stream);
             if (rc) return rc;
+            wg[i].db = nullptr;
         }
-        rc = l == 2 ? lstm_seq_weight_products(hs1, hs2, h0_2, dz2, dK2, dR2, db2, B, T, H, H, accumulate, 0, kr2, r2, true, scratch, scratch_floats, stream)
-                    : lstm_seq_weight_products(x, hs1, h0_1, dz1, dK1, dR1, db1, B, T, F, H, accumulate, 0, kr1, r1, true, scratch, scratch_floats, stream);
+        rc = lstm_seq_weight_products(wg[i], form[i], B, H, accumulate, 0, scratch, scratch_floats, stream);
         if (rc) return rc;
     }
     return FOV_OK;

@@ -506,28 +506,30 @@ bool wgrad_group_takes(int B, int T, int H) {
 // Weight gradients of up to four layers in one launch.  Layer l: x_l (B,T,F_l), hs_l (B,T,H), optional h0_l (B,H), dz_l (B,T,4H) ->
 // dK_l (F_l,4H), dR_l (H,4H), db_l (4H); any of dK / dR / db may be NULL (db alone is not supported: it rides on dR's launch
 // blocks, or on dK's when dR is NULL).
-int wgrad_group_layers(int L, const float* const* x, const int* F, const float* const* hs, const float* const* h0, const float* const* dz,
-                       float* const* dK, float* const* dR, float* const* db, int B, int T, int H, int accumulate, hipStream_t stream) {
+int wgrad_group_layers(int L, const LayerWgrad* layers, int B, int H, int accumulate, hipStream_t stream) {
     if (L < 1 || 2 * L > kMaxProb) { set_error("wgrad_group: at most %d layers", kMaxProb / 2); return FOV_ERR_INVALID; }
+    const int T = layers[0].T;
     WgBatch g = {};
     g.RO = B; g.RI = T; g.accumulate = accumulate ? 1 : 0;
     g.ri_magic = T <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)T);
     const int N = 4 * H;
     int blocks = 0;
     for (int l = 0; l < L; ++l) {
-        if (((uintptr_t)dz[l]) & 15) { set_error("wgrad_group: dz must be 16-byte aligned"); return FOV_ERR_INVALID; }
-        float* bias = db[l];
+        const LayerWgrad& w = layers[l];
+        if (w.T != T) { set_error("wgrad_group: the layers share one time length"); return FOV_ERR_INVALID; }
+        if (((uintptr_t)w.dz) & 15) { set_error("wgrad_group: dz must be 16-byte aligned"); return FOV_ERR_INVALID; }
+        float* bias = w.db;
         for (int which = 0; which < 2; ++which) {       // 0: dR (with the bias row), 1: dK
-            float* c = which == 0 ? dR[l] : dK[l];
+            float* c = which == 0 ? w.dR : w.dK;
             if (!c) continue;
             WgProb& q = g.p[g.count++];
-            q.a = which == 0 ? hs[l] : x[l];
-            q.M = which == 0 ? H : F[l];
+            q.a = which == 0 ? w.hs : w.x;
+            q.M = which == 0 ? H : w.F;
             q.lda = q.M; q.a_so = (long)T * q.M;
             q.shift = which == 0 ? 1 : 0;
-            q.h0 = which == 0 ? h0[l] : nullptr;
+            q.h0 = which == 0 ? w.h0 : nullptr;
             q.ldh0 = H;
-            q.b = dz[l]; q.ldb = N; q.b_so = (long)T * N; q.N = N;
+            q.b = w.dz; q.ldb = N; q.b_so = (long)T * N; q.N = N;
             q.c = c; q.ldc = N;
             q.bias = bias; bias = nullptr;               // the first problem of the layer carries db
             q.grid_n = (N + WT - 1) / WT;
@@ -554,9 +556,8 @@ bool wgrad_rows_takes(long rows, int H) {
     return !env_knobs().no_wgrad_group && rows > 0 && rows <= WR_MAXROWS && H <= 512 && (H & 15) == 0;
 }
 
-// Weight gradients of up to four layers in one launch, every layer with its own time length T[l] (an encoder / decoder pair).
-int wgrad_rows_layers(int L, const float* const* x, const int* F, const int* T, const float* const* hs, const float* const* h0,
-                      const float* const* dz, float* const* dK, float* const* dR, float* const* db, int B, int H, int accumulate, hipStream_t stream) {
+// Weight gradients of up to four layers in one launch, every layer with its own time length w.T (an encoder / decoder pair).
+int wgrad_rows_layers(int L, const LayerWgrad* layers, int B, int H, int accumulate, hipStream_t stream) {
     if (L < 1 || 2 * L > kMaxProb) { set_error("wgrad_rows: at most %d layers", kMaxProb / 2); return FOV_ERR_INVALID; }
     WrBatch g = {};
     g.accumulate = accumulate ? 1 : 0;
@@ -567,27 +568,28 @@ int wgrad_rows_layers(int L, const float* const* x, const int* F, const int* T, 
     // tiles of wgrad_group_kernel 43.5 us (profiles/r05_wgrad_rows_probe.txt)
     const int MT = H >= 512 ? 2 : 1;
     for (int l = 0; l < L; ++l) {
-        if (T[l] <= 0 || B <= 0) { set_error("wgrad_rows: empty layer"); return FOV_ERR_INVALID; }
-        float* bias = db[l];
+        const LayerWgrad& w = layers[l];
+        if (w.T <= 0 || B <= 0) { set_error("wgrad_rows: empty layer"); return FOV_ERR_INVALID; }
+        float* bias = w.db;
         for (int which = 0; which < 2; ++which) {       // 0: dR (with the bias row), 1: dK
-            float* c = which == 0 ? dR[l] : dK[l];
+            float* c = which == 0 ? w.dR : w.dK;
             if (!c) continue;
             WrProb& q = g.p[g.count++];
-            q.a = which == 0 ? hs[l] : x[l];
-            q.M = which == 0 ? H : F[l];
-            q.lda = q.M; q.a_so = T[l] * q.M;
+            q.a = which == 0 ? w.hs : w.x;
+            q.M = which == 0 ? H : w.F;
+            q.lda = q.M; q.a_so = w.T * q.M;
             q.shift = which == 0 ? 1 : 0;
-            q.h0 = which == 0 ? h0[l] : nullptr;
+            q.h0 = which == 0 ? w.h0 : nullptr;
             q.ldh0 = H;
-            q.b = dz[l]; q.ldb = N; q.b_so = T[l] * N; q.N = N;
+            q.b = w.dz; q.ldb = N; q.b_so = w.T * N; q.N = N;
             q.c = c; q.ldc = N;
-            q.RO = B; q.RI = T[l];
-            q.ri_magic = T[l] <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)T[l]);
+            q.RO = B; q.RI = w.T;
+            q.ri_magic = w.T <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)w.T);
             q.bias = bias; bias = nullptr;
             q.grid_n = N / WR_TN;
             q.block0 = blocks;
             blocks += q.grid_n * ((q.M + 16 * MT - 1) / (16 * MT));
-            if (q.M > WR_ZCOLS || (long)B * T[l] > WR_MAXROWS || (long)B * T[l] * N * 4 >= (1L << 31)) { set_error("wgrad_rows: operand too large"); return FOV_ERR_UNSUPPORTED; }
+            if (q.M > WR_ZCOLS || (long)B * w.T > WR_MAXROWS || (long)B * w.T * N * 4 >= (1L << 31)) { set_error("wgrad_rows: operand too large"); return FOV_ERR_UNSUPPORTED; }
             if ((((uintptr_t)q.b) | ((uintptr_t)q.c) | ((uintptr_t)q.bias)) & 15) { set_error("wgrad_rows: dz, dK, dR, db must be 16-byte aligned"); return FOV_ERR_INVALID; }
         }
         if (bias) { set_error("wgrad_rows: db needs dK or dR of the same layer"); return FOV_ERR_INVALID; }

@@ -1,17 +1,19 @@
-"""The bytes every forward workspace-size function answers, pinned for a grid that holds every edge of every dispatch predicate.
+"""The bytes every forward workspace-size function and the two of a layer's backward answer, pinned for a grid that holds every
+edge of every dispatch predicate.
 
 ops.Workspace grows on these numbers, so a change reallocates in user code; and the launch side checks its workspace against
 the same plan that the size functions answer from, so a size that moves means a kernel choice that moved.  The size functions
 are arithmetic only: without a device the library counts 256 CUs and FOV_DBG_RESIDENT_LIMIT lowers that, so the table holds on
-any machine.  fov_lstm_seq_bwd_workspace_bytes belongs to the backward dispatch and is swept as a control.
+any machine.  fov_lstm_seq_bwd_workspace_bytes and fov_lstm_stack2_bwd_workspace_bytes answer from the carve that lstm_seq_bwd
+and lstm_stack2_bwd cut their workspace by (lstm_train.hip).
 
 The expected values are a recording, never a computation of the library under test:
 
     FOV_LIB_PATH=<libfov360_hip.so of the commit to pin> python tests/test_dispatch_host.py --record
 
 writes dispatch_sizes.json beside this file (per function and environment the answers in grid order, run-length coded over the
-list of distinct values).  Equality is exact.  The table here was recorded on an MI355X: the library of that commit honoured
-FOV_DBG_RESIDENT_LIMIT only where it found a device, and answered the same bytes there as this one does anywhere."""
+list of distinct values).  Equality is exact.  The table here was recorded from the library of the commit before the backward
+plan; the answers of the functions it already held came out as they were recorded on an MI355X before the forward plan."""
 import contextlib
 import itertools
 import json
@@ -46,6 +48,7 @@ GRIDS = {
     "fov_seq2seq_tf_workspace_bytes": [(B, T_in, T_out, F, Fd, H, impl)
                                        for impl, H, B, (T_in, T_out), Fd, F in itertools.product(IMPLS, HS, BS, T_PAIRS, FDECS, FS)],
     "fov_lstm_seq_bwd_workspace_bytes": [(B, T, F, H) for H, B, T, F in itertools.product(HS, BS, TS, FS)],
+    "fov_lstm_stack2_bwd_workspace_bytes": [(B, T, F, H) for H, B, T, F in itertools.product(HS, BS, TS, FS)],
 }
 
 
