@@ -405,6 +405,29 @@ int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0,
                            int act, int impl,
                            void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
+/* The recurrent kernel R (H,4H) in the order the fused call's waves hold it, for callers whose weights stay the same from
+ * call to call (predict): made once per weight set, it lets the fused launch load a wave's slice as 16-byte loads.
+ *   out: H * 4H floats, 16-byte aligned.  Element ((((c * NQ + jj) * 4 + s) * 64 + lane) * 4 + g), NQ = H / 16,
+ *   lane = 16 * g4 + n, is R[16 * jj + 4 * g4 + s][g * H + 16 * c + n]  (c: 16-unit column block, jj: 16-row k-block,
+ *   s: k-step of the block, g: gate).  A permutation of R: the values are copied, nothing is rounded.
+ * R needs no alignment beyond a float's.  H in {64, 128, 256} (others: FOV_ERR_UNSUPPORTED).  One small launch on `stream`. */
+int fov_lstm_pack_r(const float* R, int H, float* out, fov_stream_t stream);
+
+/* fov_seq2seq_decode_fwd with the packs of enc_R and dec_R (fov_lstm_pack_r; either may be NULL).  The results are the same
+ * bit for bit: the packs only change how the one-launch form of the call (H in {64, 128, 256}, one 16-sequence tile per
+ * group of workgroups) loads its recurrent weights, and that form uses them when BOTH are given.  Every other form of the
+ * call reads enc_R / dec_R, which must be valid either way.  The caller keeps a pack in step with its R: after R changes
+ * the pack is made again (or NULL is passed). */
+int fov_seq2seq_decode_fwd_packed(const float* enc_in, const float* dec_in0,
+                                  const float* enc_K, const float* enc_R, const float* enc_b,
+                                  const float* dec_K, const float* dec_R, const float* dec_b,
+                                  const float* dense_W, const float* dense_b,
+                                  float* out, float* hT, float* cT,
+                                  const float* enc_Rpack, const float* dec_Rpack,
+                                  int B, int T_in, int T_out, int F_enc, int F_dec, int H,
+                                  int act, int impl,
+                                  void* workspace, size_t workspace_bytes, fov_stream_t stream);
+
 /* The decoder half alone: T_out autoregressive steps from a GIVEN state (h0, c0) (B,H) (NULL = zeros) - what the
  * reference's sampling loop does after encoder_model.predict (FoV_seq2seq.py:156-178: decoder_model.predict fed its own
  * output), any batch, one launch.  out (B,T_out,F_dec); hT, cT (B,H) optional final state.  Workspace as for

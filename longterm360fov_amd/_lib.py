@@ -52,6 +52,8 @@ SIGNATURES = {
     "fov_lstm_seq_fwd_zx": (_I, [_P] * 9 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_seq2seq_decode_workspace_bytes": (_SZ, [_I] * 7),
     "fov_seq2seq_decode_fwd": (_I, [_P] * 13 + [_I] * 8 + [_P, _SZ, _P]),
+    "fov_lstm_pack_r": (_I, [_P, _I, _P, _P]),
+    "fov_seq2seq_decode_fwd_packed": (_I, [_P] * 15 + [_I] * 8 + [_P, _SZ, _P]),
     "fov_seq2seq_decoder_fwd": (_I, [_P] * 11 + [_I] * 6 + [_P, _SZ, _P]),
     "fov_stacked_seq2seq_decode_supported": (_I, [_I] * 7),
     "fov_stacked_seq2seq_decode_fwd": (_I, [_P] * 25 + [_I] * 8 + [_P]),

@@ -471,15 +471,21 @@ size_t fov_seq2seq_decode_workspace_bytes(int B, int T_in, int T_out, int F_enc,
     return plan_decode(B, T_out, F_enc, F_dec, H, impl).need;
 }
 
-int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0, const float* enc_K, const float* enc_R,
-                           const float* enc_b, const float* dec_K, const float* dec_R, const float* dec_b,
-                           const float* dense_W, const float* dense_b, float* out, float* hT, float* cT, int B,
-                           int T_in, int T_out, int F_enc, int F_dec, int H, int act, int impl, void* workspace,
-                           size_t workspace_bytes, fov_stream_t stream) {
+// enc_Rpack / dec_Rpack: fov_lstm_pack_r of enc_R / dec_R or NULL (fov_seq2seq_decode_fwd: both NULL)
+static int seq2seq_decode_fwd_impl(const float* enc_in, const float* dec_in0, const float* enc_K, const float* enc_R,
+                                   const float* enc_b, const float* dec_K, const float* dec_R, const float* dec_b,
+                                   const float* dense_W, const float* dense_b, float* out, float* hT, float* cT,
+                                   const float* enc_Rpack, const float* dec_Rpack, int B, int T_in, int T_out, int F_enc,
+                                   int F_dec, int H, int act, int impl, void* workspace, size_t workspace_bytes,
+                                   fov_stream_t stream) {
     if (B < 0 || T_in < 0 || T_out < 0 || F_enc <= 0 || F_dec <= 0 || H <= 0 || !enc_K || !enc_R || !enc_b ||
         !dec_K || !dec_R || !dec_b || !dense_W || !dense_b ||
         (B > 0 && ((T_in > 0 && !enc_in) || !dec_in0 || (T_out > 0 && !out))) || !valid_act(act)) {
         set_error("fov_seq2seq_decode_fwd: invalid argument");
+        return FOV_ERR_INVALID;
+    }
+    if ((((uintptr_t)enc_Rpack | (uintptr_t)dec_Rpack) & 15) != 0) {
+        set_error("fov_seq2seq_decode_fwd_packed: a pack must be 16-byte aligned");
         return FOV_ERR_INVALID;
     }
     if (F_dec > 64) { set_error("fov_seq2seq_decode_fwd: F_dec > 64 unsupported"); return FOV_ERR_UNSUPPORTED; }
@@ -488,6 +494,8 @@ int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0, const floa
     LstmParams p = {};
     p.x = enc_in; p.K = enc_K; p.R = enc_R; p.b = enc_b; p.T = T_in; p.F = F_enc;
     bind_decoder(p, dec_in0, dec_K, dec_R, dec_b, dense_W, dense_b, out, hT, cT, B, T_out, F_dec, H, act, workspace);
+    // the packs are read by the fused cluster launch alone (launch_cluster's gate); every other kernel reads R as it is
+    if (lstm_pack_shape_ok(H)) { p.Rpack = enc_Rpack; p.dRpack = dec_Rpack; }
     hipStream_t s = (hipStream_t)stream;
     switch (plan.kernel) {
         case DecodeKernel::Wide16: return launch_wide16_s2s(p, s);
@@ -495,6 +503,26 @@ int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0, const floa
         case DecodeKernel::Generic: break;
     }
     return launch_generic(p, true, s);
+}
+
+int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0, const float* enc_K, const float* enc_R,
+                           const float* enc_b, const float* dec_K, const float* dec_R, const float* dec_b,
+                           const float* dense_W, const float* dense_b, float* out, float* hT, float* cT, int B,
+                           int T_in, int T_out, int F_enc, int F_dec, int H, int act, int impl, void* workspace,
+                           size_t workspace_bytes, fov_stream_t stream) {
+    return seq2seq_decode_fwd_impl(enc_in, dec_in0, enc_K, enc_R, enc_b, dec_K, dec_R, dec_b, dense_W, dense_b, out, hT, cT,
+                                   nullptr, nullptr, B, T_in, T_out, F_enc, F_dec, H, act, impl, workspace, workspace_bytes, stream);
+}
+
+int fov_seq2seq_decode_fwd_packed(const float* enc_in, const float* dec_in0, const float* enc_K, const float* enc_R,
+                                  const float* enc_b, const float* dec_K, const float* dec_R, const float* dec_b,
+                                  const float* dense_W, const float* dense_b, float* out, float* hT, float* cT,
+                                  const float* enc_Rpack, const float* dec_Rpack, int B, int T_in, int T_out, int F_enc,
+                                  int F_dec, int H, int act, int impl, void* workspace, size_t workspace_bytes,
+                                  fov_stream_t stream) {
+    return seq2seq_decode_fwd_impl(enc_in, dec_in0, enc_K, enc_R, enc_b, dec_K, dec_R, dec_b, dense_W, dense_b, out, hT, cT,
+                                   enc_Rpack, dec_Rpack, B, T_in, T_out, F_enc, F_dec, H, act, impl, workspace, workspace_bytes,
+                                   stream);
 }
 
 int fov_seq2seq_decoder_fwd(const float* dec_in0, const float* h0, const float* c0, const float* dec_K,

@@ -87,7 +87,14 @@ struct LstmParams {
     int xcd_pad;               // lstm_wide16.hip: grid padded to 8 x (workgroups per tile), block b = member b / 8 of group b % 8
     int trio;                  // lstm_wide16.hip, stacked launch on the XCD-per-group grid: 3 three roles, 2 two roles (0: not stacked) -
                                // layer 1 also publishes h_t (sc1) into a mirror ring for its readers on other XCDs
+    // lstm_cluster.hip, fused encode + decode launch only: R / dR in fragment order (lstm_pack.hip), or NULL.  Both given: each
+    // phase loads its R slice as 16-byte loads from the pack; otherwise (and in every other kernel) R / dR are read as they are
+    const float* Rpack;
+    const float* dRpack;
 };
+// lstm_pack.hip: out (H * 4H floats, 16-byte aligned) = R (H,4H) in the order the cluster kernel's MFMA B fragments take it
+bool lstm_pack_shape_ok(int H);
+int launch_lstm_pack_r(const float* R, int H, float* out, hipStream_t stream);
 
 int launch_generic(const LstmParams& p, bool decode, hipStream_t stream);
 long generic_launch_count();   // launches of the generic (VALU) LSTM kernel so far in this process (diagnostic)

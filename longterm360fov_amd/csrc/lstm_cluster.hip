@@ -254,6 +254,28 @@ __device__ __forceinline__ void load_r_block(float (&wR)[H / 16][4][4], int j, c
         for (int g = 0; g < 4; ++g)
             wR[j][s][g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, voff, kb + (unsigned)((s * H4 + g * H) * 4), 0));
 }
+// The same k-blocks from the fragment-ordered pack of R (lstm_pack.hip, made once per weight set): ONE 16-byte load per (j, s)
+// straight into wR[j][s][0..3], 1 KB contiguous per wave instruction - 64 loads per lane for the slice instead of 256, so the
+// 63 loads the counter allows in flight carry four times the bytes.  The wave's column block goes into the lane offset (the
+// wave index is no scalar to hipcc), the (k-block, k-step) part into the scalar offset / the instruction's immediate.
+template <int H>
+__device__ __forceinline__ void load_r_block_packed(float (&wR)[H / 16][4][4], int j, const float* Rpack, int col0, int slice, int lane) {
+    constexpr int G = H / 64, NQ = H / 16;
+    const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Rpack), 0, H * 4 * H * 4, 0x00020000);
+    const unsigned voff = (unsigned)((col0 >> 4) * NQ * 4096 + lane * 16);
+    const unsigned kb = (unsigned)((((slice + (j >> 2)) & (G - 1)) * 4 + (j & 3)) * 4096);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(rrs, voff, kb + (unsigned)(s * 1024), 0);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) wR[j][s][g] = __uint_as_float(v[g]);
+    }
+}
+template <int H, int J0, int J1>
+__device__ __forceinline__ void load_r_packed(float (&wR)[H / 16][4][4], const float* Rpack, int col0, int slice, int lane) {
+#pragma unroll
+    for (int j = J0; j < J1; ++j) load_r_block_packed<H>(wR, j, Rpack, col0, slice, lane);
+}
 // DECODE: bias and the two K blocks of this lane (input row k = 4*s + g4, see load_weights) straight into registers
 template <int H>
 __device__ __forceinline__ void load_dec_small(float (&bias)[4], f32x4 (&kb)[2], const float* K, const float* b, int F, int col0, int lane) {
@@ -406,8 +428,12 @@ struct ClusterCarry {
 // FUSED: 0 = the whole launch is this phase; 1 = encoder phase of the fused kernel (its last step is exchanged too, the
 // state leaves through `cy` instead of memory, nothing is settled); 2 = decoder phase (no header read, no handshake, no
 // state loads: everything comes from `cy` and the h tile the encoder phase left in LDS).  One tile per group only.
-template <int H, int ACT, int MODE, int FUSED>
+// PK (fused kernel only): the phase's R slice comes from the fragment-ordered pack (p.Rpack / p.dRpack, load_r_packed).  A
+// template parameter, not a branch: the registers of a load inside a branch are copied or waited for where the branch ends
+// (see load_weights), and the kernel without a pack stays the code it was.  The step is the same code either way.
+template <int H, int ACT, int MODE, int FUSED, bool PK = false>
 __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& cy) {
+    static_assert(!PK || FUSED != 0, "the pack is read by the fused kernel only");
     constexpr int G = H / 64;
     constexpr int NQ = H / 16;
     constexpr int NG = (G - 1) * 2;  // 16-byte loads (two adjacent units' tagged granules) per thread per step
@@ -454,6 +480,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     const float* Kp = LAYER ? p.K : p.dK;
     const float* Rp = LAYER ? p.R : p.dR;
     const float* bp = LAYER ? p.b : p.db;
+    const float* Rpk = LAYER ? p.Rpack : p.dRpack;   // (PK only)
     const int F = LAYER ? (ZX ? 0 : p.F) : p.F_dec;
     const int steps = LAYER ? p.T : p.T_out;
     const int Fp = round16(F);
@@ -493,10 +520,15 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     // Decoder phase of the fused kernel: the R slice is STREAMED - three k-blocks here, the others three blocks ahead of the
     // MFMAs of z_0 that consume them (256 loads per wave take 4 us, z_0's 264 MFMAs another 4: now side by side); bias, K
     // and the Dense kernel go out first and stay in registers (no LDS round trip, no barrier).
-    constexpr int STREAM_LA = 3;
+    // PK: a k-block is four loads - as many blocks ahead as the 63 loads the counter allows in flight leave room for beside
+    // the phase's small loads (bias 4, K 8, Dense kernel 4, Dense bias 4, y_{-1} 4): nine, i.e. the whole slice up to H = 128
+    constexpr int F2_SMALL_LOADS = 4 + 8 + 4 + 4 + 4;
+    constexpr int STREAM_LA = !PK ? 3 : ((63 - F2_SMALL_LOADS) / 4 < NQ ? (63 - F2_SMALL_LOADS) / 4 : NQ);
     f32x4 kb[2];   // DECODE: the two K-slice blocks of this lane (loop invariant)
     if constexpr (F2) {
         load_dec_small<H>(bias, kb, Kp, bp, F, col0, lane);
+    } else if constexpr (PK) {
+        load_r_packed<H, 0, JA>(wR, Rpk, col0, slice, lane);
     } else {
         load_weights<H, !LAYER, 0, JA, false>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);
     }
@@ -511,7 +543,12 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         xch_count_arrival(p.status);   // both header words have landed (stored above)
     }
     FOV_PSTAMP(3);
-    if constexpr (!F2) load_weights<H, !LAYER, JA, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);
+    if constexpr (PK && !F2) {
+        load_r_packed<H, JA, NQ>(wR, Rpk, col0, slice, lane);
+        load_weights<H, !LAYER, NQ, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);   // (no R block: bias and K)
+    } else if constexpr (!F2) {
+        load_weights<H, !LAYER, JA, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);
+    }
     FOV_PSTAMP(2);
     const bool poisoned = hdr && xch_poisoned(p.status);   // one wave-wide load per wave; wave 0's value decides (sFlag[0])
     if (tid == 0) { sFlag[0] = (poisoned || (F2 && cy.aborted)) ? 1 : 0; sFlag[1] = 0; }
@@ -580,9 +617,24 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         for (int ss = 0; ss < 4; ++ss)
             bd4[ss] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(bdrs, (4 * ss + g4 < O) ? (unsigned)((4 * ss + g4) * 4) : OORB, 0, 0));
     }
+    // PK decoder phase: y_{-1} is requested here, in front of the R stream - the loads return in order, and y_{-1} . K opens
+    // z_0: behind the stream it would wait for all of STREAM_LA blocks (one tile per group: the tile is the group's)
+    float y0pre[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (F2 && PK) {
+        const int b00 = group * BT;
+        const int live0 = p.B - b00 < BT ? p.B - b00 : BT;
+        const __amdgpu_buffer_rsrc_t y0rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.dec_in0 + (size_t)b00 * F), 0, live0 > 0 ? live0 * F * 4 : 0, 0x00020000);
+#pragma unroll
+        for (int ss = 0; ss < 4; ++ss)
+            y0pre[ss] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(y0rs, (4 * ss + g4 < F) ? (unsigned)((n * F + 4 * ss + g4) * 4) : OORB, 0, 0));
+    }
     if constexpr (F2) {
 #pragma unroll
-        for (int j = 0; j < STREAM_LA; ++j) load_r_block<H>(wR, j, Rp, col0, slice, lane);
+        for (int j = 0; j < STREAM_LA; ++j) {
+            if constexpr (PK) load_r_block_packed<H>(wR, j, Rpk, col0, slice, lane);
+            else load_r_block<H>(wR, j, Rp, col0, slice, lane);
+        }
     } else if (!LAYER) {
         __syncthreads();   // K slice written by load_weights above
         kb[0] = *(const f32x4*)(sKw + lane * 4);
@@ -728,7 +780,10 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         for (int ss = 0; ss < 2; ++ss)
             yoff[ss] = (!LAYER && 4 * ss + g4 < p.F_dec && (!F2 || (slice == 0 && wave == 0))) ? (unsigned)((n * p.T_out * p.F_dec + 4 * ss + g4) * 4) : OORB;   // (F2: only the storing wave keeps real offsets, see the steady-state step)
         f32x4 y4 = (f32x4){0.f, 0.f, 0.f, 0.f};   // DECODE: y_{t-1}[n][4*s + g4], the A fragment of y . K
-        if (!LAYER) {
+        if constexpr (F2 && PK) {
+#pragma unroll
+            for (int ss = 0; ss < 4; ++ss) y4[ss] = y0pre[ss];   // (requested in front of the R stream)
+        } else if (!LAYER) {
             // (buffer loads with an out-of-range offset for the masked elements: a `cond ? load : 0` sits in a branch whose
             // merge waits for every older load - here the streamed R slice)
             const __amdgpu_buffer_rsrc_t y0rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -757,19 +812,25 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                 for (int r = 0; r < 4; ++r)
                     acc[g][r] = bias[g] + __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(zxrs, zxoff + (unsigned)((r * p.T * 4 * H + g * H) * 4), 0, 0));
         }
-        if (steps > 0) {
+        // (PK decoder phase: unconditional - the fused launch always has steps, launch_cluster's gate.  With the test hipcc sees a
+        // way into the step loop that passes no MFMA of z_0, on which the stream's first blocks are still in flight, and waits
+        // for them, vmcnt(19) down to vmcnt(0) - i.e. for the previous step's publish stores as well - at the top of EVERY step)
+        if ((F2 && PK) || steps > 0) {
             if constexpr (ZX) input_proj_any<true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane);   // (nq = 0: nothing)
             else if constexpr (LAYER) input_proj_any<true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane, bias4);
             else input_proj_reg<true, true>(acc, y4, kb, bias4);
             // a zero initial state (the encoder of every seq2seq call): h_0 . R is exactly 0 - its 4H/16 k-blocks (256 of the
             // 352 MFMAs of an encoder step at H = 256) are skipped here and at the top of step 0
             if constexpr (F2) {
-                // the whole of h_T . R here (the loop's first partner-slice run is skipped), block j + 3 requested before the
-                // MFMAs of block j
+                // the whole of h_T . R here (the loop's first partner-slice run is skipped), block j + STREAM_LA requested before
+                // the MFMAs of block j
                 f32x4 a = *(const f32x4*)hrow;
 #pragma unroll
                 for (int j = 0; j < NQ; ++j) {
-                    if (j + STREAM_LA < NQ) load_r_block<H>(wR, j + STREAM_LA, Rp, col0, slice, lane);
+                    if (j + STREAM_LA < NQ) {
+                        if constexpr (PK) load_r_block_packed<H>(wR, j + STREAM_LA, Rpk, col0, slice, lane);
+                        else load_r_block<H>(wR, j + STREAM_LA, Rp, col0, slice, lane);
+                    }
                     f32x4 an = a;
                     if (j + 1 < NQ) an = *(const f32x4*)(hrow + 16 * (j + 1));
 #pragma unroll
@@ -1174,7 +1235,7 @@ __global__ __launch_bounds__(256, 1) void lstm_cluster_kernel(LstmParams p) {
 
 // Encoder + autoregressive decoder of the fused call in ONE launch (one 16-sequence tile per group): no second dispatch,
 // no second header read / handshake, the state stays in registers and the h_T tile in LDS; only the weights are swapped.
-template <int H, int ACT>
+template <int H, int ACT, bool PK>
 __global__ __launch_bounds__(256, 1) void lstm_cluster_fused_kernel(LstmParams p) {
     if constexpr (H >= 128) {
         // a group count that is no multiple of eight (the reference's batch of 32 = two groups; any batch that is no multiple of
@@ -1186,8 +1247,8 @@ __global__ __launch_bounds__(256, 1) void lstm_cluster_fused_kernel(LstmParams p
         }
     }
     ClusterCarry cy;
-    cluster_body<H, ACT, MODE_LAYER, 1>(p, cy);
-    cluster_body<H, ACT, MODE_DECODE, 2>(p, cy);
+    cluster_body<H, ACT, MODE_LAYER, 1, PK>(p, cy);
+    cluster_body<H, ACT, MODE_DECODE, 2, PK>(p, cy);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1287,8 +1348,11 @@ static int launch_cluster_h(const LstmParams& p, int mode, hipStream_t stream) {
 
 template <int H>
 static int launch_cluster_fused_h(const LstmParams& p, hipStream_t stream) {
-    void (*kern)(LstmParams) = p.act == FOV_ACT_HARD_SIGMOID ? lstm_cluster_fused_kernel<H, FOV_ACT_HARD_SIGMOID>
-                                                             : lstm_cluster_fused_kernel<H, FOV_ACT_SIGMOID>;
+    // both R packs given (fov_seq2seq_decode_fwd_packed): the kernel whose phases load them; one alone is not used
+    const bool pk = p.Rpack && p.dRpack;
+    void (*kern)(LstmParams) = p.act == FOV_ACT_HARD_SIGMOID
+                                   ? (pk ? lstm_cluster_fused_kernel<H, FOV_ACT_HARD_SIGMOID, true> : lstm_cluster_fused_kernel<H, FOV_ACT_HARD_SIGMOID, false>)
+                                   : (pk ? lstm_cluster_fused_kernel<H, FOV_ACT_SIGMOID, true> : lstm_cluster_fused_kernel<H, FOV_ACT_SIGMOID, false>);
     const ClusterLds L1 = cluster_lds(H, p.F, false), L2 = cluster_lds(H, p.F_dec, true);
     const size_t lds = (size_t)(L1.total_floats > L2.total_floats ? L1.total_floats : L2.total_floats) * sizeof(float);
     if (lds > 160 * 1024) { set_error("fused cluster kernel: needs %zu B of LDS (> 160 KiB)", lds); return FOV_ERR_UNSUPPORTED; }

@@ -63,6 +63,22 @@ _ENV_KEYS_B = tuple(os.fsencode(k) for k in _ENV_KNOBS)
 if not isinstance(_ENV_DATA, dict) or (_ENV_DATA and not isinstance(next(iter(_ENV_DATA)), bytes)):
     _ENV_DATA = None
 _FORCE_SAFE_KEY_B = os.fsencode("FOV_FORCE_SAFE_EXCHANGE")
+_NO_PACK_KEY_B = os.fsencode("FOV_NO_WEIGHT_PACK")
+# A recurrent kernel is packed (fov_lstm_pack_r) once this many earlier calls on the workspace have seen it unchanged: a pack
+# costs one small launch per kernel (4.8 us each at H = 256, plus its dispatch) and saves about 3 us per call (DESIGN.md
+# section 4.1), so it is paid back after some seven calls: weights used once or twice - an evaluation between two training
+# steps - never pay for one, a predict loop packs on its third call.
+_PACK_AFTER = 2
+_increment_version = getattr(getattr(torch.autograd, "graph", None), "increment_version", None)
+
+
+def _mark_written(t):
+    """A kernel wrote `t` through its raw pointer: advance torch's version counter (shared by every view of the buffer), which
+    is how Workspace.r_pack sees that a weight has changed."""
+    if _increment_version is not None:
+        _increment_version(t)
+    else:
+        t.add_(0)
 
 
 def _env_snapshot():
@@ -109,6 +125,31 @@ class Workspace:
     def __init__(self, device=None):
         self.device = device
         self.buf = None
+        self._rpacks = {}     # role -> [key, R (kept alive: its address cannot be handed to another tensor), calls seen, pack]
+
+    def r_pack(self, role, R):
+        """The fragment-ordered pack (fov_lstm_pack_r) of the recurrent kernel R that plays `role` ('enc_R', 'dec_R') in the
+        calls on this workspace, or None while R has not been seen unchanged on _PACK_AFTER earlier calls, for a width the
+        pack does not have, and under FOV_NO_WEIGHT_PACK=1.  The key is (data_ptr, _version, shape): an in-place update
+        through torch, or through this package's optimizer steps, makes a new pack; so does another tensor.  Made on the
+        current stream, like the call that uses it."""
+        no_pack = _ENV_DATA.get(_NO_PACK_KEY_B) == b"1" if _ENV_DATA is not None else os.environ.get("FOV_NO_WEIGHT_PACK", "") == "1"
+        H = R.shape[0]
+        if no_pack or H not in (64, 128, 256) or R.is_inference():
+            return None
+        key = (R.data_ptr(), R._version, R.shape, R.device)
+        e = self._rpacks.get(role)
+        if e is None or e[0] != key:
+            self._rpacks[role] = [key, R, 1, None]
+            return None
+        if e[3] is None:
+            e[2] += 1
+            if e[2] <= _PACK_AFTER:
+                return None
+            pack = torch.empty(H * 4 * H, dtype=torch.float32, device=R.device)
+            check(_lib.lib().fov_lstm_pack_r(R.data_ptr(), H, pack.data_ptr(), _stream()))
+            e[3] = pack
+        return e[3]
 
     def get(self, nbytes, device):
         nbytes = max(int(nbytes), 256)
@@ -221,10 +262,22 @@ def seq2seq_decode(enc_in, dec_in0, w, T_out, act="sigmoid", impl="auto", worksp
         return out
     impl = impl_code(impl)
     buf = ws.get(L.fov_seq2seq_decode_workspace_bytes(B, T_in, T_out, F_enc, F_dec, H, impl), enc_in.device)
-    check(L.fov_seq2seq_decode_fwd(_ptr(enc_in), _ptr(dec_in0), *[_ptr(t) for t in ws_t], _ptr(out),
-                                   None if hT is None else _ptr(_dev(hT, "hT")), None if cT is None else _ptr(_dev(cT, "cT")),
-                                   B, T_in, T_out, F_enc, F_dec, H, act_code(act), impl,
-                                   buf.data_ptr(), buf.numel(), _stream()))
+    # The R packs live with the workspace the caller handed in (a predict loop keeps one); the shared default workspace keeps
+    # none.  The library uses them in the one-launch form of the call only, the results are the same bits either way.
+    packs = (None, None)
+    if workspace is not None and impl != IMPL_GENERIC and B > 0:
+        packs = (workspace.r_pack("enc_R", ws_t[1]), workspace.r_pack("dec_R", ws_t[4]))
+    if packs[0] is None or packs[1] is None:
+        check(L.fov_seq2seq_decode_fwd(_ptr(enc_in), _ptr(dec_in0), *[_ptr(t) for t in ws_t], _ptr(out),
+                                       None if hT is None else _ptr(_dev(hT, "hT")), None if cT is None else _ptr(_dev(cT, "cT")),
+                                       B, T_in, T_out, F_enc, F_dec, H, act_code(act), impl,
+                                       buf.data_ptr(), buf.numel(), _stream()))
+    else:
+        check(L.fov_seq2seq_decode_fwd_packed(_ptr(enc_in), _ptr(dec_in0), *[_ptr(t) for t in ws_t], _ptr(out),
+                                              None if hT is None else _ptr(_dev(hT, "hT")), None if cT is None else _ptr(_dev(cT, "cT")),
+                                              packs[0].data_ptr(), packs[1].data_ptr(),
+                                              B, T_in, T_out, F_enc, F_dec, H, act_code(act), impl,
+                                              buf.data_ptr(), buf.numel(), _stream()))
     return out
 
 
@@ -993,6 +1046,7 @@ def rmsprop_tf_step(params, grads, ms, lr, decay=0.9, eps=1e-10, clip_value=0.0,
     else:
         check(_lib.lib().fov_rmsprop_tf_step_guarded(_ptr(params), _ptr(grads), _ptr(ms), params.numel(), lr, decay, eps, clip_value,
                                                      *_guard_ptrs(guards), _applied_ptr(applied), _stream()))
+    _mark_written(params)
 
 
 def dense_bwd(x, W, dpre, dW=None, db=None, need_dx=True, accumulate=False, scratch=None, need_dW=True, need_db=True,
@@ -1114,6 +1168,7 @@ def adam_step(params, grads, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e
         _dev(t, "flat buffer")
     check(_lib.lib().fov_adam_step_guarded(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), lr, beta1, beta2,
                                            eps, int(step), *_guard_ptrs(guards), _applied_ptr(applied), _stream()))
+    _mark_written(params)
 
 
 def reduce_defer_begin(grad, arena):
@@ -1137,6 +1192,7 @@ def rmsprop_step(params, grads, accum, lr=1e-3, rho=0.9, eps=1e-7, guards=None, 
         _dev(t, "flat buffer")
     check(_lib.lib().fov_rmsprop_step_guarded(_ptr(params), _ptr(grads), _ptr(accum), params.numel(), lr, rho, eps,
                                               *_guard_ptrs(guards), _applied_ptr(applied), _stream()))
+    _mark_written(params)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@ graph, and inside each, again, those left when the edges back to its entry block
 a loop out in one piece, so label order says nothing); the instructions of an inner MFMA-carrying loop are counted with
 that loop only.  Classes go by mnemonic prefix alone.
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --offload-device-only -o k.s lstm_cluster.hip
-       python tools/isa_step_counts.py k.s [kernel-name substring, default the H = 256 sigmoid fused kernel] [--hist]
+       python tools/isa_step_counts.py k.s [kernel-name substring, default the H = 256 sigmoid fused kernel that loads R from packs; ...ELb0: the one that does not] [--hist]
 --hist adds each loop's non-MFMA mnemonics with their counts."""
 import re
 import sys
@@ -118,7 +118,7 @@ def sccs(nodes, succ):
 def main():
     argv = [a for a in sys.argv[1:] if a != "--hist"]
     hist = "--hist" in sys.argv
-    sub = argv[1] if len(argv) > 1 else "lstm_cluster_fused_kernelILi256ELi0"
+    sub = argv[1] if len(argv) > 1 else "lstm_cluster_fused_kernelILi256ELi0ELb1"
     body = kernel_body(open(argv[0]).read().split("\n"), sub)
     if not body:
         sys.exit("no kernel matches %r" % sub)
