@@ -271,10 +271,66 @@ __device__ __forceinline__ void load_r_block_packed(float (&wR)[H / 16][4][4], i
         for (int g = 0; g < 4; ++g) wR[j][s][g] = __uint_as_float(v[g]);
     }
 }
+// one of them: k-step s of k-block j
+template <int H>
+__device__ __forceinline__ void load_r_frag_packed(float (&wR)[H / 16][4][4], int j, int s, const float* Rpack, int col0, int slice, int lane) {
+    constexpr int G = H / 64, NQ = H / 16;
+    const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Rpack), 0, H * 4 * H * 4, 0x00020000);
+    const unsigned voff = (unsigned)((col0 >> 4) * NQ * 4096 + lane * 16);
+    const unsigned kb = (unsigned)((((slice + (j >> 2)) & (G - 1)) * 4 + (j & 3)) * 4096);
+    const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(rrs, voff, kb + (unsigned)(s * 1024), 0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) wR[j][s][g] = __uint_as_float(v[g]);
+}
 template <int H, int J0, int J1>
 __device__ __forceinline__ void load_r_packed(float (&wR)[H / 16][4][4], const float* Rpack, int col0, int slice, int lane) {
 #pragma unroll
     for (int j = J0; j < J1; ++j) load_r_block_packed<H>(wR, j, Rpack, col0, slice, lane);
+}
+// K-first prologue (the packed fused kernel's encoder phase): bias and the wave's K slice are REQUESTED here - the same 100
+// loads as in load_weights - and the slice is stored to LDS by store_k_slice, so that the caller can put the other loads
+// step 0 needs (x_0, x_1, the poison word) behind these requests and in front of the wait the stores carry.
+template <int H>
+__device__ __forceinline__ void load_k_slice(float (&bias)[4], f32x4 (&kv)[CL_MAX_F / 16][4], const float* K, const float* b, int F,
+                                             int col0, int lane) {
+    const int n = lane & 15, g4 = lane >> 4;
+    const int H4 = 4 * H;
+    const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b), 0, b ? H4 * 4 : 0, 0x00020000);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bias[g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brs, (unsigned)((g * H + col0 + n) * 4), 0, 0));
+    const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(K), 0, F * H4 * 4, 0x00020000);
+#pragma unroll
+    for (int q = 0; q < CL_MAX_F / 16; ++q)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const unsigned voff = (unsigned)(((16 * q + 4 * g4 + s) * H4 + col0 + n) * 4);   // k >= F: past the descriptor
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                kv[q][s][g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(krs, voff + (unsigned)(g * H * 4), 0, 0));
+        }
+}
+// ... and x_0, x_1 of the group's (only) tile of the fused call: thread (tid / 16, tid % 16) requests columns tid % 16 + 16 i of
+// row tid / 16, as the prologue of cluster_body does for every other kernel
+__device__ __forceinline__ void load_x01(float (&xpre)[2][XR], const LstmParams& p, int group, int F, int tid) {
+    const int xrw0 = tid >> 4, xcl0 = tid & 15;
+    const int b00 = group * BT;
+    const int live0 = (group < p.num_tiles) ? (p.B - b00 < BT ? p.B - b00 : BT) : 0;
+    const __amdgpu_buffer_rsrc_t xg0 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(live0 > 0 ? p.x + (size_t)b00 * p.T * F : nullptr), 0, live0 * p.T * F * 4, 0x00020000);
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int i = 0; i < XR; ++i)
+            xpre[tt][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                xg0, (tt < p.T && xcl0 + 16 * i < F) ? (unsigned)((xrw0 * p.T * F + xcl0 + 16 * i) * 4) : 0x80000000u, (unsigned)(tt * F * 4), 0));
+}
+__device__ __forceinline__ void store_k_slice(const f32x4 (&kv)[CL_MAX_F / 16][4], float* sKw, int nq, int lane) {
+#pragma unroll
+    for (int q = 0; q < CL_MAX_F / 16; ++q)
+        if (q < nq) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) *(f32x4*)(sKw + ((q * 4 + s) * 64 + lane) * 4) = kv[q][s];
+        }
 }
 // DECODE: bias and the two K blocks of this lane (input row k = 4*s + g4, see load_weights) straight into registers
 template <int H>
@@ -350,8 +406,11 @@ __device__ __forceinline__ void input_proj(f32x4 (&acc)[4], const float* arow, c
 // registers are renamed instead of rotated - the run-time loop above carries two v_mov_b64 and two v_add_u32 per 16
 // MFMAs, and on this chip a VALU instruction is never hidden behind an fp32 MFMA (tools/microbench/mfma_f32_overlap.hip:
 // 32 -> 46 cycles for ONE v_fma_f32 in an MFMA gap).
-template <int NQC, bool FIRST, bool LAST, bool CINIT = false>
-__device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* arow, const float* sKw, int lane, const f32x4* c0 = nullptr) {
+// `pre(q, s)` runs in front of the four MFMAs of k-step s of k-block q: the K-first encoder phase requests its R pack there, a
+// load or two per k-step.
+struct NoPre { __device__ __forceinline__ void operator()(int, int) const {} };
+template <int NQC, bool FIRST, bool LAST, bool CINIT = false, class Pre = NoPre>
+__device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* arow, const float* sKw, int lane, const f32x4* c0 = nullptr, Pre pre = Pre{}) {
     const float* bl = sKw + lane * 4;
     f32x4 a = *(const f32x4*)arow;
     f32x4 b0 = *(const f32x4*)bl;
@@ -364,6 +423,7 @@ __device__ __forceinline__ void input_proj_fixed(f32x4 (&acc)[4], const float* a
         for (int s = 0; s < 4; ++s) {
             f32x4 bn = b1;
             if (4 * q + s + 2 < 4 * NQC) bn = *(const f32x4*)(bl + (4 * q + s + 2) * 256);
+            pre(q, s);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 if (CINIT && q == 0 && s == 0) mfma_f32_c<false>(acc[g], a[s], b0[g], c0[g], false);
@@ -525,7 +585,23 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     constexpr int F2_SMALL_LOADS = 4 + 8 + 4 + 4 + 4;
     constexpr int STREAM_LA = !PK ? 3 : ((63 - F2_SMALL_LOADS) / 4 < NQ ? (63 - F2_SMALL_LOADS) / 4 : NQ);
     f32x4 kb[2];   // DECODE: the two K-slice blocks of this lane (loop invariant)
-    if constexpr (F2) {
+    // K first (KF, the packed kernel's encoder phase).  The fused encoder starts from zero state: step 0 reads no R before its
+    // own-slice run, which stands behind x_0 . K, the cell update and x_1 . K.  Loads return in order, so everything consumed
+    // in front of that run is requested - and has landed - in front of the 64 loads of the R pack: the header words, bias,
+    // K, x_0 / x_1, the poison word, the hello sweep.  The pack is requested last, behind the tile's barrier and spread over the
+    // MFMAs of x_0 . K and x_1 . K (see there), and lands under step 0; nothing between its first request and step 0's
+    // own-slice run waits for one of its registers (tools/isa_waits.py).  The first wait that covers the pack's tail is the
+    // tag check of step 0's gather, whose loads are younger: every later step - and, where T = 1, the decoder phase that
+    // loads its own R into these registers (loads return in order) - finds everything that was requested landed.
+    constexpr bool KF = PK && F1;
+    f32x4 kv[KF ? CL_MAX_F / 16 : 1][4];   // (KF) the K slice between its request and its LDS store
+    float xpre_kf[2][XR];                  // (KF) x_0, x_1 of the tile
+    unsigned poison_word = 0;              // (KF) requested with the weights, tested behind them
+    if constexpr (KF) {
+        load_k_slice<H>(bias, kv, Kp, bp, F, col0, lane);
+        load_x01(xpre_kf, p, group, F, tid);
+        if constexpr (G > 1) poison_word = xch_timeout_word(p.status);   // (F1: hdr == (G > 1); no run-time branch around a load)
+    } else if constexpr (F2) {
         load_dec_small<H>(bias, kb, Kp, bp, F, col0, lane);
     } else if constexpr (PK) {
         load_r_packed<H, 0, JA>(wR, Rpk, col0, slice, lane);
@@ -543,14 +619,18 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         xch_count_arrival(p.status);   // both header words have landed (stored above)
     }
     FOV_PSTAMP(3);
-    if constexpr (PK && !F2) {
+    if constexpr (KF) {
+        // the x tiles are zeroed while K is in flight (depends on nothing); then the slice goes to LDS
+        for (int i = tid; i < NXBUF * BT * LDX; i += 256) sX[i] = 0.f;
+        store_k_slice(kv, sKw, nq, lane);
+    } else if constexpr (PK && !F2) {
         load_r_packed<H, JA, NQ>(wR, Rpk, col0, slice, lane);
         load_weights<H, !LAYER, NQ, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);   // (no R block: bias and K)
     } else if constexpr (!F2) {
         load_weights<H, !LAYER, JA, NQ, true>(wR, bias, sKw, Kp, Rp, bp, F, Fp, col0, slice, lane);
     }
     FOV_PSTAMP(2);
-    const bool poisoned = hdr && xch_poisoned(p.status);   // one wave-wide load per wave; wave 0's value decides (sFlag[0])
+    const bool poisoned = hdr && (KF ? xch_timeout_set(poison_word) : xch_poisoned(p.status));   // one wave-wide load per wave; wave 0's value decides (sFlag[0])
     if (tid == 0) { sFlag[0] = (poisoned || (F2 && cy.aborted)) ? 1 : 0; sFlag[1] = 0; }
     if (hdr && !poisoned && tid < G) {   // (lanes of wave 0: thread 0 has just written sFlag, program order)
         const unsigned long long hello_tag = (unsigned long long)sXch[0] + 1ull;
@@ -571,8 +651,9 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
     FOV_PSTAMP(4);
     // x_0, x_1 of the FIRST tile are requested here, in front of the prologue's barrier (their round trip used to sit between
     // that barrier and the tile's: 1.5 us of the launch's fixed part)
+    // (KF: requested with K - xpre_kf - and zeroed under it, above)
     float xpre[2][XR];
-    {
+    if constexpr (!KF) {
         const int xrw0 = tid >> 4, xcl0 = tid & 15;
         const bool xuse0 = LAYER && !ZX;
         const int b00 = group * BT;
@@ -587,7 +668,8 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                     xg0, (tt < steps && xcl0 + 16 * i < F) ? (unsigned)((xrw0 * p.T * F + xcl0 + 16 * i) * 4) : OORB, (unsigned)(tt * F * 4), 0));
     }
     // zero the x tiles once: pad columns [F, Fp) are never written afterwards
-    for (int i = tid; i < NXBUF * BT * LDX; i += 256) sX[i] = 0.f;
+    if constexpr (!KF)
+        for (int i = tid; i < NXBUF * BT * LDX; i += 256) sX[i] = 0.f;
 
     // DECODE: Dense(F_dec, tanh) runs on the matrix pipe, transposed: y^T = Wd^T . h^T, and is DISTRIBUTED (round 5): every wave
     // forms the partial product over ITS OWN 16 units (4 MFMAs on the columns it wrote to LDS) in the shadow of the gather of
@@ -674,6 +756,9 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         const int osl = (slice + rot) & (G - 1);
         goff[j] = (unsigned)((within >> 6) * H + osl * 64 + (within & 63)) * 16u;
         loff[j] = 2 * (within >> 6) * LDH + rot * 64 + (within & 63);
+        // (KF: opaque, one register each as in every other kernel - hipcc re-formed them from two addends in every step here,
+        // six VALU adds in the steady-state loop, tools/isa_step_counts.py)
+        if constexpr (KF) asm volatile("" : "+v"(loff[j]));
     }
 
     // DECODE: the workgroups' Dense partials travel like h - tagged granules in an area of their own behind the hello words,
@@ -714,6 +799,12 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             if constexpr (F2) {   // handed over in registers by the encoder phase
                 c[r] = cy.c[r];
                 hcur[r] = cy.h[r];
+            } else if constexpr (KF) {
+                // the zero state the NULL descriptors below return, without the loads: c is read by step 0's cell update.
+                // Opaque, so that the update stays the arithmetic it is (fmaf(f, 0, i * g), not i * g).
+                c[r] = 0.f;
+                hcur[r] = 0.f;
+                asm volatile("" : "+v"(c[r]));
             } else {
                 c[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(c0rs, off, 0, 0));
                 hcur[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(h0rs, off, 0, 0));
@@ -756,7 +847,7 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-                    for (int i = 0; i < XR; ++i) x2[tt][i] = xpre[tt][i];
+                    for (int i = 0; i < XR; ++i) x2[tt][i] = KF ? xpre_kf[tt][i] : xpre[tt][i];
             } else {
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt)
@@ -794,6 +885,26 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         }
         __syncthreads();
         FOV_PSTAMP(6);
+        // KF: the R pack is requested from here on, behind the last consumer of an older load (the x tiles' stores above) and
+        // behind the barrier (in front of a barrier with 64 loads in flight hipcc puts s_waitcnt vmcnt(63) - a wait for the
+        // pack's head).  Not in one go: with all 64 requests in one place the stamps read 2.35 us between the barrier and the
+        // first MFMA - the four waves' 256 KB leave the CU's load path at some 64 bytes a clock, about 16 clocks per 16-byte
+        // wave load, and a wave that is issuing loads issues nothing else.  A k-step of x . K - four MFMAs, 128 clocks on each
+        // of the four SIMDs - is then the time two loads per wave take: two go out in front of each of the 24 k-steps of
+        // x_0 . K (k-blocks [0, R_EARLY = 12), in order: the own-slice blocks first), one in front of each of the first 16 of
+        // x_1 . K (step 0 below).  Any other input width: the same blocks at the same two places, each lot in one go.
+        constexpr int R_EARLY = NQ < 12 ? NQ : 12;
+        auto r_with_x0 = [&](const int q, const int s) __attribute__((always_inline)) {   // loads 2i, 2i + 1 of the pack, i = 4q + s
+            const int j = (4 * q + s) >> 1, s2 = 2 * (s & 1);
+            if (j < R_EARLY) {
+                load_r_frag_packed<H>(wR, j, s2, Rpk, col0, slice, lane);
+                load_r_frag_packed<H>(wR, j, s2 + 1, Rpk, col0, slice, lane);
+            }
+        };
+        auto r_with_x1 = [&](const int q, const int s) __attribute__((always_inline)) {   // load 4 R_EARLY + i, i = 4q + s
+            if (R_EARLY + q < NQ) load_r_frag_packed<H>(wR, R_EARLY + q, s, Rpk, col0, slice, lane);
+        };
+        if constexpr (KF) FOV_PSTAMP(7);
 
         // ---- pre-activations of step 0 that need no remote data ----
         // The splatted bias is the C operand of the first MFMA on each accumulator of every step (mfma_f32_c).  Opaque to
@@ -817,7 +928,14 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         // for them, vmcnt(19) down to vmcnt(0) - i.e. for the previous step's publish stores as well - at the top of EVERY step)
         if ((F2 && PK) || steps > 0) {
             if constexpr (ZX) input_proj_any<true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane);   // (nq = 0: nothing)
-            else if constexpr (LAYER) input_proj_any<true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane, bias4);
+            else if constexpr (KF) {
+                if (nq == 6) {
+                    input_proj_fixed<6, true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, lane, bias4, r_with_x0);
+                } else {
+                    load_r_packed<H, 0, R_EARLY>(wR, Rpk, col0, slice, lane);
+                    input_proj<true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane, bias4);
+                }
+            } else if constexpr (LAYER) input_proj_any<true, true, true>(acc, sX + n * LDX + 4 * g4, sKw, nq, lane, bias4);
             else input_proj_reg<true, true>(acc, y4, kb, bias4);
             // a zero initial state (the encoder of every seq2seq call): h_0 . R is exactly 0 - its 4H/16 k-blocks (256 of the
             // 352 MFMAs of an encoder step at H = 256) are skipped here and at the top of step 0
@@ -851,8 +969,10 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
         // One step.  ST = the steady-state copy of the fused kernel (see the driver loop below): same-XCD exchange, t > 0,
         // t + 2 < steps (decoder: t + 1 < steps) and, in the encoder phase, six input k-blocks are compile-time facts there,
         // so its body is straight-line code between the barriers and the bounded spin loops.  Returns false on an abort.
-        auto step = [&](const int t, auto st_c) __attribute__((always_inline)) -> bool {
+        // K1 = step 0 of the K-first encoder phase (KF), on which the R pack is still landing: see the gather below.
+        auto step = [&](const int t, auto st_c, auto k1_c) __attribute__((always_inline)) -> bool {
             constexpr bool ST = decltype(st_c)::value;
+            constexpr bool K1 = decltype(k1_c)::value;
             const bool t_pos = ST || t > 0;
             const bool more = ST || (t + 1 < steps);
             const bool more2 = ST || (t + 2 < steps);
@@ -1026,6 +1146,15 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
                     for (int g = 0; g < 4; ++g) acc[g] = zr[g];
                 } else if constexpr (LAYER && ST) {
                     input_proj_fixed<6, true, false, true>(acc, xa, sKw, lane, bias4);
+                } else if constexpr (K1) {
+                    // the rest of the R pack goes out with x_1 . K (T = 1: never requested, and never read - the decoder phase
+                    // loads its own R into these registers)
+                    if (nq == 6) {
+                        input_proj_fixed<6, true, false, true>(acc, xa, sKw, lane, bias4, r_with_x1);
+                    } else {
+                        load_r_packed<H, R_EARLY, NQ>(wR, Rpk, col0, slice, lane);
+                        input_proj<true, false, true>(acc, xa, sKw, nq, lane, bias4);
+                    }
                 } else if constexpr (LAYER) {
                     input_proj_any<true, false, true>(acc, xa, sKw, nq, lane, bias4);
                 }
@@ -1037,7 +1166,14 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             // eight-workgroup kernels, whose stores are sc1, gain far more from the same delay - lstm_wide.hip)
             constexpr int GJ = LAYER ? 0 : 1;
             // (one branch around both MFMA runs: where two `if (more)` met, hipcc copied the accumulators between them)
-            if (more) {
+            if constexpr (K1) {
+                // One request of the gather on both ways.  With one in each arm of the branch below hipcc waits at the head of the
+                // `more` arm - vmcnt(2) to vmcnt(0), i.e. for the whole R pack - before it reuses the registers the OTHER arm's
+                // loads were given.  The accumulator copies that two `if (more)` cost are paid in this one step.
+#pragma unroll
+                for (int j = 0; j < NG; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(xrs, goff[j], xsoff, 16);
+                if (more) recurrent<H, 0, 4, true, (G == 1)>(acc, hrow, wR);
+            } else if (more) {
                 recurrent<H, 0, GJ, true, false, true>(acc, hrow, wR, bias4);   // (DECODE only: GJ = 0 is no run)
                 if (do_xch) {
 #pragma unroll
@@ -1112,6 +1248,10 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             FOV_STAMP(6);
             __syncthreads();  // barrier 2: the whole h_t tile is in LDS
             FOV_STAMP(7);
+            // (K1 without partners: no tag check has waited for loads younger than the R pack, and with T = 1 no MFMA has read it -
+            // the pack counts as landed from here on, so that the loop below waits for none of it in every step.  vmcnt(0) only;
+            // the loads of x_2, the youngest, went out before the step's MFMAs)
+            if constexpr (K1 && G == 1) __builtin_amdgcn_s_waitcnt(0x0F70);
             if (G > 1 && sFlag[0]) { aborted = true; return false; }
             if (!LAYER && G > 1 && wave == 0) {      // the workgroup's Dense partial of y_t, tagged like h_t
                 const f32x2 mine = own_partial(t & 1);
@@ -1131,11 +1271,13 @@ __device__ __forceinline__ void cluster_body(const LstmParams& p, ClusterCarry& 
             if constexpr (FZ) {
                 constexpr int TAIL = LAYER ? 2 : 1;
                 const bool fast = (G > 1) && same_xcd && (!LAYER || nq == 6);
-                if (steps > 0) { go = step(0, BoolC<false>{}); t = 1; }
+                // (KF: unconditional, as z_0 of the packed decoder phase above and for the same reason - the fused launch always has
+                // steps, and a way into the loops that passes no step 0 is one on which the R pack is in flight)
+                if (KF || steps > 0) { go = step(0, BoolC<false>{}, BoolC<KF>{}); t = 1; }
                 if (fast)
-                    for (; go && t + TAIL < steps; ++t) go = step(t, BoolC<true>{});
+                    for (; go && t + TAIL < steps; ++t) go = step(t, BoolC<true>{}, BoolC<false>{});
             }
-            for (; go && t < steps; ++t) go = step(t, BoolC<false>{});
+            for (; go && t < steps; ++t) go = step(t, BoolC<false>{}, BoolC<false>{});
         }
         if (!LAYER && steps > 0 && !aborted) {
             // y of the last step: the workgroups' partials were published behind the last barrier 2 - one wave of the tile waits for them

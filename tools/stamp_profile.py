@@ -57,6 +57,12 @@ def main():
         names = ["entry", "loop left", "weights issued (K in LDS)", "arrival ticket taken", "hello handshake done", "first barrier passed", "tile state + x tiles in LDS"]
         print("   prologue (us after phase entry): " + ", ".join("%s %.2f" % (names[i], (pro[i] - pro[0]) / ghz * 1e-3) for i in (2, 3, 4, 5, 6))
               + ", first step %.2f" % ((int(st[0, 0]) - pro[0]) / ghz * 1e-3))
+        # slot 7 of the prologue row: the R pack requested (K-first encoder phase of the packed kernel only; 0 = not stamped);
+        # step 0 against the median step: a stall in front of its own-slice run shows in the last figure
+        us = lambda a, b: (int(b) - int(a)) / ghz * 1e-3
+        print("   R pack requested %s; step 0: top -> cell update %.2f us, x(1).K %.2f us (median %.2f), gather issue + own-slice MFMAs %.2f us (median %.2f)"
+              % ("%.2f" % us(pro[0], buf[mode, 63, 7]) if buf[mode, 63, 7] else "-", us(st[0, 0], st[0, 1]), us(st[0, 4], st[0, 5]),
+                 np.median(seg[1:, 4]) / ghz * 1e-3, us(st[0, 5], buf[mode, 0, 11]), np.median(own) / ghz * 1e-3))
         med = np.median(seg[1:], axis=0)
         for i, v in enumerate(med):
             print("   %-34s %8.0f cyc %7.0f ns  %5.1f%%" % (SEG[i], v, v / ghz, 100.0 * v / med.sum()))
