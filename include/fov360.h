@@ -502,6 +502,58 @@ int fov_selffed_decoder_bwd(const float* Cs, const float* XA, const float* A, co
                             float* DY, float* DPRE, float* DZ, float* dx0, float* dh0, float* dc0,
                             int B, int T, int O, int H, int act, int dact, int a_from_A, fov_stream_t stream);
 
+/* The self-fed TWO-layer decoder of mycode/given_others_gt_mean_var_seq2seq.py:203-299 (the unrolled loop over predict_step
+ * seconds; heads `target_user_only` :219-220, `others_mlp` :223-233, `others_lstm` :234-240; its gradient is Keras autodiff
+ * under model.fit) as ONE launch per direction, fp32 on the matrix core, exact expf / tanhf.  The others only enter through a
+ * per-step context that does not depend on the decoder: the caller projects it through its rows of decoder_dense once
+ * (ctx (B,T,O) = ctx_t . W_c [+ bias]) and the head adds it inside the tanh.  One workgroup owns a 16-sequence tile for both
+ * layers and every step: no workspace, no library state, nothing to wait on; rows of a ragged last tile beyond B read zeros and
+ * store nothing.
+ *
+ * fov_selffed2_decoder_fwd - replaces the T iterations of :209-299.  From x0 (B,O) and the states h1_0, c1_0, h2_0, c2_0 (B,H;
+ * each may be NULL = zeros), for t < T:
+ *   z1 = b1 + x_t . K1 + h1 . R1     -> the Keras cell update -> h1_t, c1_t
+ *   z2 = b2 + h1_t . K2 + h2 . R2    -> the Keras cell update -> h2_t, c2_t                     (sums in this order)
+ *   y_t = tanh(bd + h2_t . W + ctx[:, t]);   x_{t+1} = y_t, kept on the chip
+ * K1 (O,4H), K2, R1, R2 (H,4H), b1, b2 (4H), W (H,O), Keras gate order; bd (O) and ctx (B,T,O) are each optional (NULL = absent).
+ * act: FOV_ACT_*.  Outputs, each of which may be NULL and is then not written - the tapes of the training step, time-major:
+ *   H1, C1, H2, C2 (T+1,B,H)  row t = state before step t (row 0 = the initial state)
+ *   XY (T+1,B,O)              row 0 = x0, row t+1 = y_t
+ *   RES1, RES2 (T,B,1,5,H)    activated i, f, g, o and c of step t (the reserve layout of fov_lstm_seq_fwd_train at T = 1)
+ *   y (B,T,O)                 the prediction, batch-major
+ *   hT, cT (2,B,H)            the final states, layer 1 then layer 2
+ * With every tape NULL the call is the inference forward.
+ *
+ * fov_selffed2_decoder_bwd - replaces Keras autodiff through that loop.  dloss (T,B,O) = dL/dy_t.  For t = T-1 .. 0:
+ *   dy_t = dloss_t + dx_{t+1};  dpre_t = dy_t (1 - y_t^2)  with y_t = XY[t+1]
+ *   dh2 = dpre_t . W^T + dz2_{t+1} . R2^T;  the cell's pointwise backward (stored gates, c_{t-1} = C2[t]) -> dz2_t
+ *   dh1 = dz2_t . K2^T + dz1_{t+1} . R1^T;  the cell's pointwise backward (stored gates, c_{t-1} = C1[t]) -> dz1_t
+ *   dx_t = dz1_t . K1^T                                                       (dx_T = dz1_T = dz2_T = 0)
+ * Outputs: DPRE (T,B,O), DZ1, DZ2 (T,B,4H), and dx0 (B,O), dh1_0, dc1_0, dh2_0, dc2_0 (B,H), each of these five optional (NULL
+ * = not written).  The final states carry no incoming gradient.  The weight gradients are products over all steps of these
+ * tapes (fov_dense_bwd); the gradient of ctx is DPRE.
+ *
+ * Shapes: 1 <= O <= 8, B >= 0, T >= 0; H = 32 or 64 for the forward, H = 32 for the backward (R2^T, K2^T and R1^T stay in LDS:
+ * 48 KB at H = 32, 192 KB at H = 64, more than a CU has).  Anything else is FOV_ERR_UNSUPPORTED, decided before any pointer is
+ * looked at and before any HIP call.  A missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 or T = 0
+ * launches nothing: the forward then writes nothing (no tape row 0 either); the backward sets dx0 and the four state gradients
+ * to zero with T = 0.  fov_selffed2_decoder_supported(B, T, O, H, backward) is the shape rule of the forward (backward = 0) or
+ * of the backward (backward != 0) as arithmetic (no device query), and 0 under FOV_NO_SELFFED2_FUSED=1 (the caller's host loop
+ * stays: A/B timing, cross-check); the two entries do not read the knob. */
+int fov_selffed2_decoder_supported(int B, int T, int O, int H, int backward);
+int fov_selffed2_decoder_fwd(const float* x0, const float* h1_0, const float* c1_0, const float* h2_0, const float* c2_0,
+                             const float* K1, const float* R1, const float* b1, const float* K2, const float* R2, const float* b2,
+                             const float* W, const float* bd, const float* ctx,
+                             float* H1, float* C1, float* H2, float* C2, float* XY, float* RES1, float* RES2, float* y,
+                             float* hT, float* cT,
+                             int B, int T, int O, int H, int act, fov_stream_t stream);
+int fov_selffed2_decoder_bwd(const float* C1, const float* C2, const float* XY, const float* RES1, const float* RES2,
+                             const float* dloss,
+                             const float* K1, const float* R1, const float* K2, const float* R2, const float* W,
+                             float* DPRE, float* DZ1, float* DZ2, float* dx0,
+                             float* dh1_0, float* dc1_0, float* dh2_0, float* dc2_0,
+                             int B, int T, int O, int H, int act, fov_stream_t stream);
+
 /* The 2- and 3-layer target-only seq2seq model's TRAINING graph as ONE launch per direction (replaces the layer-by-layer
  * graph of mycode/Fov_seq2seq_2layers.py:232-272 under model.fit / model.predict, :332-343, and 3layers.py's): fp32 on the matrix
  * core, exact expf / tanhf, pre-activations summed in the order bias, x . K, h . R.  One workgroup owns a 16-sequence tile for

@@ -60,6 +60,9 @@ SIGNATURES = {
     "fov_selffed_decoder_supported": (_I, [_I] * 4),
     "fov_selffed_decoder_fwd": (_I, [_P] * 15 + [_I] * 6 + [_P]),
     "fov_selffed_decoder_bwd": (_I, [_P] * 14 + [_I] * 7 + [_P]),
+    "fov_selffed2_decoder_supported": (_I, [_I] * 5),
+    "fov_selffed2_decoder_fwd": (_I, [_P] * 24 + [_I] * 5 + [_P]),
+    "fov_selffed2_decoder_bwd": (_I, [_P] * 19 + [_I] * 5 + [_P]),
     "fov_stacked_seq2seq_train_supported": (_I, [_I] * 7),
     "fov_stacked_seq2seq_train_bwd_scratch_bytes": (_SZ, [_I] * 4),
     "fov_stacked_seq2seq_train_fwd": (_I, [_P] * 15 + [_I] * 8 + [_P]),

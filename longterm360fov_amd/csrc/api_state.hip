@@ -64,6 +64,7 @@ void env_reload() {
     g_env.no_stack2 = env_flag("FOV_NO_STACK2");
     g_env.no_stacked_decode = env_flag("FOV_NO_STACKED_DECODE");
     g_env.no_selffed_fused = env_flag("FOV_NO_SELFFED_FUSED");
+    g_env.no_selffed2_fused = env_flag("FOV_NO_SELFFED2_FUSED");
     g_env.no_stacked_train = env_flag("FOV_NO_STACKED_TRAIN");
     g_env.bwd_stepped = getenv("FOV_BWD_STEPPED") ? 1 : 0;
     g_env.no_wgrad_fusion = getenv("FOV_NO_WGRAD_FUSION") ? 1 : 0;

@@ -105,6 +105,7 @@ int launch_cluster_decoder(const LstmParams& p, hipStream_t stream);   // MODE_D
 bool cluster_shape_ok(int F, int H);
 bool stacked_s2s_shape_ok(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);   // lstm_stacked_s2s.hip, lstm_stacked_train.hip: the L-layer seq2seq decode / training graph as one launch per direction
 bool selffed_shape_ok(int B, int T, int O, int H);   // lstm_selffed.hip: the self-fed one-layer decoder's unroll (forward with tapes, BPTT) as one launch each
+bool selffed2_shape_ok(int B, int T, int O, int H, bool backward);   // lstm_selffed2.hip: the self-fed two-layer decoder's unroll; the BPTT at H = 32 only
 size_t cluster_workspace_bytes(int B, int H);
 int cluster_num_groups(int B, int H);
 int device_cu_count();                               // CUs of the current device a persistent grid may count on (FOV_DBG_RESIDENT_LIMIT caps it: tests)
@@ -124,6 +125,7 @@ struct EnvKnobs {
     int no_wgrad_bf16_tiles;   // FOV_NO_WGRAD_BF16_TILES=1: the bf16 Conv2D weight gradient on its plain kernel (tests; conv_wgrad_bf16.hip)
     int no_stacked_decode;     // FOV_NO_STACKED_DECODE=1: fov_stacked_seq2seq_decode_supported -> 0, the stacked model's decode stays a host loop (tests / A-B timing)
     int no_selffed_fused;      // FOV_NO_SELFFED_FUSED=1: fov_selffed_decoder_supported -> 0, the self-fed decoder's unroll stays a host loop (tests / A-B timing)
+    int no_selffed2_fused;     // FOV_NO_SELFFED2_FUSED=1: fov_selffed2_decoder_supported -> 0, the self-fed two-layer decoder's unroll stays a host loop (tests / A-B timing)
     int no_stacked_train;      // FOV_NO_STACKED_TRAIN=1: fov_stacked_seq2seq_train_supported -> 0, the stacked model trains and predicts layer by layer (tests / A-B timing)
 };
 const EnvKnobs& env_knobs();

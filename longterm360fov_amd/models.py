@@ -1149,7 +1149,8 @@ class OthersContextSeq2Seq(KerasModelSurface):
       mode='others_lstm'       two Bidirectional LSTMs over the others' future mu/var, concatenated with h2_t    (:157-166,234-240)
     (`mlp_mixing`, the flag the script ships, is OthersMixingSeq2Seq.)  Inputs as the script's Model (:301-307):
     [encoder_input (N,T_in,F), others_fut_input (N,T_out,U-1,6), decoder_input (N,1,6)] -> (N,T_out,6);
-    'target_user_only' takes [encoder_input, decoder_input]."""
+    'target_user_only' takes [encoder_input, decoder_input].  At latent_dim 32 and 64 predict runs the unrolled decoder as ONE
+    launch (fov_selffed2_decoder_fwd); training: training.OthersContextTrainer."""
 
     def __init__(self, mode, num_encoder_tokens=None, num_decoder_tokens=6, latent_dim=32, num_user=34, recurrent_activation=None,
                  seed=None, impl="auto", device="cuda", predict_step=None):
@@ -1225,6 +1226,11 @@ class OthersContextSeq2Seq(KerasModelSurface):
             hs1, h1, c1 = ops.lstm_seq(e, dw["enc1_K"], dw["enc1_R"], dw["enc1_b"], act=act, impl=self.impl, workspace=self._ws)
             _, h2, c2 = ops.lstm_seq(hs1, dw["enc2_K"], dw["enc2_R"], dw["enc2_b"], act=act, impl=self.impl, return_sequences=False,
                                      workspace=self._ws)
+            if self.impl == "auto" and ops.selffed2_decoder_supported(B, T_out, O, H):
+                # ONE launch, no tapes (lstm_selffed2.hip); the head's bias is inside ctx_proj where there is a context
+                return ops.selffed2_decoder_fwd(xin.reshape(B, O), dw, W_h, T_out, act=act, tape=False,
+                                                states={"h1_0": h1, "c1_0": c1, "h2_0": h2, "c2_0": c2},
+                                                bd=dw["dense_b"] if ctx_proj is None else None, ctx=ctx_proj)[0]
             xin = xin.reshape(B, 1, O)
             y = torch.empty((B, T_out, O), dtype=torch.float32, device=self.device)
             for t in range(T_out):

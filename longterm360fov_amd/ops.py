@@ -53,7 +53,7 @@ def _stream():
 _ENV_KNOBS = ("FOV_FORCE_SAFE_EXCHANGE", "FOV_TWO_LAUNCHES", "FOV_DBG_RESIDENT_LIMIT", "FOV_NO_CELL_PATCH", "FOV_NO_CONV_PATCH", "FOV_NO_WIDE16", "FOV_BWD_STEPPED",
               "FOV_NO_WGRAD_FUSION", "FOV_NO_DX_FUSION", "FOV_BWD_GROUPS4", "FOV_GEMM_BF16_NOREMAP", "FOV_GEMM_BF16_SPLIT", "FOV_GEMM_BF16_SHALLOW", "FOV_NO_WGRAD_GROUP", "FOV_NO_WIDE16_TRIO", "FOV_DBG_TRACE", "FOV_GEMM_VARIANT",
               "FOV_GEMM_SPLIT", "FOV_NO_XCD_PAD", "FOV_XCD_PAD_MAX", "FOV_NO_BWD16_NARROW", "FOV_BWD16_GROUPS", "FOV_NO_STACK2", "FOV_NO_WGRAD_LINES", "FOV_NO_WGRAD_BF16_TILES", "FOV_NO_STACKED_DECODE",
-              "FOV_NO_SELFFED_FUSED", "FOV_NO_STACKED_TRAIN")
+              "FOV_NO_SELFFED_FUSED", "FOV_NO_STACKED_TRAIN", "FOV_NO_SELFFED2_FUSED")
 _env_seen = None
 # os.environ.get costs 0.7 us per key (encode, lookup, decode): 9 us for the knob list, paid at every workspace / scratch
 # fetch - 0.15 ms of a 0.3 ms training step at batch 32.  The mapping underneath (bytes -> bytes on POSIX) answers the
@@ -396,6 +396,94 @@ def selffed_decoder_bwd(tp, dloss, K, R, W, act="sigmoid", dense_activation="tan
                                              _ptr(dloss), _ptr(_dev(K, "K")), _ptr(_dev(R, "R")), _ptr(_dev(W, "W")), _ptr(o["DY"]),
                                              _ptr(o["DPRE"]), _ptr(o["DZ"]), _ptr(o["dx0"]), _ptr(o["dh0"]), _ptr(o["dc0"]), B, T, O, H,
                                              act_code(act), _ACT_CODES[dense_activation], 0 if A is None else 1, _stream()))
+    return o
+
+
+def selffed2_decoder_supported(B, T, O, H, backward=False):
+    """Shapes fov_selffed2_decoder_fwd (backward=False: H = 32 or 64) / _bwd (backward=True: H = 32) take, 1 <= O <= 8, any batch
+    and length; False under FOV_NO_SELFFED2_FUSED=1.  Arithmetic only: answers on a machine without a GPU."""
+    _sync_env()
+    return bool(_lib.lib().fov_selffed2_decoder_supported(B, T, O, H, 1 if backward else 0))
+
+
+_S2_STATES = ("h1_0", "c1_0", "h2_0", "c2_0")
+_S2_TAPES = ("H1", "C1", "H2", "C2", "XY", "RES1", "RES2")
+
+
+def selffed2_decoder_fwd(x0, w, W, T, states=None, bd=None, ctx=None, act="sigmoid", tape=True, tapes=None, out=None,
+                         hT=None, cT=None):
+    """The self-fed two-layer decoder (given_others_gt_mean_var_seq2seq.py:203-299) unrolled T times in one launch: x0 (B,O),
+    w: dec1_K/R/b, dec2_K/R/b, W (H,O) the head; states: dict h1_0, c1_0, h2_0, c2_0 (B,H), each absent or None for zeros;
+    y_t = tanh(bd + h2_t . W + ctx[:, t]) fed back as x_{t+1} (bd (O), ctx (B,T,O) optional).  -> (y (B,T,O), tapes),
+    tapes = None without `tape`, else the trainer's time-major dict H1, C1, H2, C2 (T+1,B,H), XY (T+1,B,O), RES1, RES2
+    (T,B,1,5,H); `tapes` hands in preallocated ones (any subset; the rest is allocated here).  hT / cT (2,B,H): the final
+    states, if wanted.  T = 0: no launch; row 0 of the tapes (the initial states, zeros without, and x0) is written here.  No
+    workspace."""
+    x0 = _dev(x0, "x0")
+    B, O = x0.shape
+    H = w["dec1_R"].shape[0]
+    T = int(T)
+    states = states or {}
+    assert w["dec1_K"].shape == (O, 4 * H) and W.shape == (H, O) and (bd is None or bd.shape == (O,))
+    for k in ("dec1_R", "dec2_K", "dec2_R"):
+        assert w[k].shape == (H, 4 * H), k
+    assert w["dec1_b"].shape == (4 * H,) and w["dec2_b"].shape == (4 * H,)
+    for k in _S2_STATES:
+        assert states.get(k) is None or states[k].shape == (B, H), k
+    assert ctx is None or (ctx.shape == (B, T, O) and ctx.is_contiguous())
+    e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=x0.device)
+    y = e(B, T, O) if out is None else out
+    assert _dev(y, "out").shape == (B, T, O)
+    for s_, name in ((hT, "hT"), (cT, "cT")):
+        assert s_ is None or _dev(s_, name).shape == (2, B, H), name
+    tp = None
+    if tape:
+        shapes = {"H1": (T + 1, B, H), "C1": (T + 1, B, H), "H2": (T + 1, B, H), "C2": (T + 1, B, H), "XY": (T + 1, B, O),
+                  "RES1": (T, B, 1, 5, H), "RES2": (T, B, 1, 5, H)}
+        tp = dict(tapes or {})
+        for k, s_ in shapes.items():
+            if tp.get(k) is None:
+                tp[k] = e(*s_)
+            assert _dev(tp[k], k).shape == s_ and tp[k].is_contiguous(), k
+    g = (lambda k: None) if tp is None else (lambda k: _ptr(tp[k]))
+    check(_lib.lib().fov_selffed2_decoder_fwd(_ptr(x0), *[_ptr(_dev(states.get(k), k)) for k in _S2_STATES],
+                                              *[_ptr(_dev(w[k], k)) for k in ("dec1_K", "dec1_R", "dec1_b", "dec2_K", "dec2_R", "dec2_b")],
+                                              _ptr(_dev(W, "W")), _ptr(_dev(bd, "bd")), _ptr(_dev(ctx, "ctx")), *[g(k) for k in _S2_TAPES],
+                                              _ptr(y), _ptr(hT), _ptr(cT), B, T, O, H, act_code(act), _stream()))
+    if tp is not None and T == 0:      # the entry writes nothing without a step: row 0 of the tapes is the initial state and x0
+        for k, src in (("H1", "h1_0"), ("C1", "c1_0"), ("H2", "h2_0"), ("C2", "c2_0")):
+            if states.get(src) is None:
+                tp[k].zero_()
+            elif tp[k][0].data_ptr() != states[src].data_ptr():
+                tp[k][0].copy_(states[src])
+        tp["XY"][0].copy_(x0)
+    return y, tp
+
+
+def selffed2_decoder_bwd(tp, dloss, w, W, act="sigmoid", need_dx0=True, need_state_grads=True):
+    """BPTT of selffed2_decoder_fwd through the feedback in one launch (H = 32).  tp: the tapes (C1, C2, XY, RES1, RES2); dloss
+    (T,B,O) = dL/dy_t, time-major.  -> dict DPRE (T,B,O), DZ1, DZ2 (T,B,4H), dx0 (B,O) (None without need_dx0), dh1_0, dc1_0,
+    dh2_0, dc2_0 (B,H) (None without need_state_grads).  The weight gradients are dense_bwd products over these tapes; the
+    context's gradient is DPRE."""
+    dloss = _dev(dloss, "dloss")
+    T, B, O = dloss.shape
+    H = w["dec1_R"].shape[0]
+    assert dloss.is_contiguous() and w["dec1_K"].shape == (O, 4 * H) and W.shape == (H, O)
+    for k in ("dec1_R", "dec2_K", "dec2_R"):
+        assert w[k].shape == (H, 4 * H), k
+    for k in ("C1", "C2"):
+        assert _dev(tp[k], k).shape == (T + 1, B, H) and tp[k].is_contiguous(), k
+    assert _dev(tp["XY"], "XY").shape == (T + 1, B, O) and tp["XY"].is_contiguous()
+    for k in ("RES1", "RES2"):
+        assert _dev(tp[k], k).numel() == T * B * 5 * H and tp[k].is_contiguous(), k
+    e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=dloss.device)
+    o = {"DPRE": e(T, B, O), "DZ1": e(T, B, 4 * H), "DZ2": e(T, B, 4 * H), "dx0": e(B, O) if need_dx0 else None}
+    for k in ("dh1_0", "dc1_0", "dh2_0", "dc2_0"):
+        o[k] = e(B, H) if need_state_grads else None
+    check(_lib.lib().fov_selffed2_decoder_bwd(*[_ptr(tp[k]) for k in ("C1", "C2", "XY", "RES1", "RES2")], _ptr(dloss),
+                                              *[_ptr(_dev(w[k], k)) for k in ("dec1_K", "dec1_R", "dec2_K", "dec2_R")], _ptr(_dev(W, "W")),
+                                              *[_ptr(o[k]) for k in ("DPRE", "DZ1", "DZ2", "dx0", "dh1_0", "dc1_0", "dh2_0", "dc2_0")],
+                                              B, T, O, H, act_code(act), _stream()))
     return o
 
 

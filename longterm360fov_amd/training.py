@@ -951,8 +951,10 @@ class OthersContextTrainer(FlatParamTrainer):
     forcing, Adam + MSE): `target_user_only` (:219-220), `others_mlp` (:153-156,223-233), `others_lstm` (two Bidirectional
     LSTMs over the others' future mu/var, :157-166,234-240).  The others only enter through a per-step context that
     does not depend on the decoder, so its projection through decoder_dense is ONE product hoisted out of the unrolled
-    loop (y_t = tanh(h2_t W_h + [ctx_t W_c + b])) and so is its gradient; the decoder is walked step by step on the
-    layer kernels, weight gradients are one product over all steps."""
+    loop (y_t = tanh(h2_t W_h + [ctx_t W_c + b])) and so is its gradient.  The unrolled decoder is ONE launch per direction
+    (lstm_selffed2.hip: the forward at width 32 or 64, the BPTT at width 32; the two choices are independent and both write /
+    read the walk's tapes) or, for every other width, under FOV_NO_SELFFED2_FUSED=1 and for impl != 'auto', walked step by
+    step on the layer kernels; weight gradients are one product over all steps."""
 
     def __init__(self, weights, mode, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda"):
         assert mode in ("target_user_only", "others_mlp", "others_lstm")
@@ -1025,37 +1027,50 @@ class OthersContextTrainer(FlatParamTrainer):
                                              out=(e(B, T_in, H), H2[0], C2[0], e(B, T_in, 5, H)))
         XY = e(T_out + 1, B, O)
         R1, R2 = e(T_out, B, 1, 5, H), e(T_out, B, 1, 5, H)
-        XY[0].copy_(dec0.reshape(B, O))
-        for t in range(T_out):
-            ops.lstm_seq_train(XY[t].view(B, 1, O), w["dec1_K"], w["dec1_R"], w["dec1_b"], H1[t], C1[t], act=act, impl=impl,
-                               workspace=ws, out=(H1[t + 1].view(B, 1, H), None, C1[t + 1], R1[t]))
-            ops.lstm_seq_train(H1[t + 1].view(B, 1, H), w["dec2_K"], w["dec2_R"], w["dec2_b"], H2[t], C2[t], act=act, impl=impl,
-                               workspace=ws, out=(H2[t + 1].view(B, 1, H), None, C2[t + 1], R2[t]))
-            if ctx is None:
-                ops.dense(H2[t + 1], W_h, w["dense_b"], activation="tanh", out=XY[t + 1])
-            else:
-                ops.dense_add(H2[t + 1], W_h, None, ctx_proj[:, t], activation="tanh", out=XY[t + 1])
-        out = XY[1:].transpose(0, 1).contiguous()
+        fused_fwd = impl == "auto" and ops.selffed2_decoder_supported(B, T_out, O, H)
+        fused_bwd = impl == "auto" and ops.selffed2_decoder_supported(B, T_out, O, H, backward=True)
+        if fused_fwd:        # ONE launch; the head's bias is inside ctx_proj where there is a context
+            out, _ = ops.selffed2_decoder_fwd(dec0.reshape(B, O), w, W_h, T_out, act=act,
+                                              states={"h1_0": H1[0], "c1_0": C1[0], "h2_0": H2[0], "c2_0": C2[0]},
+                                              bd=w["dense_b"] if ctx is None else None, ctx=None if ctx is None else ctx_proj,
+                                              tapes={"H1": H1, "C1": C1, "H2": H2, "C2": C2, "XY": XY, "RES1": R1, "RES2": R2})
+        else:
+            XY[0].copy_(dec0.reshape(B, O))
+            for t in range(T_out):
+                ops.lstm_seq_train(XY[t].view(B, 1, O), w["dec1_K"], w["dec1_R"], w["dec1_b"], H1[t], C1[t], act=act, impl=impl,
+                                   workspace=ws, out=(H1[t + 1].view(B, 1, H), None, C1[t + 1], R1[t]))
+                ops.lstm_seq_train(H1[t + 1].view(B, 1, H), w["dec2_K"], w["dec2_R"], w["dec2_b"], H2[t], C2[t], act=act, impl=impl,
+                                   workspace=ws, out=(H2[t + 1].view(B, 1, H), None, C2[t + 1], R2[t]))
+                if ctx is None:
+                    ops.dense(H2[t + 1], W_h, w["dense_b"], activation="tanh", out=XY[t + 1])
+                else:
+                    ops.dense_add(H2[t + 1], W_h, None, ctx_proj[:, t], activation="tanh", out=XY[t + 1])
+            out = XY[1:].transpose(0, 1).contiguous()
         # ---------------- backward ----------------
         dloss, loss = ops.mse_dense_grad(out, target, None, scratch=sc)
         dloss_tm = dloss.transpose(0, 1).contiguous()
-        DY, DPRE, DZ1, DZ2 = e(T_out, B, O), e(T_out, B, O), e(T_out, B, 4 * H), e(T_out, B, 4 * H)
         dh1 = dc1 = dh2 = dc2 = dx_next = None
-        for t in range(T_out - 1, -1, -1):
-            if dx_next is None:
-                DY[t].copy_(dloss_tm[t])
-            else:
-                ops.act_bwd(dx_next.reshape(B, O), XY[t + 1], base=dloss_tm[t], activation=None, out=DY[t])
-            ops.act_bwd(DY[t], XY[t + 1], activation="tanh", out=DPRE[t])
-            dh2_dense, _, _ = ops.dense_bwd(H2[t + 1], W_h, DPRE[t], need_dx=True, need_dW=False, need_db=False, scratch=sc)
-            b2 = ops.lstm_seq_bwd(H1[t + 1].view(B, 1, H), w["dec2_K"], w["dec2_R"], H2[t + 1].view(B, 1, H), R2[t], h0=H2[t],
-                                  c0=C2[t], dhs=dh2_dense.reshape(B, 1, H), dhT=dh2, dcT=dc2, need_dx=True, need_state_grads=True,
-                                  act=act, dz=DZ2[t].view(B, 1, 4 * H), scratch=bsc, need_weight_grads=False)
-            dh2, dc2 = b2["dh0"], b2["dc0"]
-            b1 = ops.lstm_seq_bwd(XY[t].view(B, 1, O), w["dec1_K"], w["dec1_R"], H1[t + 1].view(B, 1, H), R1[t], h0=H1[t],
-                                  c0=C1[t], dhs=b2["dx"], dhT=dh1, dcT=dc1, need_dx=(t > 0), need_state_grads=True, act=act,
-                                  dz=DZ1[t].view(B, 1, 4 * H), scratch=bsc, need_weight_grads=False)
-            dh1, dc1, dx_next = b1["dh0"], b1["dc0"], b1["dx"]
+        if fused_bwd:        # ONE launch on the same tapes
+            b = ops.selffed2_decoder_bwd({"C1": C1, "C2": C2, "XY": XY, "RES1": R1, "RES2": R2}, dloss_tm, w, W_h, act=act, need_dx0=False)
+            DPRE, DZ1, DZ2 = b["DPRE"], b["DZ1"], b["DZ2"]
+            dh1, dc1, dh2, dc2 = b["dh1_0"], b["dc1_0"], b["dh2_0"], b["dc2_0"]
+        else:
+            DY, DPRE, DZ1, DZ2 = e(T_out, B, O), e(T_out, B, O), e(T_out, B, 4 * H), e(T_out, B, 4 * H)
+            for t in range(T_out - 1, -1, -1):
+                if dx_next is None:
+                    DY[t].copy_(dloss_tm[t])
+                else:
+                    ops.act_bwd(dx_next.reshape(B, O), XY[t + 1], base=dloss_tm[t], activation=None, out=DY[t])
+                ops.act_bwd(DY[t], XY[t + 1], activation="tanh", out=DPRE[t])
+                dh2_dense, _, _ = ops.dense_bwd(H2[t + 1], W_h, DPRE[t], need_dx=True, need_dW=False, need_db=False, scratch=sc)
+                b2 = ops.lstm_seq_bwd(H1[t + 1].view(B, 1, H), w["dec2_K"], w["dec2_R"], H2[t + 1].view(B, 1, H), R2[t], h0=H2[t],
+                                      c0=C2[t], dhs=dh2_dense.reshape(B, 1, H), dhT=dh2, dcT=dc2, need_dx=True, need_state_grads=True,
+                                      act=act, dz=DZ2[t].view(B, 1, 4 * H), scratch=bsc, need_weight_grads=False)
+                dh2, dc2 = b2["dh0"], b2["dc0"]
+                b1 = ops.lstm_seq_bwd(XY[t].view(B, 1, O), w["dec1_K"], w["dec1_R"], H1[t + 1].view(B, 1, H), R1[t], h0=H1[t],
+                                      c0=C1[t], dhs=b2["dx"], dhT=dh1, dcT=dc1, need_dx=(t > 0), need_state_grads=True, act=act,
+                                      dz=DZ1[t].view(B, 1, 4 * H), scratch=bsc, need_weight_grads=False)
+                dh1, dc1, dx_next = b1["dh0"], b1["dc0"], b1["dx"]
         TB = T_out * B
         fl = lambda a, n: a.reshape(TB, n)
         ops.dense_bwd(fl(H2[1:], H), W_h, fl(DPRE, O), dW=gW_h, db=g["dense_b"], need_dx=False, accumulate=True, scratch=sc)
