@@ -25,6 +25,21 @@
  *   - Weight gradients over an empty batch or sequence (B = 0, T = 0, no rows): accumulate = 0 writes zeros
  *     (the gradient of an empty sum), accumulate != 0 leaves the output unchanged.  Every weight-gradient entry
  *     point keeps this rule (a data-parallel rank with an empty shard contributes zero, not a stale gradient).
+ *   - Arguments are checked on the host: the refusals this header names - a NULL required pointer, a size, stride or
+ *     enumeration out of range, an unsupported shape, a short workspace - come before the call's first HIP call, so
+ *     such a call has enqueued and written nothing.  (An entry point made of several launches can still fail in a
+ *     later one - a kernel attribute the runtime refuses, an inner product's own limit - after the earlier ones were
+ *     enqueued; fov_seq2seq_tf_fwd names its case.)  A required pointer that is
+ *     NULL, a negative size, a negative stride or a value outside an enumeration (act, impl, activation, ...) is
+ *     FOV_ERR_INVALID; a width of zero is refused, an empty batch / sequence / row count is FOV_OK (a weight-gradient
+ *     entry point still zeroes its outputs, see above).  A workspace that is NULL or smaller than its size function
+ *     answers is FOV_ERR_WORKSPACE, and so is one whose base is not 16-byte aligned.
+ *   - The persistent kernels tag every step with a 32-bit epoch and count a launch's span of them in an int.
+ *     fov_lstm_seq_fwd (_train, _zx, _bf16), fov_lstm_seq_bwd(_bf16), fov_seq2seq_decode_fwd (_packed, _bf16),
+ *     fov_seq2seq_decoder_fwd, fov_seq2seq_tf_fwd and fov_mix_decoder_fwd / _bwd (_bf16) therefore refuse, whichever
+ *     kernel the call would reach, (steps + 2) * ceil(B / 8) > 2^30 (steps = T, T_out, or T_in + T_out of the fused
+ *     calls; the longer of the two for fov_seq2seq_tf_fwd): FOV_ERR_UNSUPPORTED.  (The fov_lstm_stack2_* calls are
+ *     bounded by their granule area, see their predicates; the fov_lstm_seq_wgrad* calls exchange nothing.)
  *   - Every function returns FOV_OK (0) or a negative FOV_ERR_*; fov_last_error() gives the
  *     message of the calling thread's last failure.  No host synchronisation inside a call
  *     (except fov_check_status, which is the explicit "did the persistent kernel finish
@@ -66,7 +81,7 @@ typedef void* fov_stream_t; /* hipStream_t */
  * hard_sigmoid = clip(0.2x+0.5,0,1); BASELINE.json:north_star names sigmoid. */
 enum { FOV_ACT_SIGMOID = 0, FOV_ACT_HARD_SIGMOID = 1 };
 
-/* kernel family selection */
+/* kernel family selection; any other value of `impl` is FOV_ERR_INVALID */
 enum {
     FOV_IMPL_AUTO = 0,    /* cluster kernel when the shape is supported, else generic        */
     FOV_IMPL_GENERIC = 1, /* one workgroup per 4 sequences, weights streamed from L2; any H,F */
@@ -94,6 +109,7 @@ int fov_cluster_supported(int F, int H);
  *   replaces: mycode/FoV_seq2seq.py:83-86 (encoder), :93-95 (teacher-forced decoder),
  *             mycode/given_others_gt_mean_var_seq2seq.py:108-112.
  *   x:(B,T,F)  h0,c0:(B,H) or NULL (= zeros)  hs:(B,T,H) or NULL  hT,cT:(B,H) or NULL
+ *   B = 0: nothing is launched; T = 0: hT, cT receive the initial state.
  * ------------------------------------------------------------------------------------- */
 size_t fov_lstm_seq_workspace_bytes(int B, int T, int F, int H, int impl);
 int fov_lstm_seq_fwd(const float* x, const float* K, const float* R, const float* b,
@@ -104,7 +120,8 @@ int fov_lstm_seq_fwd(const float* x, const float* K, const float* R, const float
 /* ---------------------------------------------------------------------------------------
  * keras.layers.Dense(Out, activation)(x)   y = act(x W + b), W:(In,Out)
  *   replaces: mycode/FoV_seq2seq.py:96-97; given_others...py:127-130,168.
- *   activation: 0 = linear, 1 = tanh.   x:(N,In)  y:(N,Out)
+ *   activation: 0 = linear, 1 = tanh.   x:(N,In)  y:(N,Out); b may be NULL (no bias).
+ *   In, Out <= 2^24 (also for fov_dense_add_fwd), else FOV_ERR_INVALID.
  * ------------------------------------------------------------------------------------- */
 int fov_dense_fwd(const float* x, const float* W, const float* b, float* y,
                   int N, int In, int Out, int activation, fov_stream_t stream);
@@ -112,14 +129,16 @@ int fov_dense_fwd(const float* x, const float* W, const float* b, float* y,
 /* y = act(x W + b + add[row*add_row_stride + :]) - Dense with an additive per-row term, used to fold the
  * precomputed "others" part of the mixing layer into the decoder step:
  *   replaces: Concatenate(axis=1)([others_t, pred]) -> Flatten -> Dense(6,'tanh')
- *             (mycode/given_others_gt_mean_var_seq2seq.py:257-265), with W = mix_W[-6:], add = others_t . mix_W[:-6]. */
+ *             (mycode/given_others_gt_mean_var_seq2seq.py:257-265), with W = mix_W[-6:], add = others_t . mix_W[:-6].
+ * add_row_stride >= 0 floats (0 broadcasts one row); b may be NULL. */
 int fov_dense_add_fwd(const float* x, const float* W, const float* b, const float* add, int64_t add_row_stride,
                       float* y, int N, int In, int Out, int activation, fov_stream_t stream);
 
 /* One decoder step of the others-mixing head in ONE launch (given_others...py:127-130,168,257-265):
  *   p (N,O) = tanh(h dense_W + dense_b);   m (N,O) = tanh(p mix_Wp + add[row*add_row_stride + :])
  * with mix_Wp = mix_W[-O:] (O x O) and add = others_t . mix_W[:-O] + mix_b (fov_dense_fwd, hoisted out of the loop).
- * O <= 8, H % 4 == 0.  Backward of the same step: dm_loss = dL/d(pre-tanh of m) from the loss, dm_feedback =
+ * O <= 8, H % 4 == 0, H <= 2048, h 16-byte aligned, add_row_stride >= 0 (the forward; anything else is FOV_ERR_INVALID).
+ * Backward of the same step: dm_loss = dL/d(pre-tanh of m) from the loss, dm_feedback =
  * dL/dm arriving through x_{t+1} = m_t (NULL at the last step); writes dpre_m, dpre_p (N,O: the pre-activation
  * gradients the weight-gradient products need) and dh (N,H) = dL/dh.  Outputs must not alias inputs. */
 int fov_mix_head_fwd(const float* h, const float* dense_W, const float* dense_b, const float* mix_Wp, const float* add,
@@ -143,7 +162,7 @@ int fov_mix_head_wgrad(const float* h2, const float* dpre_p, const float* others
  * (given_others...py:203-299): per step LSTM1(x_t) -> LSTM2 -> Dense(O,'tanh') -> mixing Dense -> x_{t+1}.
  *   dec0 (B,O); h1,c1,h2,c2 (B,H) = encoder states; oth_proj: others_t . mix_W[:-O] + mix_b, element (b,t,o) at
  *   b*oth_batch_stride + t*oth_step_stride + o; weights in Keras layout; mix_Wp = mix_W[-O:] (O,O).
- *   out (T_out,B,O) step-major = m_t.  h1T..c2T (B,H): final states or NULL.
+ *   (both strides >= 0).  out (T_out,B,O) step-major = m_t.  h1T..c2T (B,H): final states or NULL.
  *   Training buffers (all or none): P (T_out,B,O) = p_t; H1,C1,H2,C2 (T_out,B,H) = states after step t;
  *   res1,res2 (T_out,B,5,H) = activated i,f,g,o and c (the reserve layout of fov_lstm_seq_fwd_train with T = 1).
  * Supported: H = 256, O <= 8 (FOV_ERR_UNSUPPORTED otherwise: use the per-step entry points). */
@@ -215,7 +234,10 @@ int fov_dense_bwd_bf16(const float* x, const float* W, const float* dpre, float*
  * gradients; dz1, dz2 (B,T,4H) out; dK / dR / db of either layer optional (NULL: data path only); dh0 / dc0 optional.  The
  * gradient with respect to x is NOT produced (lstm.py's first layer needs none).  Results equal the two-call path's up to the
  * summation order of dx (sixteen partial sums added in slice order instead of a split GEMM's reduce).
- * Shapes: fov_lstm_stack2_bwd_supported (H = 512, at most 32 sequences on 256 CUs).  workspace: stateful like every exchange
+ * Shapes: fov_lstm_stack2_bwd_supported (H = 512, at most 32 sequences on 256 CUs).  The width is decided first: H != 512 is
+ * FOV_ERR_UNSUPPORTED whatever B and T are.  At H = 512 an empty call (B = 0 or T = 0) is taken - it zeroes the weight gradients
+ * (accumulate = 0) and, at T = 0, passes dhT / dcT through to dh0 / dc0 - although the predicate answers 0 for it (there is
+ * nothing to fuse).  workspace: stateful like every exchange
  * workspace (zero-filled once), fov_lstm_stack2_bwd_workspace_bytes. */
 int fov_lstm_stack2_bwd_supported(int B, int T, int F, int H);
 size_t fov_lstm_stack2_bwd_workspace_bytes(int B, int T, int F, int H);
@@ -323,7 +345,8 @@ int fov_dense_fwd_bf16(const float* x, const float* W, const float* b, float* y,
  * hands it over in tagged mailboxes, layer 2 keeps R2 only; every 32-workgroup group runs on an XCD of its own.  Same results
  * as two fov_lstm_seq_fwd[_train] calls: bit-identical for layer 1 and for the two-role form (33..64 sequences,
  * FOV_NO_WIDE16_TRIO=1), up to the order of layer 2's fp32 sums (2e-5 relative) in the three-role form.  h0_* / c0_* (B,H) or
- * NULL; reserve* (B,T,5,H) or NULL (training tape); hs1 may be NULL when only the top layer's sequence is wanted.
+ * NULL; reserve* (B,T,5,H) or NULL (training tape); hs1 may be NULL when only the top layer's sequence is wanted; hs2, hT*
+ * and cT* may be NULL.
  * Shapes: fov_lstm_stack2_supported (H = 512, F <= 96, T >= 2, both layers' groups resident: <= 64 sequences on 256 CUs);
  * workspace >= fov_lstm_seq_workspace_bytes of a width-512 layer (header + granule area). */
 int fov_lstm_stack2_supported(int B, int T, int F, int H);
@@ -360,7 +383,8 @@ size_t fov_mix_decoder_bwd_workspace_bytes(int B, int H);
  * workspaces; the NEXT fov_mix_decoder_fwd / _bwd on a marked workspace with the same dec2_K skips its own pack.  The caller
  * orders the streams (the launch must come behind the pack).  The mark is valid for that one launch and only while dec2_K's
  * CONTENTS are unchanged (it is keyed by pointer: a caller that updates the weights in place packs again); fov_workspace_init and
- * the reset inside fov_check_status erase it, since they zero the packed copy. */
+ * the reset inside fov_check_status erase it, since they zero the packed copy.  H = 256 (another H: FOV_ERR_INVALID); both
+ * workspaces are checked against their size functions before the first pack is launched. */
 int fov_mix_decoder_prepack(const float* dec2_K, void* workspace_fwd, size_t fwd_bytes, void* workspace_bwd, size_t bwd_bytes,
                             int H, fov_stream_t stream);
 int fov_mix_decoder_bwd(const float* M, const float* P, const float* dloss, const float* res1, const float* res2,
@@ -393,7 +417,8 @@ int fov_lstm_seq_fwd_zx(const float* zx, const float* R, const float* b, const f
  *   replaces: the host loop mycode/FoV_seq2seq.py:154-178 over encoder_model / decoder_model
  *             (:137-148), batched.
  *   enc_in:(B,T_in,F_enc)  dec_in0:(B,1,F_dec)  out:(B,T_out,F_dec)
- *   hT,cT: final decoder state (B,H) or NULL.
+ *   hT,cT: final decoder state (B,H) or NULL.   F_dec <= 64 (wider: FOV_ERR_UNSUPPORTED).
+ *   B = 0: nothing is launched.
  * ------------------------------------------------------------------------------------- */
 size_t fov_seq2seq_decode_workspace_bytes(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int impl);
 int fov_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0,
@@ -417,7 +442,7 @@ int fov_lstm_pack_r(const float* R, int H, float* out, fov_stream_t stream);
  * bit for bit: the packs only change how the one-launch form of the call (H in {64, 128, 256}, one 16-sequence tile per
  * group of workgroups) loads its recurrent weights, and that form uses them when BOTH are given.  Every other form of the
  * call reads enc_R / dec_R, which must be valid either way.  The caller keeps a pack in step with its R: after R changes
- * the pack is made again (or NULL is passed). */
+ * the pack is made again (or NULL is passed).  A pack that is not 16-byte aligned is FOV_ERR_INVALID. */
 int fov_seq2seq_decode_fwd_packed(const float* enc_in, const float* dec_in0,
                                   const float* enc_K, const float* enc_R, const float* enc_b,
                                   const float* dec_K, const float* dec_R, const float* dec_b,
@@ -450,7 +475,7 @@ int fov_seq2seq_decoder_fwd(const float* dec_in0, const float* h0, const float* 
  * One workgroup owns a 16-sequence tile for all layers and steps, so the call takes NO workspace, keeps NO library state, waits
  * on nothing, and writes every element of `out` exactly once (rows of a ragged last tile beyond B are neither read nor written).
  * Shapes: H = 32 or 64 (a narrower model zero-padded by the caller, which is exact), L = 2 or 3, 1 <= F_enc <= 96,
- * 1 <= F_dec <= 8, any B, T_in, T_out >= 0; anything else: FOV_ERR_UNSUPPORTED before any HIP call.
+ * 1 <= F_dec <= 8, 0 <= B, T_in, T_out <= 2^30; anything else: FOV_ERR_UNSUPPORTED before any HIP call.
  * fov_stacked_seq2seq_decode_supported is that rule as arithmetic (no device query), and 0 under FOV_NO_STACKED_DECODE=1
  * (the caller's host loop stays: A/B timing, cross-check); the _fwd entry itself does not read the knob. */
 int fov_stacked_seq2seq_decode_supported(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L);
@@ -487,7 +512,7 @@ int fov_stacked_seq2seq_decode_fwd(const float* enc_in, const float* dec_in0,
  * a_t is read from A when a_from_A != 0, else from XA[1:].  Outputs: DY, DPRE (T,B,O), DZ (T,B,4H), dx0 (B,O), and dh0, dc0
  * (B,H; either may be NULL).  The weight gradients are products over all steps of these tapes (fov_dense_bwd).
  *
- * Shapes: H = 32 or 64, 1 <= O <= 8, B >= 0, T >= 0; anything else is FOV_ERR_UNSUPPORTED, decided before any HIP call.  A
+ * Shapes: H = 32 or 64, 1 <= O <= 8, 0 <= B, T <= 2^30; anything else is FOV_ERR_UNSUPPORTED, decided before any HIP call.  A
  * missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 or T = 0 launches nothing: the forward then
  * writes nothing (no tape row 0 either); the backward, which takes no gradient of the final state, sets dx0, dh0 and dc0 to
  * zero with T = 0.  fov_selffed_decoder_supported is the shape rule as arithmetic (no device query), and 0 under
@@ -533,7 +558,7 @@ int fov_selffed_decoder_bwd(const float* Cs, const float* XA, const float* A, co
  * = not written).  The final states carry no incoming gradient.  The weight gradients are products over all steps of these
  * tapes (fov_dense_bwd); the gradient of ctx is DPRE.
  *
- * Shapes: 1 <= O <= 8, B >= 0, T >= 0; H = 32 or 64 for the forward, H = 32 for the backward (R2^T, K2^T and R1^T stay in LDS:
+ * Shapes: 1 <= O <= 8, 0 <= B, T <= 2^30; H = 32 or 64 for the forward, H = 32 for the backward (R2^T, K2^T and R1^T stay in LDS:
  * 48 KB at H = 32, 192 KB at H = 64, more than a CU has).  Anything else is FOV_ERR_UNSUPPORTED, decided before any pointer is
  * looked at and before any HIP call.  A missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 or T = 0
  * launches nothing: the forward then writes nothing (no tape row 0 either); the backward sets dx0 and the four state gradients
@@ -582,7 +607,7 @@ int fov_selffed2_decoder_bwd(const float* C1, const float* C2, const float* XY, 
  * bytes of plain memory (the dx hand-off between layers), nothing is kept in it between calls.
  *
  * Shapes: H = 32 or 64 (a narrower model zero-padded by the caller, which is exact), L = 2 or 3, 1 <= F_enc <= 96,
- * 1 <= F_dec <= 8, any B, T_in, T_out >= 0; anything else is FOV_ERR_UNSUPPORTED, decided before any pointer is looked at and
+ * 1 <= F_dec <= 8, 0 <= B, T_in, T_out <= 2^30; anything else is FOV_ERR_UNSUPPORTED, decided before any pointer is looked at and
  * before any HIP call.  A missing required pointer or an unknown activation is FOV_ERR_INVALID.  B = 0 launches nothing.
  * fov_stacked_seq2seq_train_supported is the shape rule as arithmetic (no device query), and 0 under FOV_NO_STACKED_TRAIN=1 (the
  * caller's per-layer path stays: A/B timing, cross-check); the two entries do not read the knob. */
@@ -607,6 +632,10 @@ int fov_stacked_seq2seq_train_bwd(const float* enc_res, const float* dec_res, co
  *             mycode/FoV_seq2seq.py:82-101.
  *   dec_in:(B,T_out,F_dec)  out:(B,T_out,F_dec)
  *   workspace additionally holds the decoder hidden sequence (B,T_out,H).
+ *   dense_b may be NULL.  The call is three launches in a row (encoder, decoder, head): every pointer, act and impl
+ *   of all three are checked before the first one; only a shape that the requested impl does not have for the
+ *   decoder layer is refused by the second call, after the encoder has been enqueued.
+ *   B * T_out <= 2^31 - 1 (the head's row count), else FOV_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------------------- */
 size_t fov_seq2seq_tf_workspace_bytes(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int impl);
 int fov_seq2seq_tf_fwd(const float* enc_in, const float* dec_in,
@@ -623,7 +652,7 @@ int fov_seq2seq_tf_fwd(const float* enc_in, const float* dec_in,
  * (population variance, ddof = 0).
  *   replaces: mycode/utility.py:483-500 (get_gt_target_xyz) and :505-517 (_oth); the (N,T,90)
  *   and (N,T,30,3) layouts are the same bytes, so `rows` = N*T (or N*T*U for others).
- *   y:(rows, 3*fps)  out:(rows, 6)
+ *   y:(rows, 3*fps)  out:(rows, 6);  1 <= fps <= 2^20, else FOV_ERR_INVALID.
  * ------------------------------------------------------------------------------------- */
 int fov_meanvar_xyz(const float* y, float* out, int64_t rows, int fps, fov_stream_t stream);
 
@@ -678,7 +707,7 @@ int fov_mse_dense_grad_w(const float* y, const float* target, float* dpre, float
 /* fov_mse_dense_grad_w (batch-major) that also leaves the Dense head's BIAS gradient: db[o] = sum over the n / O rows of
  * dpre[row][o] (written, not added) - the `db` half of fov_dense_bwd (keras Dense(O) behind mean_squared_error,
  * mycode/FoV_seq2seq.py:96-101,267) from the launch that forms dpre; widths O <= 8 inside the kernel, wider heads by a column-sum
- * launch.  Pass db = NULL to fov_dense_bwd afterwards. */
+ * launch.  Pass db = NULL to fov_dense_bwd afterwards.  n is a multiple of O; workspace >= 4*(9*((n+255)/256) + 64 + 256*O) bytes. */
 int fov_mse_dense_grad_db(const float* y, const float* target, float* dpre, float* loss, float* db, int64_t n, int O, int activation,
                           float weight, void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
@@ -709,6 +738,7 @@ int fov_act_bwd(const float* dy, const float* y, const float* base, float* out, 
  *   fov_gauss_nll_grad: likelihood_loss_tf - mu, var (B,3); y (B,T_y,3*fps) interleaved x,y,z; per element
  *     l = log(var + 1e-20) + (y - mu)^2 / (var + 1e-20) clipped to [-10,10]; *loss = scale * mean_b sum l (scale =
  *     1/(running_length*fps) under cfg.process_in_seconds); dmu, dvar (B,3).  workspace >= 4*(B + 64) bytes.
+ *     B <= 2^29 and 3 T_y fps <= 2^31 - 1, else FOV_ERR_INVALID.
  *   fov_rmsprop_tf_step: tf.train.RMSPropOptimizer (momentum 0): g' = clip_by_value(g, -clip, clip) if clip > 0;
  *     ms = decay*ms + (1-decay) g'^2; p -= lr * g' / sqrt(ms + eps)   (TF initialises ms to ONE, eps = 1e-10). */
 int fov_act_fwd(const float* x, float* y, int64_t n, int activation, fov_stream_t stream);
@@ -764,7 +794,7 @@ int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* 
  * (x, y, z interleaved) per row, rows ldy floats apart (cfg.process_in_seconds: second 0 of y (B,T_y,3 fps), ldy = T_y * 3 fps, n_pts =
  * fps; per frame: y (B,T,3), n_pts = T).  Per (row, mixture): covariance [[s1^2, r12 s1 s2, r13 s1 s3], ...], repaired as
  * cost.py:335-348 (smallest eigenvalue lambda < 0: Sigma - 10 lambda I), density N(y_t; mu_m, Sigma'_m);
- *   *loss = scale * sum_{b,t} -log(sum_m [pi_m] N_bmt + 1e-20)      (scale = 1 / (batch_size * running_length [* fps]), cost.py:544-549)
+ *   *loss (may be NULL: gradient only) = scale * sum_{b,t} -log(sum_m [pi_m] N_bmt + 1e-20)      (scale = 1 / (batch_size * running_length [* fps]), cost.py:544-549)
  * weight_by_pi = 0 is the reference: cost.py:532-538 never multiplies by mixture_pi, so the softmax weights get no gradient.
  * dpre (B, 10 n_mix) = d loss / d the head's PRE-activations (through softmax / exp / tanh and the eigenvalue repair).  The 3x3
  * work runs in fp64.  n_mix <= 32, n_pts <= 256.  workspace >= 256 + 4 * B bytes, STATEFUL like the exchange workspaces: its first
@@ -799,7 +829,8 @@ int fov_xyz_sum1_grad(const float* p, float* dp, float* reg, int64_t n_pix, int 
  * and has the layout of x.  std_mode 0: sd = sqrt(var) (lstm.py), 1: sd = var (lstm_keras.py hands the variance to
  * `stddev`).  layout 0: a(e) = e % 3, frames interleaved x,y,z; 1: a(e) = e / fps, planar.  Rows of x / dx are ldx floats
  * apart, so a slot of the (B,T,3*fps) window is written / read in place.  Backward (reparameterisation, what TF
- * differentiates): dmu[b,a] = sum_e dx, dvar[b,a] = sum_e dx * noise * sd'(var); accumulate != 0 adds into dmu / dvar. */
+ * differentiates): dmu[b,a] = sum_e dx, dvar[b,a] = sum_e dx * noise * sd'(var); accumulate != 0 adds into dmu / dvar.
+ * B <= 2^29, fps <= 2^20 and ldx >= 3 fps, else FOV_ERR_INVALID. */
 int fov_sample_refeed_fwd(const float* mu, const float* var, const float* noise, float* x, int64_t ldx, int B, int fps,
                           int std_mode, int layout, fov_stream_t stream);
 int fov_sample_refeed_bwd(const float* dx, int64_t ldx, const float* var, const float* noise, float* dmu, float* dvar,
@@ -839,14 +870,16 @@ int fov_rmsprop_step_guarded(float* params, const float* grads, float* accum, in
  * arenas and pending records are separate - so several may be open at once from different threads (at most 16 per process;
  * _begin on a buffer that overlaps an open region flushes and replaces that region).  The library holds the record table of
  * an open region (16 records, host memory) until _end; it allocates no device memory.  _flush / _end with grad_base = NULL
- * address every open region of the process; _begin with arena = NULL only closes what overlaps grad_base. */
+ * address every open region of the process; _begin with grad_base = NULL opens nothing (FOV_OK), a grad_base without an arena
+ * of at least 256 bytes is FOV_ERR_INVALID, a 17th open region FOV_ERR_UNSUPPORTED. */
 int fov_reduce_defer_begin(float* grad_base, size_t grad_floats, void* arena, size_t arena_bytes, fov_stream_t stream);
 int fov_reduce_defer_flush(const float* grad_base, fov_stream_t stream);
 int fov_reduce_defer_end(const float* grad_base, fov_stream_t stream);
 /* Data-parallel training (the all-reduce of model.fit's gradients, given_others_gt_mean_var_seq2seq.py:494-506):
  * *out = 1.0f if the timeout word of one of the workspaces is set, else 0.0f.  The trainers keep `out` inside the flat
  * gradient buffer: after the SUM all-reduce it is nonzero on EVERY rank if any rank's step failed, and handed to the
- * guarded optimizer as its guard (a nonzero float is a nonzero word) all replicas skip the update together. */
+ * guarded optimizer as its guard (a nonzero float is a nonzero word) all replicas skip the update together.  guard0..2: each
+ * may be NULL, as for the optimizers. */
 int fov_guard_flag(const void* guard0, const void* guard1, const void* guard2, float* out, fov_stream_t stream);
 
 /* =======================================================================================
@@ -957,7 +990,10 @@ int fov_convlstm_gates_bwd(const float* dh, int64_t dh_pixel_stride, float* dc, 
 
 /* Weight gradient of y = conv2d_same(x, w): dw (kh,kw,C,N) (+)= sum over the B*H*W pixels of
  * x[pixel + tap][c] * dy[pixel][n].  x: batch-dense NHWC with pixel stride x_pixel_stride >= C; dy (B*H*W, N).
- * workspace >= fov_conv2d_wgrad_workspace_bytes (split-K partials; deterministic fixed-order reduce). */
+ * workspace >= fov_conv2d_wgrad_workspace_bytes (split-K partials; deterministic fixed-order reduce).  With accumulate = 0,
+ * without a workspace (NULL) or with a smaller one the product is split less or not at all; accumulate != 0 forms the product
+ * in the workspace and needs kh*kw*C*N floats of it (FOV_ERR_WORKSPACE otherwise).  dw of 2 GiB or more (kh*kw*C*N >= 2^29):
+ * FOV_ERR_UNSUPPORTED, also for fov_conv2d_dilated_wgrad. */
 size_t fov_conv2d_wgrad_workspace_bytes(int C, int N, int kh, int kw);
 int fov_conv2d_wgrad(const float* x, int64_t x_pixel_stride, const float* dy, float* dw, int B, int H, int W,
                      int C, int N, int kh, int kw, int accumulate, void* workspace, size_t workspace_bytes,
@@ -1007,7 +1043,8 @@ int fov_conv2d_weight_transpose(const float* w, float* wt, int kh, int kw, int C
 /* Backward of fov_softmax_lastdim given its output p: dy = p * (dp - sum_c dp*p); dy may alias dp. */
 int fov_softmax_lastdim_bwd(const float* dp, const float* p, float* dy, int64_t rows, int n, fov_stream_t stream);
 
-/* out (cols) (+)= column sums of x (rows, cols): bias gradients.  workspace >= 4*(256*cols + 64) bytes. */
+/* out (cols) (+)= column sums of x (rows, cols): bias gradients.  workspace >= 4*(256*cols + 64) bytes.  1 <= cols <= 2^24,
+ * else FOV_ERR_INVALID. */
 int fov_colsum(const float* x, float* out, int64_t rows, int cols, int accumulate, void* workspace,
                size_t workspace_bytes, fov_stream_t stream);
 
@@ -1099,7 +1136,8 @@ int fov_heatmap_index_xyz(const int* index, float* xyz, int64_t n, int* status, 
  * floats; its C channels are contiguous, row_stride >= C (a 30-of-32-channel view works as it lies), outer strides >= 0.
  * A time-major prediction (T, B, H*W, C) meets a batch-major target (B, T, H*W, C) by swapping s0 and s1, not by a copy.
  * *matches (device memory, 8-byte aligned) receives the number of matching rows, or has it added when accumulate != 0; an
- * empty shape writes 0 or leaves it alone.  The count is an exact integer, the same in every run (integer atomics only).
+ * empty shape writes 0 or leaves it alone (and looks at neither operand).  Every refusal - a NULL or misaligned matches, a NULL
+ * operand, a stride below its bound - comes before the count is cleared: a refused call leaves *matches as it was.  The count is an exact integer, the same in every run (integer atomics only).
  * C > 1: a row matches when both arg-maxes agree; arg-max takes the lowest index among equal maxima (-0.0 == +0.0) and
  * the first NaN of a row as its maximum (np.argmax, the rule of fov_heatmap_argmax; TensorFlow leaves both unspecified).
  * C == 1: an element matches when target == rint(pred), half to even (0.5 -> 0, 1.5 -> 2); a NaN matches nothing.

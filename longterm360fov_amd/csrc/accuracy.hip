@@ -228,8 +228,8 @@ extern "C" {
 int fov_categorical_accuracy(const float* pred, int64_t pred_s0, int64_t pred_s1, int64_t pred_row_stride,
                              const float* target, int64_t tgt_s0, int64_t tgt_s1, int64_t tgt_row_stride,
                              int64_t n0, int64_t n1, int64_t rows, int C, int64_t* matches, int accumulate, fov_stream_t stream) {
-    if (C < 1 || n0 < 0 || n1 < 0 || rows < 0 || !matches) {
-        set_error("fov_categorical_accuracy: invalid argument (C >= 1, n0, n1, rows >= 0, matches not NULL)");
+    if (C < 1 || n0 < 0 || n1 < 0 || rows < 0 || !matches || (((uintptr_t)matches) & 7)) {
+        set_error("fov_categorical_accuracy: invalid argument (C >= 1, n0, n1, rows >= 0, matches not NULL and 8-byte aligned)");
         return FOV_ERR_INVALID;
     }
     long total = 0;
@@ -237,15 +237,17 @@ int fov_categorical_accuracy(const float* pred, int64_t pred_s0, int64_t pred_s1
         set_error("fov_categorical_accuracy: more than 2^40 rows");
         return FOV_ERR_INVALID;
     }
+    // every refusal comes before the count is touched: a refused call leaves *matches as it was
+    if (total > 0 &&
+        (!acc_operand_ok(pred, pred_s0, pred_s1, pred_row_stride, C) || !acc_operand_ok(target, tgt_s0, tgt_s1, tgt_row_stride, C))) {
+        set_error("fov_categorical_accuracy: invalid operand (not NULL, outer strides >= 0, row_stride >= C)");
+        return FOV_ERR_INVALID;
+    }
     if (!accumulate) {
         const hipError_t e = hipMemsetAsync(matches, 0, sizeof(int64_t), (hipStream_t)stream);
         if (e != hipSuccess) { set_error("fov_categorical_accuracy: zeroing the count: %s", hipGetErrorString(e)); return FOV_ERR_LAUNCH; }
     }
     if (total == 0) return FOV_OK;
-    if (!acc_operand_ok(pred, pred_s0, pred_s1, pred_row_stride, C) || !acc_operand_ok(target, tgt_s0, tgt_s1, tgt_row_stride, C)) {
-        set_error("fov_categorical_accuracy: invalid operand (not NULL, outer strides >= 0, row_stride >= C)");
-        return FOV_ERR_INVALID;
-    }
     AccParams p;
     p.pred = {pred, (long)pred_s0, (long)pred_s1, (long)pred_row_stride};
     p.tgt = {target, (long)tgt_s0, (long)tgt_s1, (long)tgt_row_stride};

@@ -4,6 +4,16 @@
 
 using namespace fov;
 
+// a (kh,kw,C,N) fp32 kernel of 2 GiB or more: the weight-gradient launchers count its tiles and taps in ints
+static bool weights_over_2g(int kh, int kw, int C, int N) {
+    const long lim = 1L << 29;
+    long t = (long)kh * kw;
+    if (t >= lim) return true;
+    t *= C;
+    if (t >= lim) return true;
+    return t * N >= lim;
+}
+
 extern "C" {
 
 int fov_conv2d_fwd(const float* x, int64_t x_pixel_stride, int64_t x_batch_stride, const float* w, const float* b,
@@ -186,6 +196,7 @@ int fov_conv2d_wgrad(const float* x, int64_t x_pixel_stride, const float* dy, fl
         set_error("fov_conv2d_wgrad: invalid argument (odd kernel sizes only)");
         return FOV_ERR_INVALID;
     }
+    if (weights_over_2g(kh, kw, C, N)) { set_error("fov_conv2d_wgrad: dw of 2 GiB or more"); return FOV_ERR_UNSUPPORTED; }
     if (workspace && (((uintptr_t)workspace) & 15)) { set_error("workspace must be 16-byte aligned"); return FOV_ERR_WORKSPACE; }
     return conv2d_wgrad(x, (long)x_pixel_stride, dy, dw, B, H, W, C, N, kh, kw, accumulate, (float*)workspace,
                         workspace ? workspace_bytes / sizeof(float) : 0, (hipStream_t)stream);
@@ -216,6 +227,7 @@ int fov_conv2d_dilated_wgrad(const float* x, int64_t x_pixel_stride, const float
         set_error("fov_conv2d_dilated_wgrad: invalid argument (odd kernel sizes only, dilation >= 1)");
         return FOV_ERR_INVALID;
     }
+    if (weights_over_2g(kh, kw, C, N)) { set_error("fov_conv2d_dilated_wgrad: dw of 2 GiB or more"); return FOV_ERR_UNSUPPORTED; }
     if (workspace && (((uintptr_t)workspace) & 15)) { set_error("workspace must be 16-byte aligned"); return FOV_ERR_WORKSPACE; }
     return conv2d_wgrad(x, (long)x_pixel_stride, dy, dw, B, H, W, C, N, kh, kw, accumulate, (float*)workspace,
                         workspace ? workspace_bytes / sizeof(float) : 0, (hipStream_t)stream, dilation);

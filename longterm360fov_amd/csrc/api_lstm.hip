@@ -13,6 +13,15 @@ static bool want_cluster(int impl, int F, int H, int F_dec, bool decode) {
     return impl == FOV_IMPL_CLUSTER ? true : ok;
 }
 
+// The persistent kernels tag every exchange step with a 32-bit epoch and count a launch's span of them in an int: steps times
+// the tile rounds a group may make (at most one per 8-row tile) must stay far below 2^31.  Decided here, as arithmetic, for
+// every LSTM entry point alike - whichever kernel the call would reach.
+static bool steps_ok(const char* who, long steps, int B) {
+    if ((steps + 2) * (((long)B + 7) / 8 > 0 ? ((long)B + 7) / 8 : 1) <= (1L << 30)) return true;
+    set_error("%s: (steps + 2) * ceil(B / 8) exceeds 2^30 (steps = %ld, B = %d)", who, steps, B);
+    return false;
+}
+
 // one layer's parameters (phase 1 of LstmParams) on its workspace
 static LstmParams layer_params(const float* x, const float* K, const float* R, const float* b, const float* h0, const float* c0,
                                float* hs, float* hT, float* cT, float* reserve, int B, int T, int F, int H, int act, void* workspace) {
@@ -149,10 +158,12 @@ size_t fov_lstm_seq_workspace_bytes(int B, int T, int F, int H, int impl) {
 static int lstm_seq_fwd_impl(const float* x, const float* K, const float* R, const float* b, const float* h0,
                              const float* c0, float* hs, float* hT, float* cT, float* reserve, int B, int T, int F,
                              int H, int act, int impl, void* workspace, size_t workspace_bytes, fov_stream_t stream) {
-    if (B < 0 || T < 0 || F <= 0 || H <= 0 || !K || !R || !b || (B > 0 && T > 0 && !x) || !valid_act(act)) {
+    if (B < 0 || T < 0 || F <= 0 || H <= 0 || !K || !R || !b || (B > 0 && T > 0 && !x) || !valid_act(act) ||
+        !valid_impl(impl)) {
         set_error("fov_lstm_seq_fwd: invalid argument");
         return FOV_ERR_INVALID;
     }
+    if (!steps_ok("fov_lstm_seq_fwd", T, B)) return FOV_ERR_UNSUPPORTED;
     LstmParams p = layer_params(x, K, R, b, h0, c0, hs, hT, cT, reserve, B, T, F, H, act, workspace);
     return launch_lstm_fwd(plan_lstm_fwd(B, T, F, H, impl, (((uintptr_t)x) & 15) == 0, false), p, workspace, workspace_bytes,
                            (hipStream_t)stream);
@@ -181,6 +192,7 @@ int fov_lstm_seq_fwd_bf16(const float* x, const float* K, const float* R, const 
         return FOV_ERR_INVALID;
     }
     if (!layer_bf16_shape_ok(F, H)) { set_error("fov_lstm_seq_fwd_bf16: H = 256 and F <= 256 only"); return FOV_ERR_UNSUPPORTED; }
+    if (!steps_ok("fov_lstm_seq_fwd_bf16", T, B)) return FOV_ERR_UNSUPPORTED;
     if (int rc = check_ws(workspace, workspace_bytes, B > 0 ? kStatusBytes + kXchBytes : kStatusBytes)) return rc;
     return launch_layer_bf16(layer_params(x, K, R, b, h0, c0, hs, hT, cT, reserve, B, T, F, H, act, workspace), (hipStream_t)stream);
 }
@@ -200,6 +212,7 @@ int fov_seq2seq_decode_fwd_bf16(const float* enc_in, const float* dec_in0, const
         set_error("fov_seq2seq_decode_fwd_bf16: H = 256, F_enc <= 256 and F_dec <= 8 only (got H=%d F_enc=%d F_dec=%d)", H, F_enc, F_dec);
         return FOV_ERR_UNSUPPORTED;
     }
+    if (!steps_ok("fov_seq2seq_decode_fwd_bf16", (long)T_in + T_out, B)) return FOV_ERR_UNSUPPORTED;
     if (int rc = check_ws(workspace, workspace_bytes, B > 0 ? kStatusBytes + kXchBytes : kStatusBytes)) return rc;
     LstmParams p = {};
     p.x = enc_in; p.K = enc_K; p.R = enc_R; p.b = enc_b; p.T = T_in; p.F = F_enc;
@@ -251,10 +264,11 @@ int fov_lstm_stack2_fwd(const float* x, const float* K1, const float* R1, const 
 int fov_lstm_seq_fwd_zx(const float* zx, const float* R, const float* b, const float* h0, const float* c0, float* hs,
                         float* hT, float* cT, float* reserve, int B, int T, int H, int act, int impl, void* workspace,
                         size_t workspace_bytes, fov_stream_t stream) {
-    if (B < 0 || T < 0 || H <= 0 || !R || !b || (B > 0 && T > 0 && !zx) || !valid_act(act)) {
+    if (B < 0 || T < 0 || H <= 0 || !R || !b || (B > 0 && T > 0 && !zx) || !valid_act(act) || !valid_impl(impl)) {
         set_error("fov_lstm_seq_fwd_zx: invalid argument");
         return FOV_ERR_INVALID;
     }
+    if (!steps_ok("fov_lstm_seq_fwd_zx", T, B)) return FOV_ERR_UNSUPPORTED;
     LstmParams p = layer_params(nullptr, nullptr, R, b, h0, c0, hs, hT, cT, reserve, B, T, 1, H, act, workspace);
     p.zx = zx;
     return launch_lstm_fwd(plan_lstm_fwd(B, T, 1, H, impl, true, true), p, workspace, workspace_bytes, (hipStream_t)stream);
@@ -274,6 +288,7 @@ static int lstm_seq_bwd_entry(const LstmBwdLayer& l, void* workspace, size_t wor
         set_error(l.bf16 ? "fov_lstm_seq_bwd_bf16: invalid argument (H = 256 only)" : "fov_lstm_seq_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
+    if (!steps_ok(l.bf16 ? "fov_lstm_seq_bwd_bf16" : "fov_lstm_seq_bwd", T, B)) return FOV_ERR_UNSUPPORTED;
     if (B == 0) return l.accumulate ? FOV_OK : zero_lstm_wgrads(l.wg.dK, l.wg.dR, l.wg.db, F, H, (hipStream_t)stream);
     if (int rc = check_ws(workspace, workspace_bytes, fov_lstm_seq_bwd_workspace_bytes(B, T, F, H))) return rc;
     return lstm_seq_bwd(l, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
@@ -317,6 +332,8 @@ int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const 
         set_error("fov_lstm_stack2_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
+    // the width rule first, as arithmetic: an empty batch of a width the kernel does not have is refused like a full one
+    if (H != 512) { set_error("fov_lstm_stack2_bwd: H = 512 only (got H=%d)", H); return FOV_ERR_UNSUPPORTED; }
     if (B == 0 || T == 0) {
         hipStream_t s = (hipStream_t)stream;
         int rc = accumulate ? FOV_OK : zero_lstm_wgrads(dK1, dR1, db1, F, H, s);
@@ -359,7 +376,7 @@ static int mix_decoder_fwd_impl(const float* dec0, const float* h1, const float*
                         size_t workspace_bytes, fov_stream_t stream, bool bf16) {
     if (B < 0 || T_out < 0 || O <= 0 || !dec1_K || !dec1_R || !dec1_b || !dec2_K || !dec2_R || !dec2_b || !dense_W ||
         !dense_b || !mix_Wp || (B > 0 && T_out > 0 && (!dec0 || !h1 || !c1 || !h2 || !c2 || !oth_proj || !out)) ||
-        !valid_act(act)) {
+        oth_batch_stride < 0 || oth_step_stride < 0 || !valid_act(act)) {
         set_error("fov_mix_decoder_fwd: invalid argument");
         return FOV_ERR_INVALID;
     }
@@ -367,6 +384,7 @@ static int mix_decoder_fwd_impl(const float* dec0, const float* h1, const float*
                        (res2 != nullptr);
     if (ntrain != 0 && ntrain != 7) { set_error("fov_mix_decoder_fwd: give all training buffers or none"); return FOV_ERR_INVALID; }
     if (H != 256 || O > 8) { set_error("fov_mix_decoder_fwd: the fused decoder supports H = 256, O <= 8"); return FOV_ERR_UNSUPPORTED; }
+    if (!steps_ok("fov_mix_decoder_fwd", T_out, B)) return FOV_ERR_UNSUPPORTED;
     if (B == 0 || T_out == 0) return FOV_OK;
     if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_workspace_bytes(B, H))) return rc;
     MixDecParams p = {};
@@ -421,6 +439,7 @@ static int mix_decoder_bwd_impl(const float* M, const float* P, const float* dlo
         return FOV_ERR_INVALID;
     }
     if (H != 256 || O > 8) { set_error("fov_mix_decoder_bwd: the fused decoder supports H = 256, O <= 8"); return FOV_ERR_UNSUPPORTED; }
+    if (!steps_ok("fov_mix_decoder_bwd", T_out, B)) return FOV_ERR_UNSUPPORTED;
     if (B == 0 || T_out == 0) return FOV_OK;
     if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_bwd_workspace_bytes(B, H))) return rc;
     MixDecBwdParams p = {};
@@ -436,15 +455,14 @@ static int mix_decoder_bwd_impl(const float* M, const float* P, const float* dlo
 int fov_mix_decoder_prepack(const float* dec2_K, void* workspace_fwd, size_t fwd_bytes, void* workspace_bwd, size_t bwd_bytes, int H,
                             fov_stream_t stream) {
     if (!dec2_K || H != 256) { set_error("fov_mix_decoder_prepack: invalid argument (H = 256)"); return FOV_ERR_INVALID; }
+    // both workspaces before the first pack is launched
+    if (workspace_fwd)
+        if (int rc = check_ws(workspace_fwd, fwd_bytes, mix_decoder_workspace_bytes(1))) return rc;
+    if (workspace_bwd)
+        if (int rc = check_ws(workspace_bwd, bwd_bytes, mix_decoder_bwd_workspace_bytes(1))) return rc;
     int rc = FOV_OK;
-    if (workspace_fwd) {
-        rc = check_ws(workspace_fwd, fwd_bytes, mix_decoder_workspace_bytes(1));
-        if (!rc) rc = mix_decoder_prepack(dec2_K, workspace_fwd, (hipStream_t)stream);
-    }
-    if (!rc && workspace_bwd) {
-        rc = check_ws(workspace_bwd, bwd_bytes, mix_decoder_bwd_workspace_bytes(1));
-        if (!rc) rc = mix_decoder_bwd_prepack(dec2_K, workspace_bwd, (hipStream_t)stream);
-    }
+    if (workspace_fwd) rc = mix_decoder_prepack(dec2_K, workspace_fwd, (hipStream_t)stream);
+    if (!rc && workspace_bwd) rc = mix_decoder_bwd_prepack(dec2_K, workspace_bwd, (hipStream_t)stream);
     return rc;
 }
 
@@ -480,7 +498,7 @@ static int seq2seq_decode_fwd_impl(const float* enc_in, const float* dec_in0, co
                                    fov_stream_t stream) {
     if (B < 0 || T_in < 0 || T_out < 0 || F_enc <= 0 || F_dec <= 0 || H <= 0 || !enc_K || !enc_R || !enc_b ||
         !dec_K || !dec_R || !dec_b || !dense_W || !dense_b ||
-        (B > 0 && ((T_in > 0 && !enc_in) || !dec_in0 || (T_out > 0 && !out))) || !valid_act(act)) {
+        (B > 0 && ((T_in > 0 && !enc_in) || !dec_in0 || (T_out > 0 && !out))) || !valid_act(act) || !valid_impl(impl)) {
         set_error("fov_seq2seq_decode_fwd: invalid argument");
         return FOV_ERR_INVALID;
     }
@@ -489,6 +507,7 @@ static int seq2seq_decode_fwd_impl(const float* enc_in, const float* dec_in0, co
         return FOV_ERR_INVALID;
     }
     if (F_dec > 64) { set_error("fov_seq2seq_decode_fwd: F_dec > 64 unsupported"); return FOV_ERR_UNSUPPORTED; }
+    if (!steps_ok("fov_seq2seq_decode_fwd", (long)T_in + T_out, B)) return FOV_ERR_UNSUPPORTED;
     const DecodePlan plan = plan_decode(B, T_out, F_enc, F_dec, H, impl);
     if (int rc = check_ws(workspace, workspace_bytes, plan.need)) return rc;
     LstmParams p = {};
@@ -530,11 +549,12 @@ int fov_seq2seq_decoder_fwd(const float* dec_in0, const float* h0, const float* 
                             float* hT, float* cT, int B, int T_out, int F_dec, int H, int act, int impl, void* workspace,
                             size_t workspace_bytes, fov_stream_t stream) {
     if (B < 0 || T_out < 0 || F_dec <= 0 || H <= 0 || !dec_K || !dec_R || !dec_b || !dense_W || !dense_b ||
-        (B > 0 && (!dec_in0 || (T_out > 0 && !out))) || !valid_act(act)) {
+        (B > 0 && (!dec_in0 || (T_out > 0 && !out))) || !valid_act(act) || !valid_impl(impl)) {
         set_error("fov_seq2seq_decoder_fwd: invalid argument");
         return FOV_ERR_INVALID;
     }
     if (F_dec > 64) { set_error("fov_seq2seq_decoder_fwd: F_dec > 64 unsupported"); return FOV_ERR_UNSUPPORTED; }
+    if (!steps_ok("fov_seq2seq_decoder_fwd", T_out, B)) return FOV_ERR_UNSUPPORTED;
     const DecodePlan plan = plan_decode(B, T_out, 1, F_dec, H, impl);
     if (int rc = check_ws(workspace, workspace_bytes, plan.need)) return rc;
     LstmParams p = {};
@@ -556,9 +576,17 @@ int fov_seq2seq_tf_fwd(const float* enc_in, const float* dec_in, const float* en
                        const float* dense_W, const float* dense_b, float* out, int B, int T_in, int T_out,
                        int F_enc, int F_dec, int H, int act, int impl, void* workspace, size_t workspace_bytes,
                        fov_stream_t stream) {
-    if (B < 0 || T_in < 0 || T_out < 0 || F_enc <= 0 || F_dec <= 0 || H <= 0) {
+    // all three calls' operands before the first launch: a refused call has enqueued nothing
+    if (B < 0 || T_in < 0 || T_out < 0 || F_enc <= 0 || F_dec <= 0 || H <= 0 || !enc_K || !enc_R || !enc_b || !dec_K || !dec_R ||
+        !dec_b || !dense_W || (B > 0 && ((T_in > 0 && !enc_in) || (T_out > 0 && (!dec_in || !out)))) || !valid_act(act) ||
+        !valid_impl(impl)) {
         set_error("fov_seq2seq_tf_fwd: invalid argument");
         return FOV_ERR_INVALID;
+    }
+    if (!steps_ok("fov_seq2seq_tf_fwd", T_in > T_out ? T_in : T_out, B)) return FOV_ERR_UNSUPPORTED;
+    if ((long)B * T_out > 0x7fffffffL) {      // the head's row count is an int
+        set_error("fov_seq2seq_tf_fwd: B * T_out exceeds 2^31 - 1");
+        return FOV_ERR_UNSUPPORTED;
     }
     if (B == 0) return check_ws(workspace, workspace_bytes, kStatusBytes);
     const TfCarve at = tf_carve(B, T_in, T_out, F_enc, F_dec, H, impl);

@@ -199,8 +199,9 @@ int fov_act_fwd(const float* x, float* y, int64_t n, int activation, fov_stream_
 
 int fov_gauss_nll_grad(const float* mu, const float* var, const float* y, float* loss, float* dmu, float* dvar, int B,
                        int T_y, int fps, float scale, void* workspace, size_t workspace_bytes, fov_stream_t stream) {
-    if (B < 0 || T_y <= 0 || fps <= 0 || (B > 0 && (!mu || !var || !y || !dmu || !dvar))) {
-        set_error("fov_gauss_nll_grad: invalid argument");
+    if (B < 0 || B > kMaxRows3 || T_y <= 0 || fps <= 0 || (long)T_y * fps * 3 > 0x7fffffffL ||
+        (B > 0 && (!mu || !var || !y || !dmu || !dvar))) {
+        set_error("fov_gauss_nll_grad: invalid argument (B <= 2^29, 3 T_y fps < 2^31)");
         return FOV_ERR_INVALID;
     }
     if (B == 0) return FOV_OK;
@@ -233,8 +234,9 @@ int fov_xyz_sum1_grad(const float* p, float* dp, float* reg, int64_t n_pix, int 
 
 int fov_sample_refeed_fwd(const float* mu, const float* var, const float* noise, float* x, int64_t ldx, int B, int fps,
                           int std_mode, int layout, fov_stream_t stream) {
-    if (B < 0 || fps <= 0 || ldx < 3 * (int64_t)fps || (std_mode | layout) & ~1 || (B > 0 && (!mu || !var || !noise || !x))) {
-        set_error("fov_sample_refeed_fwd: invalid argument");
+    if (B < 0 || B > kMaxRows3 || fps <= 0 || fps > kMaxFps || ldx < 3 * (int64_t)fps || (std_mode | layout) & ~1 ||
+        (B > 0 && (!mu || !var || !noise || !x))) {
+        set_error("fov_sample_refeed_fwd: invalid argument (B <= 2^29, fps <= 2^20)");
         return FOV_ERR_INVALID;
     }
     return sample_refeed_fwd(mu, var, noise, x, (long)ldx, B, fps, std_mode, layout, (hipStream_t)stream);
@@ -242,9 +244,9 @@ int fov_sample_refeed_fwd(const float* mu, const float* var, const float* noise,
 
 int fov_sample_refeed_bwd(const float* dx, int64_t ldx, const float* var, const float* noise, float* dmu, float* dvar, int B,
                           int fps, int std_mode, int layout, int accumulate, fov_stream_t stream) {
-    if (B < 0 || fps <= 0 || ldx < 3 * (int64_t)fps || (std_mode | layout) & ~1 ||
+    if (B < 0 || B > kMaxRows3 || fps <= 0 || fps > kMaxFps || ldx < 3 * (int64_t)fps || (std_mode | layout) & ~1 ||
         (B > 0 && (!dx || !var || !noise || !dmu || !dvar))) {
-        set_error("fov_sample_refeed_bwd: invalid argument");
+        set_error("fov_sample_refeed_bwd: invalid argument (B <= 2^29, fps <= 2^20)");
         return FOV_ERR_INVALID;
     }
     return sample_refeed_bwd(dx, (long)ldx, var, noise, dmu, dvar, B, fps, std_mode, layout, accumulate, (hipStream_t)stream);
@@ -353,7 +355,11 @@ int fov_matmul(const float* a, const float* b, float* c, int M, int K, int N, vo
 
 int fov_colsum(const float* x, float* out, int64_t rows, int cols, int accumulate, void* workspace, size_t workspace_bytes,
                fov_stream_t stream) {
-    if (rows < 0 || cols <= 0 || !out || (rows > 0 && !x)) { set_error("fov_colsum: invalid argument"); return FOV_ERR_INVALID; }
+    // cols <= 2^24: the wide form counts its column blocks, (cols + 255) / 256, in an int
+    if (rows < 0 || cols <= 0 || cols > (1 << 24) || !out || (rows > 0 && !x)) {
+        set_error("fov_colsum: invalid argument (1 <= cols <= 2^24)");
+        return FOV_ERR_INVALID;
+    }
     if (int rc = check_ws(workspace, workspace_bytes, sizeof(float) * ((size_t)256 * cols + 64))) return rc;
     if (rows == 0) {
         return accumulate ? FOV_OK : zero_grad(out, (size_t)cols, (hipStream_t)stream);

@@ -197,7 +197,7 @@ static int launch_dense(const float* x, const float* W, const float* b, const fl
                                add_stride, y, N, In, Out, activation);
         return launch_check(xvec ? "dense (16 rows, vector x)" : "dense (16 rows, scalar x)");
     }
-    hipLaunchKernelGGL(dense_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, x, W, b, add, add_stride, y, N, In, Out, activation);
+    hipLaunchKernelGGL(dense_kernel, dim3((unsigned)(((long)N + 3) / 4)), dim3(256), 0, stream, x, W, b, add, add_stride, y, N, In, Out, activation);
     return launch_check("dense (wave per row)");
 }
 
@@ -387,12 +387,16 @@ __global__ __launch_bounds__(256) void window_stacks_kernel(const float* __restr
 
 using namespace fov;
 
+// the wave-per-row kernel strides its int loops over In by 64 and over Out by its tile: widths far below INT_MAX only
+static constexpr int kMaxDenseWidth = 1 << 24;
+
 extern "C" {
 
 int fov_dense_fwd(const float* x, const float* W, const float* b, float* y, int N, int In, int Out,
                   int activation, fov_stream_t stream) {
-    if (N < 0 || In <= 0 || Out <= 0 || !W || (N > 0 && (!x || !y)) || (activation != 0 && activation != 1)) {
-        set_error("fov_dense_fwd: invalid argument");
+    if (N < 0 || In <= 0 || Out <= 0 || In > kMaxDenseWidth || Out > kMaxDenseWidth || !W || (N > 0 && (!x || !y)) ||
+        (activation != 0 && activation != 1)) {
+        set_error("fov_dense_fwd: invalid argument (In, Out <= 2^24)");
         return FOV_ERR_INVALID;
     }
     if (N == 0) return FOV_OK;
@@ -401,8 +405,9 @@ int fov_dense_fwd(const float* x, const float* W, const float* b, float* y, int 
 
 int fov_dense_add_fwd(const float* x, const float* W, const float* b, const float* add, int64_t add_row_stride,
                       float* y, int N, int In, int Out, int activation, fov_stream_t stream) {
-    if (N < 0 || In <= 0 || Out <= 0 || !W || (N > 0 && (!x || !y || !add)) || (activation != 0 && activation != 1)) {
-        set_error("fov_dense_add_fwd: invalid argument");
+    if (N < 0 || In <= 0 || Out <= 0 || In > kMaxDenseWidth || Out > kMaxDenseWidth || !W || (N > 0 && (!x || !y || !add)) || add_row_stride < 0 ||
+        (activation != 0 && activation != 1)) {
+        set_error("fov_dense_add_fwd: invalid argument (In, Out <= 2^24, add_row_stride >= 0)");
         return FOV_ERR_INVALID;
     }
     if (N == 0) return FOV_OK;
@@ -412,8 +417,8 @@ int fov_dense_add_fwd(const float* x, const float* W, const float* b, const floa
 int fov_mix_head_fwd(const float* h, const float* dense_W, const float* dense_b, const float* mix_Wp, const float* add,
                      int64_t add_row_stride, float* p, float* m, int N, int H, int O, fov_stream_t stream) {
     if (N < 0 || H <= 0 || O <= 0 || O > 8 || (H & 3) || H > 2048 || !dense_W || !dense_b || !mix_Wp ||
-        (N > 0 && (!h || !add || !p || !m)) || (((uintptr_t)h) & 15)) {
-        set_error("fov_mix_head_fwd: invalid argument (O <= 8, H a multiple of 4 and <= 2048, h 16-byte aligned)");
+        (N > 0 && (!h || !add || !p || !m)) || add_row_stride < 0 || (((uintptr_t)h) & 15)) {
+        set_error("fov_mix_head_fwd: invalid argument (O <= 8, H a multiple of 4 and <= 2048, h 16-byte aligned, add_row_stride >= 0)");
         return FOV_ERR_INVALID;
     }
     if (N == 0) return FOV_OK;
@@ -451,8 +456,8 @@ int fov_dense_fwd_bf16(const float* x, const float* W, const float* b, float* y,
 }
 
 int fov_meanvar_xyz(const float* y, float* out, int64_t rows, int fps, fov_stream_t stream) {
-    if (rows < 0 || fps <= 0 || (rows > 0 && (!y || !out))) {
-        set_error("fov_meanvar_xyz: invalid argument");
+    if (rows < 0 || fps <= 0 || fps > kMaxFps || (rows > 0 && (!y || !out))) {
+        set_error("fov_meanvar_xyz: invalid argument (1 <= fps <= 2^20)");
         return FOV_ERR_INVALID;
     }
     if (rows == 0) return FOV_OK;

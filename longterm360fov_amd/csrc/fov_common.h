@@ -149,6 +149,11 @@ int launch_check(const char* what);
 // FOV_OK when `need` bytes fit the 16-byte aligned workspace (need = 0: no workspace wanted), else FOV_ERR_WORKSPACE with its message
 int check_ws(void* ws, size_t have, size_t need);
 inline bool valid_act(int act) { return act == FOV_ACT_SIGMOID || act == FOV_ACT_HARD_SIGMOID; }
+// one-workgroup-per-tile launches count their tiles in an int: batches and lengths beyond this are refused as arithmetic
+constexpr int kMaxTileBatch = 1 << 30;
+// kernels that index rows as 3 * b and frames as 3 * f in an int: the bounds their entry points refuse beyond
+constexpr int kMaxFps = 1 << 20, kMaxRows3 = 1 << 29;
+inline bool valid_impl(int impl) { return impl == FOV_IMPL_AUTO || impl == FOV_IMPL_GENERIC || impl == FOV_IMPL_CLUSTER; }
 // wide-input layer, H = 256, 96 < F <= 256 (lstm_wide.hip)
 bool wide_shape_ok(int F, int H);
 bool wide_narrow_preferred(int B, int F, int H);

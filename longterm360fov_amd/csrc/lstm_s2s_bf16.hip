@@ -358,7 +358,7 @@ bool dense_bf16_shape_ok(int In, int Out) { return In >= 1 && In <= QH && Out >=
 
 int launch_dense_bf16(const float* x, const float* W, const float* b, float* y, int N, int In, int Out, int act, hipStream_t stream) {
     if (N == 0) return FOV_OK;
-    hipLaunchKernelGGL(dense_bf16_kernel, dim3((N + QBT - 1) / QBT), dim3(256), 0, stream, x, W, b, y, N, In, Out, act);
+    hipLaunchKernelGGL(dense_bf16_kernel, dim3((unsigned)(((long)N + QBT - 1) / QBT)), dim3(256), 0, stream, x, W, b, y, N, In, Out, act);
     return launch_check("bf16 dense");
 }
 

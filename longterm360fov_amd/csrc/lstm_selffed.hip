@@ -338,7 +338,7 @@ int selffed_refuse(const char* entry, int B, int T, int O, int H) {
 }  // namespace
 
 // pure arithmetic: no device query
-bool selffed_shape_ok(int B, int T, int O, int H) { return B >= 0 && T >= 0 && (H == 32 || H == 64) && O >= 1 && O <= 8; }
+bool selffed_shape_ok(int B, int T, int O, int H) { return B >= 0 && B <= kMaxTileBatch && T >= 0 && T <= kMaxTileBatch && (H == 32 || H == 64) && O >= 1 && O <= 8; }
 
 }  // namespace fov
 

@@ -405,7 +405,7 @@ int selffed2_refuse(const char* entry, const char* widths, int B, int T, int O, 
 
 // pure arithmetic: no device query.  The backward keeps R2^T, K2^T and R1^T in LDS: 48 KB at H = 32, 192 KB (> 160 KB) at H = 64
 bool selffed2_shape_ok(int B, int T, int O, int H, bool backward) {
-    return B >= 0 && T >= 0 && (H == 32 || (H == 64 && !backward)) && O >= 1 && O <= 8;
+    return B >= 0 && B <= kMaxTileBatch && T >= 0 && T <= kMaxTileBatch && (H == 32 || (H == 64 && !backward)) && O >= 1 && O <= 8;
 }
 
 }  // namespace fov

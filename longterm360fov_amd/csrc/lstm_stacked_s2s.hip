@@ -244,7 +244,7 @@ int launch_stacked(const StackedParams& p, int act, hipStream_t stream) {
 
 // pure arithmetic (and the knob): no device query
 bool stacked_s2s_shape_ok(int B, int T_in, int T_out, int F_enc, int F_dec, int H, int L) {
-    return B >= 0 && T_in >= 0 && T_out >= 0 && (H == 32 || H == 64) && (L == 2 || L == 3) && F_enc >= 1 && F_enc <= SS_MAX_F &&
+    return B >= 0 && B <= kMaxTileBatch && T_in >= 0 && T_in <= kMaxTileBatch && T_out >= 0 && T_out <= kMaxTileBatch && (H == 32 || H == 64) && (L == 2 || L == 3) && F_enc >= 1 && F_enc <= SS_MAX_F &&
            F_dec >= 1 && F_dec <= 8;
 }
 

@@ -769,7 +769,7 @@ int fov_mlp_head_fwd(const float* x, const float* const* W, const float* const* 
     const size_t lds = sizeof(float) * (size_t)MH_FWD_LDS;
     int rc = ensure_dynamic_lds((const void*)mlp_head_fwd_kernel, lds, MH_NT);
     if (rc) return rc;
-    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3((unsigned)((B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3((unsigned)(((long)B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
     return launch_check("mlp head forward");
 }
 
@@ -811,7 +811,7 @@ int fov_mlp_head_bwd(const float* x, const float* const* W, const float* const* 
         const size_t lds = sizeof(float) * (size_t)CH_LDS;
         int rc = ensure_dynamic_lds((const void*)mlp_head_bwd_chain_kernel, lds, MH_NT);
         if (rc) return rc;
-        hipLaunchKernelGGL(mlp_head_bwd_chain_kernel, dim3((unsigned)((B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(mlp_head_bwd_chain_kernel, dim3((unsigned)(((long)B + MH_ROWS - 1) / MH_ROWS)), dim3(MH_NT), lds, (hipStream_t)stream, p);
         rc = launch_check("mlp head backward chain");
         if (rc) return rc;
     }
