@@ -9,6 +9,7 @@ staged through torch (device memory and streams only).  Weights keep the Keras l
 (``[kernel, recurrent_kernel, bias]`` per LSTM, ``[kernel, bias]`` for Dense) so files round-trip.
 """
 import os
+import threading
 
 import numpy as np
 
@@ -153,6 +154,59 @@ class _ArrayFeed:
         self.val_dev = None
         self.resident = sum(a.nbytes for a in self.inputs) + self.tgt.nbytes <= self.limit
         self.dev_arrays = [self._d(a) for a in self.inputs] + [self._d(self.tgt)] if self.resident else None
+        # A set that is not resident goes through staging rings (hostpipe.py), one for the training batches and one for the
+        # validation batches, half of FOV_HOST_PIPELINE_BYTES each: the fit loop names the epoch's batches up front
+        # (plan_epoch, an attribute only here), and while step k runs batch k + 1 is gathered into pinned memory and uploaded.
+        self._rings, self._train_up, self._val_up = {}, None, None
+        if not self.resident and model._pipelined():
+            self.plan_epoch = self._plan_epoch
+
+    def _ring(self, which, arrays, rows):
+        from . import hostpipe
+        if which not in self._rings:
+            self._rings[which] = hostpipe.make_ring(self.model._pipe_backend, [a.shape[1:] for a in arrays], [], rows,
+                                                    hostpipe.budget_bytes() // 2)
+        return self._rings[which]
+
+    def _plan_epoch(self, train_rows, val_rows):
+        """train_rows: per step the rows of the arrays it takes (what train_batch gets as lidx); val_rows: per validation
+        batch its slice of the held-out rows.  Batches are then handed out in this order."""
+        from . import hostpipe
+        for up in (self._train_up, self._val_up):      # the last batch of the pass before: its readers are all queued by now
+            if up is not None:
+                up.ring.finish()
+        self._train_up = self._val_up = None
+        arrays = self.inputs + [self.tgt]
+        ring = self._ring("train", arrays, max(len(r) for r in train_rows)) if train_rows else None
+        if ring is not None:
+            self._train_up = hostpipe.Uploader(ring)
+            self._train_plan = [(self._gather(arrays, r), len(r)) for r in train_rows]
+        if val_rows and self.val is not None and sum(a.nbytes for a in self.val[0]) + self.val[1].nbytes > self.limit:
+            arrays = list(self.val[0]) + [self.val[1]]
+            ring = self._ring("val", arrays, max(r.stop - r.start for r in val_rows))
+            if ring is not None:
+                self._val_up = hostpipe.Uploader(ring)
+                self._val_plan = [(self._gather(arrays, r), r.stop - r.start) for r in val_rows]
+
+    def abort(self):
+        """After an exception in the fit loop: nothing of the staging rings is in flight when this returns; they are dropped."""
+        for ring in self._rings.values():
+            if ring is not None:
+                ring.abort()
+        self._rings, self._train_up, self._val_up = {}, None, None
+
+    @staticmethod
+    def _gather(arrays, rows):
+        from . import hostpipe
+        return lambda views: [hostpipe.gather(v, a, rows) for v, a in zip(views, arrays)]
+
+    @staticmethod
+    def _staged(up, plan):
+        """The next batch of `plan` from its ring, and the one after it staged behind it."""
+        dev = up.next(*plan[up.k])
+        if up.k < len(plan):
+            up.ahead(*plan[up.k])
+        return dev
 
     def _d(self, a):
         import torch
@@ -172,6 +226,8 @@ class _ArrayFeed:
 
     def train_batch(self, lo, hi, lidx):
         """Rows lo .. hi-1 of the epoch's order, which are the rows `lidx` of the arrays -> device [*inputs, target]."""
+        if self._train_up is not None:
+            return self._staged(self._train_up, self._train_plan)
         if not self.resident:
             return [self._d(arr[lidx]) for arr in self.inputs] + [self._d(self.tgt[lidx])]
         if self.epoch_arrays is not None:
@@ -183,10 +239,39 @@ class _ArrayFeed:
 
     def val_batch(self, lo, hi):
         val = self.val
+        if self._val_up is not None:
+            return self._staged(self._val_up, self._val_plan)
         if self.val_dev is None and sum(a.nbytes for a in val[0]) + val[1].nbytes <= self.limit:
             self.val_dev = [self._d(a) for a in val[0]] + [self._d(val[1])]      # uploaded once per fit()
         sl = slice(lo, hi)
         return [t[sl] for t in self.val_dev] if self.val_dev is not None else [self._d(arr[sl]) for arr in val[0]] + [self._d(val[1][sl])]
+
+
+class _ChunkUploader:
+    """evaluate's chunks (input list, target: contiguous float32 rows) through the model's 'evaluate' staging ring, in order:
+    chunk k + 1 is copied into pinned memory and uploaded while the kernels of chunk k run.  rows: the chunk size, set by
+    evaluate before the first chunk; 0: every chunk is left to the caller (None), as is every one when there is no ring."""
+
+    def __init__(self, model):
+        self.model, self.rows, self.ring, self.up = model, 0, None, None
+
+    def __call__(self, xb, yb):
+        from . import hostpipe
+        if not self.rows:
+            return None
+        arrays = list(xb) + [yb]
+        if self.up is None:
+            self.ring = self.model._pipe_acquire("evaluate", [a.shape[1:] for a in arrays], [], self.rows)
+            if self.ring is None:
+                self.rows = 0
+                return None
+            self.up = hostpipe.Uploader(self.ring)
+        return self.up.next(lambda views: [hostpipe.narrow(v, a) for v, a in zip(views, arrays)], len(yb))
+
+    def close(self, failed=False):
+        if self.ring is not None:
+            self.model._pipe_release("evaluate", self.ring, failed)
+            self.ring = self.up = None
 
 
 class _DatasetFeed:
@@ -221,8 +306,12 @@ class _DatasetFeed:
 def _keras_fit(model, trainer, inputs, y, batch_size, epochs, validation_split, shuffle, callbacks, initial_epoch,
                validation_data):
     """Keras `Model.fit` on host arrays: see _fit_loop for the semantics."""
-    return _fit_loop(model, trainer, _ArrayFeed(model, inputs, y, validation_split, validation_data), batch_size, epochs, shuffle,
-                     callbacks, initial_epoch)
+    feed = _ArrayFeed(model, inputs, y, validation_split, validation_data)
+    try:
+        return _fit_loop(model, trainer, feed, batch_size, epochs, shuffle, callbacks, initial_epoch)
+    except BaseException:
+        feed.abort()
+        raise
 
 
 def _fit_loop(model, trainer, feed, batch_size, epochs, shuffle, callbacks, initial_epoch):
@@ -250,6 +339,10 @@ def _fit_loop(model, trainer, feed, batch_size, epochs, shuffle, callbacks, init
             # not synchronised), then each takes its contiguous shard of every global batch
             idx = parallel.broadcast_index(idx)
         feed.begin_epoch(idx, shuffle)
+        if getattr(feed, "plan_epoch", None) is not None:      # a feed that stages batch k + 1 under step k is told the order
+            steps = [idx[lo:lo + batch_size] for lo in range(0, n_train, batch_size)]
+            feed.plan_epoch([g[slice(*parallel.shard_range(len(g), rank, world))] for g in steps],
+                            [slice(lo, lo + min(batch_size, feed.n_val - lo)) for lo in range(0, feed.n_val, max(batch_size, 1))])
         # the epoch's loss sum stays on the device (fp64): no host synchronisation per step, so the launches of step k + 1 are
         # queued while step k runs (the returned loss tensor is overwritten by the NEXT step: the add is queued before it)
         # ... and so do the matches of the accuracy metric, in the trainer's own accumulator: two more reads per epoch, none per step
@@ -306,6 +399,9 @@ class KerasModelSurface:
         self._accuracy = False
         self._lr = 1e-3
         self.stop_training = False
+        # host arrays through a staging ring (hostpipe.py): True / False, None: FOV_HOST_PIPELINE, else hostpipe.DEFAULT_ON
+        self.host_pipeline = None
+        self._pipe_lock, self._pipe_rings = threading.Lock(), {}
 
     # ---- weights ----
     def get_weights(self):
@@ -395,6 +491,82 @@ class KerasModelSurface:
         import torch
         return torch.from_numpy(_as_f32(a)).to(self.device)
 
+    # ---- host arrays through a ring of staging slots (hostpipe.py) ----
+    def _pipelined(self):
+        from . import hostpipe
+        return hostpipe.enabled(self.host_pipeline)
+
+    def _host_in(self, a):
+        """A predict input on its way to _predict_chunks: with the pipeline on, a NumPy array of a real dtype is handed on as
+        it is - the ring narrows it chunk by chunk, so chunk 0 runs before the last one is narrowed; anything else (lists,
+        scalars; every input with the pipeline off) becomes a contiguous float32 array here, as always."""
+        return a if self._stays_on_host(a) else _as_f32(a)
+
+    def _stays_on_host(self, a):
+        from . import hostpipe
+        return hostpipe.is_host_array(a) and self._pipelined()
+
+    def _pipe_backend(self):
+        from . import hostpipe
+        return hostpipe.TorchBackend(self.device)
+
+    def _pipe_acquire(self, kind, in_shapes, out_shapes, rows):
+        """The model's ring of this kind ('predict' | 'evaluate') for these row shapes, made on first use and kept until the
+        shapes change, with the model's pipeline lock HELD - or None, lock free: another thread is in a pipelined call on
+        this model, or two slots do not fit FOV_HOST_PIPELINE_BYTES.  The caller then takes the serial loop."""
+        from . import hostpipe
+        if not self._pipe_lock.acquire(blocking=False):
+            return None
+        key = (tuple(map(tuple, in_shapes)), tuple(map(tuple, out_shapes)), int(rows), hostpipe.budget_bytes())
+        kept = self._pipe_rings.get(kind)
+        if kept is None or kept[0] != key:
+            self._pipe_rings.pop(kind, None)
+            try:
+                kept = (key, hostpipe.make_ring(self._pipe_backend, in_shapes, out_shapes, rows))
+            except BaseException:
+                self._pipe_lock.release()
+                raise
+            self._pipe_rings[kind] = kept
+        if kept[1] is None:
+            self._pipe_lock.release()
+        return kept[1]
+
+    def _pipe_release(self, kind, ring, failed=False):
+        """After an exception the three streams are waited for and the ring is dropped: the next call makes a new one."""
+        try:
+            if failed:
+                self._pipe_rings.pop(kind, None)
+                ring.abort()
+            else:
+                ring.finish()
+        finally:
+            self._pipe_lock.release()
+
+    def _predict_pipelined(self, arrays, batch_size, run, empty):
+        """_predict_chunks' loop with the host arrays among `arrays` staged through the ring: same chunks, same run(...) calls
+        in the same order, same result.  None where the serial loop has to run: no host array among them, one that is not a
+        NumPy array of a real dtype, or no ring (_pipe_acquire)."""
+        from . import hostpipe
+        several = isinstance(empty, list)
+        host = [i for i, a in enumerate(arrays) if a is not None and not hasattr(a, "is_cuda")]
+        if not host or not all(hostpipe.is_host_array(arrays[i]) for i in host):
+            return None
+        plan = hostpipe.chunk_plan(arrays[0].shape[0], batch_size)
+        ring = self._pipe_acquire("predict", [arrays[i].shape[1:] for i in host], empty if several else [empty], plan[0][1])
+        if ring is None:
+            return None
+
+        def call(lo, hi, dev):
+            staged = iter(dev)
+            return run(*[a if a is None else a[lo:hi] if hasattr(a, "is_cuda") else next(staged) for a in arrays])
+        try:
+            res = hostpipe.predict(ring, [arrays[i] for i in host], plan, call, several)
+        except BaseException:
+            self._pipe_release("predict", ring, failed=True)
+            raise
+        self._pipe_release("predict", ring)
+        return res
+
     def _predict_chunks(self, arrays, batch_size, run, empty):
         """run(*chunks) over `batch_size` rows of `arrays` at a time (None: all rows in one call), each result copied to the
         host, the results concatenated along the rows.  arrays: host arrays (a chunk is uploaded), device tensors (sliced) or
@@ -403,6 +575,10 @@ class KerasModelSurface:
         n = arrays[0].shape[0]
         bs = n if not batch_size else int(batch_size)
         several = isinstance(empty, list)
+        if n > max(bs, 1) and self._pipelined():      # two chunks or more of host arrays: through the staging ring
+            res = self._predict_pipelined(arrays, batch_size, run, empty)
+            if res is not None:
+                return res
         outs = []
         for lo in range(0, n, max(bs, 1)):
             o = run(*[a if a is None else a[lo:lo + bs] if hasattr(a, "is_cuda") else self._to_device(a[lo:lo + bs]) for a in arrays])
@@ -497,21 +673,31 @@ class KerasModelSurface:
         for xb, yb in batches:
             yield self._fit_inputs(xb), _as_f32(self._fit_target(yb))
 
-    def _evaluate_batches(self, batches, what):
+    def _evaluate_batches(self, batches, what, upload=None):
         """Loss (and accuracy) over an iterable of host batches (input list, target array) in the trainer's form (_host_batches),
         batch-size-weighted -> float, or [loss, acc] when the accuracy metric is compiled (model.metrics_names).  No update;
-        sums stay on the device until the end.  Nothing of `batches` is drawn before the compile check."""
+        sums stay on the device until the end.  Nothing of `batches` is drawn before the compile check.  upload: evaluate's
+        _ChunkUploader - (xb, yb) -> the batch on the device through the staging ring, or None: upload it here."""
         if self.optimizer is None:
             raise RuntimeError("call compile() before %s()" % what)
         tr = self._get_trainer()
         meter = _EpochMeter(self.device, self._accuracy)
-        for xb, yb in batches:
-            dev = [self._to_device(a) for a in xb] + [self._to_device(yb)]
-            if self._accuracy:
-                loss, matches = tr.eval_metrics(*dev)
-                meter.add(loss, len(yb), matches, tr.metric_rows(yb.shape))
-            else:
-                meter.add(tr.eval_loss(*dev), len(yb))
+        try:
+            for xb, yb in batches:
+                dev = upload(xb, yb) if upload is not None else None
+                if dev is None:
+                    dev = [self._to_device(a) for a in xb] + [self._to_device(yb)]
+                if self._accuracy:
+                    loss, matches = tr.eval_metrics(*dev)
+                    meter.add(loss, len(yb), matches, tr.metric_rows(yb.shape))
+                else:
+                    meter.add(tr.eval_loss(*dev), len(yb))
+        except BaseException:
+            if upload is not None:
+                upload.close(failed=True)
+            raise
+        if upload is not None:
+            upload.close()
         tr.check()
         return [meter.loss(), meter.acc()] if self._accuracy else meter.loss()
 
@@ -521,9 +707,12 @@ class KerasModelSurface:
         def chunks():      # converted once, here: _evaluate_batches takes the batches as the trainer takes them
             xs, yt = self._fit_inputs(x), _as_f32(self._fit_target(y))
             bs = max(int(batch_size or len(yt)), 1)
+            if upload is not None and len(yt) > bs:      # two chunks or more: their uploads run under the kernels
+                upload.rows = bs
             for lo in range(0, len(yt), bs):
                 yield [a[lo:lo + bs] for a in xs], yt[lo:lo + bs]
-        return self._evaluate_batches(chunks(), "evaluate")
+        upload = _ChunkUploader(self) if self._pipelined() else None
+        return self._evaluate_batches(chunks(), "evaluate", upload)
 
     def test_on_batch(self, x, y):
         """Keras `test_on_batch`: evaluate on (x, y) as ONE batch."""
@@ -752,7 +941,7 @@ class Seq2SeqLSTM(KerasModelSurface):
         """Training-graph forward: x = [encoder_input (N,T_in,F_enc), decoder_input (N,T_out,F_dec)]
         -> (N,T_out,F_dec).  `batch_size` chunks the device calls (None = all at once)."""
         enc, dec_in = x
-        enc, dec_in = _as_f32(enc), _as_f32(dec_in)
+        enc, dec_in = self._host_in(enc), self._host_in(dec_in)
         self._device_weights()
         y = self._predict_chunks([enc, dec_in], batch_size, self.predict_device, (dec_in.shape[1], self.num_decoder_tokens))
         self._ws.check()
@@ -902,15 +1091,15 @@ class NoTeacherForcingSeq2Seq(Seq2SeqLSTM):
             return pad_rows(w[k], Hp)
         return w[k]
 
-    def _split_inputs(self, x):
+    def _split_inputs(self, x, convert=_as_f32):
         if self.enc_last_out_as_dec_in:
             enc = x[0] if isinstance(x, (list, tuple)) else x
-            return _as_f32(enc), None
-        return _as_f32(x[0]), _as_f32(x[1])
+            return convert(enc), None
+        return convert(x[0]), convert(x[1])
 
     def predict(self, x, batch_size=None, verbose=0):
         import torch
-        enc, dec0 = self._split_inputs(x)
+        enc, dec0 = self._split_inputs(x, self._host_in)
         ops, dw, act = self._ops(), self._device_weights(), self.recurrent_activation
         T_out, O, H, F = self.predict_step, self.num_decoder_tokens, self.latent_dim, self.num_encoder_tokens
         plain = not (self.add_residual_link or self.enc_last_out_as_dec_in or self.dense_activation != "tanh" or
@@ -1034,7 +1223,7 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
 
     def predict(self, x, batch_size=None, verbose=0):
         """[encoder_input (N,T_in,F), decoder_input (N,T_out,O)] -> (N,T_out,O), teacher-forced graph (:332)."""
-        enc, dec_in = _as_f32(x[0]), _as_f32(x[1])
+        enc, dec_in = self._host_in(x[0]), self._host_in(x[1])
         self._device()
         y = self._predict_chunks([enc, dec_in], batch_size, self.predict_device, (dec_in.shape[1], self.O))
         self._ws.check()
@@ -1121,7 +1310,7 @@ class StackedSeq2SeqLSTM(KerasModelSurface):
     def decode_sequence(self, input_seq, first_decoder_input, predict_step=None, batch_size=None):
         """Autoregressive loop of :399-430, any batch: encoder states, then `predict_step` steps through all decoder
         layers, each Dense output fed back as the next input (decode_device per chunk of `batch_size` rows)."""
-        enc, d0 = _as_f32(input_seq), _as_f32(first_decoder_input)
+        enc, d0 = self._host_in(input_seq), self._host_in(first_decoder_input)
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         self._device()
         y = self._predict_chunks([enc, d0], batch_size, lambda e, xin: self.decode_device(e, xin, T_out), (T_out, self.O))
@@ -1180,11 +1369,11 @@ class OthersContextSeq2Seq(KerasModelSurface):
         self._w = w
         self._init_surface(others_context_order(mode), impl, device)
 
-    def _inputs(self, x):
+    def _inputs(self, x, convert=_as_f32):
         if self.mode == "target_user_only":
-            enc, dec0 = _as_f32(x[0]), _as_f32(x[-1])
+            enc, dec0 = convert(x[0]), convert(x[-1])
             return enc, np.zeros((enc.shape[0], self.predict_step, self.U - 1, self.O), np.float32), dec0
-        return _as_f32(x[0]), _as_f32(x[1]), _as_f32(x[2])
+        return convert(x[0]), convert(x[1]), convert(x[2])
 
     def _context(self, ops, dw, oth):
         """(B,T_out,U-1,6) device tensor -> [ctx_t W_c + b] (B,T_out,O), or None."""
@@ -1215,7 +1404,7 @@ class OthersContextSeq2Seq(KerasModelSurface):
     def predict(self, x, batch_size=None, verbose=0):
         import torch
         from . import ops
-        enc, oth, dec0 = self._inputs(x)
+        enc, oth, dec0 = self._inputs(x, self._host_in)
         dw, act, H, O = self._device_weights(), self.recurrent_activation, self.H, self.O
         T_out = oth.shape[1]
         W_h = dw["dense_W"][dw["dense_W"].shape[0] - H:].contiguous()
@@ -1306,7 +1495,7 @@ class NoTeacherForcingOthersConvLSTM(KerasModelSurface):
 
     def predict(self, x, batch_size=None, verbose=0):
         from . import ops
-        enc, oth, dec0 = (_as_f32(a) for a in x)
+        enc, oth, dec0 = (self._host_in(a) for a in x)
         tr = self._get_trainer()
         if self._dw is None:          # weights were set from outside since the trainer last saw them
             tr.load_weights_(self._w)
@@ -1358,7 +1547,7 @@ class KerasSingleLSTM(KerasModelSurface):
         """`noise` (predict_step-1, N, F) standard normal for the sampled re-feed (drawn with torch.randn if None)."""
         import torch
         from . import ops
-        x = _as_f32(x)
+        x = self._host_in(x)
         dw, act = self._device_weights(), self.recurrent_activation
         P = self.predict_step
         lo = 0       # first row of the chunk: the caller's noise is (P-1, N, F), rows on its second axis
@@ -1538,7 +1727,7 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         return out.transpose(0, 1)
 
     def predict(self, x, batch_size=None, verbose=0):
-        enc, others, dec0 = (_as_f32(a) for a in x)
+        enc, others, dec0 = (self._host_in(a) for a in x)
         self._device_weights()
         y = self._predict_chunks([enc, others, dec0], batch_size, self.predict_device, (others.shape[1], self.num_decoder_tokens))
         self._ws.check()
@@ -1762,7 +1951,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         return (T_out, 6) if self.head == "dense" else (T_out, H, W, self._w["head2_W"].shape[3])
 
     def predict(self, x, batch_size=None, predict_step=None, verbose=0):
-        enc, dec0 = _as_f32(x[0]), _as_f32(x[1])
+        enc, dec0 = self._host_in(x[0]), self._host_in(x[1])
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         return self._predict_chunks([enc, dec0], batch_size, lambda e, d: self.predict_device(e, d, T_out),
                                     self._output_shape(T_out, *enc.shape[2:4]))
@@ -1772,7 +1961,7 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
         (convlstm_seq2seq.py:537-542, convlstm_heatmap.py:556-558), with the arg-max taken on the device: only the int64
         (N, T_out, C_out) pixel numbers reach the host, not the maps."""
         self._check_map_head()
-        enc, dec0 = _as_f32(x[0]), _as_f32(x[1])
+        enc, dec0 = self._host_in(x[0]), self._host_in(x[1])
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
         return self._predict_chunks([enc, dec0], batch_size, lambda e, d: self.predict_index_device(e, d, T_out),
                                     (T_out, self._w["head2_W"].shape[3])).astype(np.int64)
@@ -1949,7 +2138,8 @@ class ConvLSTMSeq2Seq(KerasModelSurface):
             raise ValueError("output must be 'maps', 'index' or 'xyz', got %r" % (output,))
         self._check_onehot_model()
         T_out = cfg.predict_step if predict_step is None else int(predict_step)
-        enc, dec = self._xyz_on_device(enc_xyz), self._xyz_on_device(dec_xyz)
+        # (host arrays stay on the host with the pipeline on: _predict_chunks uploads them chunk by chunk, under the kernels)
+        enc, dec = (a if self._stays_on_host(a) else self._xyz_on_device(a) for a in (enc_xyz, dec_xyz))
         if output == "maps":
             return self._predict_chunks([enc, dec], batch_size, lambda e, d: self.predict_device(
                 ops.one_hot_maps(e, channels=32), ops.one_hot_maps(d, channels=32), T_out), self._output_shape(T_out, 36, 18))
