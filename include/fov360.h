@@ -165,8 +165,21 @@ int fov_mix_head_wgrad(const float* h2, const float* dpre_p, const float* others
  *   (both strides >= 0).  out (T_out,B,O) step-major = m_t.  h1T..c2T (B,H): final states or NULL.
  *   Training buffers (all or none): P (T_out,B,O) = p_t; H1,C1,H2,C2 (T_out,B,H) = states after step t;
  *   res1,res2 (T_out,B,5,H) = activated i,f,g,o and c (the reserve layout of fov_lstm_seq_fwd_train with T = 1).
- * Supported: H = 256, O <= 8 (FOV_ERR_UNSUPPORTED otherwise: use the per-step entry points). */
+ * Supported: O <= 8 and H = 256, 32 or 64 (FOV_ERR_UNSUPPORTED otherwise: use the per-step entry points).
+ *   H = 256       the persistent kernel, eight workgroups per 16-sequence tile exchanging h through the workspace.
+ *   H = 32 or 64  the script's own latent_dim (given_others...py:38) and twice it: ONE workgroup owns a tile for both layers and
+ *                 every step (the ownership of fov_selffed2_decoder_fwd): no exchange, nothing to wait on, and NO workspace -
+ *                 `workspace` may be NULL and workspace_bytes is not looked at (fov_mix_decoder_workspace_bytes answers the
+ *                 status header's size there).  fp32 only: fov_mix_decoder_fwd_bf16 / _bwd_bf16 stay H = 256.  The backward
+ *                 has H = 32 alone (at 64 its three transposed matrices would take 192 KB of LDS): fov_mix_decoder_bwd at
+ *                 H = 64 is FOV_ERR_UNSUPPORTED and the caller walks the forward's tapes with the per-step entry points.
+ * The argument checks, their order and the B = 0 / T_out = 0 behaviour (FOV_OK, nothing launched, nothing written) are the
+ * same at every width.  fov_mix_decoder_tile_supported(B, T_out, H, O, backward) is the rule of the H = 32 / 64 kernels as
+ * arithmetic (no device query): 1 where fov_mix_decoder_fwd (backward = 0) / fov_mix_decoder_bwd (backward != 0) would run the
+ * one-workgroup-per-tile kernel - H = 32, or 64 for the forward, 1 <= O <= 8, 0 <= B, T_out <= 2^30 and (T_out + 2) * ceil(B / 8)
+ * <= 2^30, the bound of every LSTM entry point - and 0 for every other shape, H = 256 included. */
 size_t fov_mix_decoder_workspace_bytes(int B, int H);
+int fov_mix_decoder_tile_supported(int B, int T_out, int H, int O, int backward);
 int fov_mix_decoder_fwd(const float* dec0, const float* h1, const float* c1, const float* h2, const float* c2,
                         const float* oth_proj, int64_t oth_batch_stride, int64_t oth_step_stride,
                         const float* dec1_K, const float* dec1_R, const float* dec1_b,
@@ -375,7 +388,8 @@ int fov_lstm_stack2_fwd_bf16(const float* x, const float* K1, const float* R1, c
  *        pre-activation gradients of the mixing / Dense layers, for every step (each weight gradient is then one
  *        product over all steps: dK = x^T dz, dR = h_prev^T dz, dW = in^T dpre); dh1_0..dc2_0 (B,H) gradient
  *        w.r.t. the decoder's initial state (= the encoder's final state).
- * Supported: H = 256, O <= 8. */
+ * Supported: O <= 8 and H = 256 (persistent kernel, workspace) or H = 32 (one workgroup per tile, workspace may be NULL and
+ * its size is not looked at); H = 64 is FOV_ERR_UNSUPPORTED (see fov_mix_decoder_fwd). */
 size_t fov_mix_decoder_bwd_workspace_bytes(int B, int H);
 /* The fp32 fused decoder kernels keep a fragment-ordered copy of dec2_K in their workspaces, packed at every launch (the
  * weights change every optimizer step).  The pack depends on the weights only: this call runs it for the forward and / or

@@ -39,6 +39,7 @@ SIGNATURES = {
     "fov_mix_head_fwd": (_I, [_P] * 5 + [ctypes.c_int64, _P, _P] + [_I] * 3 + [_P]),
     "fov_mix_head_bwd": (_I, [_P] * 9 + [_I] * 3 + [_P]),
     "fov_mix_decoder_workspace_bytes": (_SZ, [_I] * 2),
+    "fov_mix_decoder_tile_supported": (_I, [_I] * 5),
     "fov_mix_decoder_fwd": (_I, [_P] * 6 + [ctypes.c_int64] * 2 + [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_mix_decoder_fwd_bf16": (_I, [_P] * 6 + [ctypes.c_int64] * 2 + [_P] * 21 + [_I] * 5 + [_P, _SZ, _P]),
     "fov_lstm_seq_fwd_bf16": (_I, [_P] * 10 + [_I] * 5 + [_P, _SZ, _P]),

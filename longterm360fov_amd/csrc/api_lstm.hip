@@ -16,8 +16,9 @@ static bool want_cluster(int impl, int F, int H, int F_dec, bool decode) {
 // The persistent kernels tag every exchange step with a 32-bit epoch and count a launch's span of them in an int: steps times
 // the tile rounds a group may make (at most one per 8-row tile) must stay far below 2^31.  Decided here, as arithmetic, for
 // every LSTM entry point alike - whichever kernel the call would reach.
+static bool steps_ok_quiet(long steps, int B) { return (steps + 2) * (((long)B + 7) / 8 > 0 ? ((long)B + 7) / 8 : 1) <= (1L << 30); }
 static bool steps_ok(const char* who, long steps, int B) {
-    if ((steps + 2) * (((long)B + 7) / 8 > 0 ? ((long)B + 7) / 8 : 1) <= (1L << 30)) return true;
+    if (steps_ok_quiet(steps, B)) return true;
     set_error("%s: (steps + 2) * ceil(B / 8) exceeds 2^30 (steps = %ld, B = %d)", who, steps, B);
     return false;
 }
@@ -383,10 +384,21 @@ static int mix_decoder_fwd_impl(const float* dec0, const float* h1, const float*
     const int ntrain = (P != nullptr) + (H1 != nullptr) + (C1 != nullptr) + (H2 != nullptr) + (C2 != nullptr) + (res1 != nullptr) +
                        (res2 != nullptr);
     if (ntrain != 0 && ntrain != 7) { set_error("fov_mix_decoder_fwd: give all training buffers or none"); return FOV_ERR_INVALID; }
-    if (H != 256 || O > 8) { set_error("fov_mix_decoder_fwd: the fused decoder supports H = 256, O <= 8"); return FOV_ERR_UNSUPPORTED; }
+    // H = 256: the persistent eight-workgroups-per-tile kernels; fp32 H = 32 / 64: one workgroup per tile (mix_tile.hip), no workspace
+    const bool tile = !bf16 && (H == 32 || H == 64);
+    if ((H != 256 && !tile) || O > 8) {
+        set_error(bf16 ? "fov_mix_decoder_fwd_bf16: the fused decoder supports H = 256, O <= 8 (got H=%d O=%d)"
+                       : "fov_mix_decoder_fwd: the fused decoder supports H = 256, 32 or 64, O <= 8 (got H=%d O=%d)", H, O);
+        return FOV_ERR_UNSUPPORTED;
+    }
     if (!steps_ok("fov_mix_decoder_fwd", T_out, B)) return FOV_ERR_UNSUPPORTED;
+    if (tile && !mix_tile_shape_ok(B, T_out, H, O, false)) {
+        set_error("fov_mix_decoder_fwd: at H = 32 / 64 at most 2^30 sequences and steps (got B=%d T_out=%d)", B, T_out);
+        return FOV_ERR_UNSUPPORTED;
+    }
     if (B == 0 || T_out == 0) return FOV_OK;
-    if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_workspace_bytes(B, H))) return rc;
+    if (!tile)
+        if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_workspace_bytes(B, H))) return rc;
     MixDecParams p = {};
     p.K1 = dec1_K; p.R1 = dec1_R; p.b1 = dec1_b; p.R2 = dec2_R; p.b2 = dec2_b; p.Wd = dense_W; p.bd = dense_b; p.Wp = mix_Wp;
     p.oth_proj = oth_proj; p.oth_sb = (long)oth_batch_stride; p.oth_st = (long)oth_step_stride;
@@ -394,6 +406,10 @@ static int mix_decoder_fwd_impl(const float* dec0, const float* h1, const float*
     p.out = out; p.P = P; p.H1 = H1; p.C1 = C1; p.H2 = H2; p.C2 = C2; p.res1 = res1; p.res2 = res2;
     p.h1T = h1T; p.c1T = c1T; p.h2T = h2T; p.c2T = c2T;
     p.B = B; p.T_out = T_out; p.O = O;
+    if (tile) {   // the tapes are written one by one, each where its pointer is given: "all or none" was checked above
+        p.K2p = dec2_K;
+        return mix_tile_fwd_launch(p, H, act, (hipStream_t)stream);
+    }
     return bf16 ? mix_decoder_bf16_launch(p, dec2_K, act, ntrain == 7, workspace, (hipStream_t)stream)
                 : mix_decoder_launch(p, dec2_K, act, ntrain == 7, workspace, (hipStream_t)stream);
 }
@@ -438,18 +454,41 @@ static int mix_decoder_bwd_impl(const float* M, const float* P, const float* dlo
         set_error("fov_mix_decoder_bwd: invalid argument");
         return FOV_ERR_INVALID;
     }
-    if (H != 256 || O > 8) { set_error("fov_mix_decoder_bwd: the fused decoder supports H = 256, O <= 8"); return FOV_ERR_UNSUPPORTED; }
+    const bool tile = !bf16 && H == 32;   // one workgroup per tile (mix_tile.hip), no workspace
+    if (!bf16 && H == 64 && O <= 8) {
+        set_error("fov_mix_decoder_bwd: H = 64 has a one-launch forward only: the backward keeps three transposed (H,4H) matrices in LDS, "
+                  "192 KB at H = 64 (use the per-step entry points on the forward's tapes)");
+        return FOV_ERR_UNSUPPORTED;
+    }
+    if ((H != 256 && !tile) || O > 8) {
+        set_error(bf16 ? "fov_mix_decoder_bwd_bf16: the fused decoder supports H = 256, O <= 8 (got H=%d O=%d)"
+                       : "fov_mix_decoder_bwd: the fused decoder supports H = 256 or 32, O <= 8 (got H=%d O=%d)", H, O);
+        return FOV_ERR_UNSUPPORTED;
+    }
     if (!steps_ok("fov_mix_decoder_bwd", T_out, B)) return FOV_ERR_UNSUPPORTED;
+    if (tile && !mix_tile_shape_ok(B, T_out, H, O, true)) {
+        set_error("fov_mix_decoder_bwd: at H = 32 at most 2^30 sequences and steps (got B=%d T_out=%d)", B, T_out);
+        return FOV_ERR_UNSUPPORTED;
+    }
     if (B == 0 || T_out == 0) return FOV_OK;
-    if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_bwd_workspace_bytes(B, H))) return rc;
+    if (!tile)
+        if (int rc = check_ws(workspace, workspace_bytes, fov_mix_decoder_bwd_workspace_bytes(B, H))) return rc;
     MixDecBwdParams p = {};
     p.R1 = dec1_R; p.K1 = dec1_K; p.R2 = dec2_R; p.Wd = dense_W; p.Wp = mix_Wp;
     p.M = M; p.P = P; p.dloss = dloss; p.res1 = res1; p.res2 = res2; p.C1 = C1; p.C2 = C2;
     p.DZ1 = DZ1; p.DZ2 = DZ2; p.dpre_m = dpre_m; p.dpre_p = dpre_p;
     p.dh1_0 = dh1_0; p.dc1_0 = dc1_0; p.dh2_0 = dh2_0; p.dc2_0 = dc2_0;
     p.B = B; p.T_out = T_out; p.O = O;
+    if (tile) {
+        p.K2p = dec2_K;
+        return mix_tile_bwd_launch(p, act, (hipStream_t)stream);
+    }
     return bf16 ? mix_decoder_bwd_bf16_launch(p, dec2_K, act, workspace, (hipStream_t)stream)
                 : mix_decoder_bwd_launch(p, dec2_K, act, workspace, (hipStream_t)stream);
+}
+
+int fov_mix_decoder_tile_supported(int B, int T_out, int H, int O, int backward) {
+    return mix_tile_shape_ok(B, T_out, H, O, backward != 0) && steps_ok_quiet(T_out, B) ? 1 : 0;
 }
 
 int fov_mix_decoder_prepack(const float* dec2_K, void* workspace_fwd, size_t fwd_bytes, void* workspace_bwd, size_t bwd_bytes, int H,

@@ -285,6 +285,10 @@ struct MixDecBwdParams {
 size_t mix_decoder_bwd_workspace_bytes(int B);
 int mix_decoder_bwd_launch(MixDecBwdParams p, const float* K2, int act, void* workspace, hipStream_t stream);
 int mix_decoder_bwd_bf16_launch(MixDecBwdParams p, const float* K2, int act, void* workspace, hipStream_t stream);   // mix_decoder_bwd_bf16.hip
+// mix_tile.hip: the same decoder at H = 32 / 64 (the backward at H = 32), one workgroup per tile, no workspace; K2p = dec2_K as it is
+bool mix_tile_shape_ok(int B, int T_out, int H, int O, bool backward);
+int mix_tile_fwd_launch(const MixDecParams& p, int H, int act, hipStream_t stream);
+int mix_tile_bwd_launch(const MixDecBwdParams& p, int act, hipStream_t stream);
 
 // lstm_wide16.hip: two stacked width-512 layers as one launch (layer 2 a few steps behind layer 1 on other CUs)
 bool wide16_pair_shape(int B, int T, int F, int H);

@@ -33,7 +33,7 @@
 // of the forward's y; every wave contracts all 4 H gate columns itself (K1's fragments are 32 registers), so the feedback
 // needs no partial sums and no third barrier.  The next step's tape rows are loaded under the step's products: layer 2's,
 // dloss and y behind the first barrier, layer 1's behind the second.
-#include "stacked_tile.h"
+#include "selffed2_tile.h"
 
 namespace fov {
 
@@ -50,33 +50,6 @@ struct SelfFed2BwdParams {
     float *DPRE, *DZ1, *DZ2, *dx0, *dh1_0, *dc1_0, *dh2_0, *dc2_0;
     int B, T, O;
 };
-
-__host__ __device__ constexpr int s2_ldz(int HP) { return 4 * HP + 4; }
-// floats of the backward's LDS: R2^T, K2^T, R1^T in B-operand order, the dz tiles of the two layers
-__host__ __device__ constexpr int s2_bwd_lds_floats(int HP) { return 3 * HP * 4 * HP + 2 * SS_BT * s2_ldz(HP); }
-
-// the cell update of this lane's unit for its four sequences; h into the layer's tile of this step; the tape rows of step t
-template <int HP, int ACT>
-__device__ __forceinline__ void s2_cell(const f32x4 (&acc)[4], float (&c)[4], float (&h)[4], float* hw, float* Hs, float* Cs, float* RES,
-                                        int t, int B, int row0, int unit) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float ig = rec_act<ACT>(acc[0][r]), fg = rec_act<ACT>(acc[1][r]), gg = tanh_f(acc[2][r]), og = rec_act<ACT>(acc[3][r]);
-        c[r] = fmaf(fg, c[r], ig * gg);
-        h[r] = og * tanh_f(c[r]);
-        hw[r * ss_ldh(HP)] = h[r];
-        const int row = row0 + r;
-        if (row < B) {
-            const size_t at = ((size_t)(t + 1) * B + row) * HP + unit;
-            if (Hs) Hs[at] = h[r];
-            if (Cs) Cs[at] = c[r];
-            if (RES) {
-                float* q = RES + ((size_t)t * B + row) * 5 * HP + unit;
-                q[0] = ig; q[HP] = fg; q[2 * HP] = gg; q[3 * HP] = og; q[4 * HP] = c[r];
-            }
-        }
-    }
-}
 
 template <int HP, int ACT>
 __global__ __launch_bounds__(4 * HP, 1) void selffed2_fwd_kernel(SelfFed2FwdParams p) {
@@ -150,7 +123,7 @@ __global__ __launch_bounds__(4 * HP, 1) void selffed2_fwd_kernel(SelfFed2FwdPara
 #pragma unroll
             for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[r], wK1[r][g], acc[g], 0, 0, 0);
         mm_frag<NJ>(acc, a_rd + prv * HT, wR1);
-        s2_cell<HP, ACT>(acc, c1, h1, h_wr + cur * HT, p.H1, p.C1, p.RES1, t, B, b0 + 4 * g4, unit);
+        s2_cell<HP, ACT>(acc, c1, h1, h_wr + cur * HT, p.H1, p.C1, p.RES1, t, t + 1, B, b0 + 4 * g4, unit);
         __syncthreads();
         // the next step's context row, under layer 2 and the head
         float cn[4];
@@ -161,7 +134,7 @@ __global__ __launch_bounds__(4 * HP, 1) void selffed2_fwd_kernel(SelfFed2FwdPara
         for (int g = 0; g < 4; ++g) acc[g] = (f32x4){bias2[g], bias2[g], bias2[g], bias2[g]};
         mm_frag<NJ>(acc, a_rd + cur * HT, wK2);
         mm_frag<NJ>(acc, a_rd + (2 + prv) * HT, wR2);
-        s2_cell<HP, ACT>(acc, c2, h2, h_wr + (2 + cur) * HT, p.H2, p.C2, p.RES2, t, B, b0 + 4 * g4, unit);
+        s2_cell<HP, ACT>(acc, c2, h2, h_wr + (2 + cur) * HT, p.H2, p.C2, p.RES2, t, t + 1, B, b0 + 4 * g4, unit);
         __syncthreads();
         // ---- head: y_t = tanh(bd + h2_t . W + ctx_t), every wave for itself ----
         f32x4 yacc = {dbv[0], dbv[1], dbv[2], dbv[3]};
@@ -198,77 +171,6 @@ __global__ __launch_bounds__(4 * HP, 1) void selffed2_fwd_kernel(SelfFed2FwdPara
             if (p.cT) { p.cT[at] = c1[r]; p.cT[BH + at] = c2[r]; }
         }
     }
-}
-
-// one step's tape rows of one layer: gates, c_t, c_{t-1} of (row 4 g4 + r, unit)
-struct S2Tape { float gi[4], gf[4], gg[4], go[4], cc[4], cp[4]; };
-
-template <int HP>
-__device__ __forceinline__ void s2_load_tape(S2Tape& tp, const float* RES, const float* Cs, int t, int B, int row0, int unit) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = row0 + r;
-        const bool live = row < B;
-        const float* q = RES + ((size_t)t * B + row) * 5 * HP + unit;
-        tp.gi[r] = live ? q[0] : 0.f;
-        tp.gf[r] = live ? q[HP] : 0.f;
-        tp.gg[r] = live ? q[2 * HP] : 0.f;
-        tp.go[r] = live ? q[3 * HP] : 0.f;
-        tp.cc[r] = live ? q[4 * HP] : 0.f;
-        tp.cp[r] = live ? Cs[((size_t)t * B + row) * HP + unit] : 0.f;
-    }
-}
-
-// gate backward of this lane's unit for its four sequences; dz_t to the layer's tile and to the tape
-template <int HP, int ACT>
-__device__ __forceinline__ void s2_gate_bwd(const S2Tape& tp, const f32x4& dh, float (&dc)[4], float* zt, float* DZ, int t, int B, int row0,
-                                            int unit) {
-    constexpr int H4 = 4 * HP, LDZ = s2_ldz(HP);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float tc = tanh_f(tp.cc[r]);
-        const float dov = dh[r] * tc;
-        const float dcv = dc[r] + dh[r] * tp.go[r] * (1.f - tc * tc);
-        float dz[4];
-        dz[0] = dcv * tp.gg[r] * rec_act_grad<ACT>(tp.gi[r]);
-        dz[1] = dcv * tp.cp[r] * rec_act_grad<ACT>(tp.gf[r]);
-        dz[2] = dcv * tp.gi[r] * (1.f - tp.gg[r] * tp.gg[r]);
-        dz[3] = dov * rec_act_grad<ACT>(tp.go[r]);
-        dc[r] = dcv * tp.gf[r];
-        const int row = row0 + r;
-        float* zg = DZ + ((size_t)t * B + row) * H4 + unit;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            zt[r * LDZ + g * HP] = dz[g];
-            if (row < B) zg[g * HP] = dz[g];
-        }
-    }
-}
-
-// a (HP, 4 HP) matrix M into LDS as the B operand of dz . M^T: this wave's slice [NJ4][64] {s = 0..3} = M[16 w + n][16 jj + 4 g4 + s].
-// Here the lane is (n, s): four consecutive floats of a row of M are one lane's b128 later.
-template <int HP>
-__device__ __forceinline__ void s2_stage_bt(f32x4* dst4, const float* M, int unit, int n, int g4) {
-    constexpr int H4 = 4 * HP;
-    const float* row = M + (size_t)unit * H4;
-    float* dst = (float*)dst4;
-    for (int q = 0; q < H4 / 4; ++q) dst[(q * 16 + n) * 4 + g4] = row[4 * q + g4];
-}
-
-// dz . M^T for this wave's 16 units: four accumulators, summed in a fixed order
-template <int NJ4>
-__device__ __forceinline__ f32x4 s2_mm_bt(const float* zr, const f32x4* bt) {
-    f32x4 a4[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a4[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int jj = 0; jj < NJ4; ++jj) {
-        const f32x4 zv = *(const f32x4*)(zr + 16 * jj);
-        const f32x4 rv = bt[jj * 64];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a4[jj & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv[s], rv[s], a4[jj & 3], 0, 0, 0);
-    }
-    return (a4[0] + a4[1]) + (a4[2] + a4[3]);
 }
 
 template <int HP, int ACT>

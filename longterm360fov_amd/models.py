@@ -1612,13 +1612,21 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         return [batch["enc"], batch["others"], batch["dec_in"]]
 
     def __init__(self, num_encoder_tokens=None, num_decoder_tokens=6, latent_dim=32, num_user=34,
-                 recurrent_activation=None, seed=None, impl="auto", device="cuda", dtype="f32"):
+                 recurrent_activation=None, seed=None, impl="auto", device="cuda", dtype="f32", native_width=False):
         """dtype 'bf16' (BASELINE configs[4], latent_dim = 256 only): gate GEMMs and the Dense head take bf16
-        operands on the matrix cores; accumulation, gates, cell state and the weights the optimizer updates stay fp32."""
+        operands on the matrix cores; accumulation, gates, cell state and the weights the optimizer updates stay fp32.
+        native_width (opt-in; latent_dim 32 or 64, fp32, impl 'auto', at most 8 decoder tokens): the model runs at its own width
+        on the one-workgroup-per-tile kernels - the encoder stack in one launch, the whole unrolled decoder in one launch - and
+        trains on an unpadded OthersMixingTrainer(tile_decoder=True), instead of zero-padded to 256 on the exchange kernels."""
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
         if dtype == "bf16" and int(latent_dim) != 256:
             raise ValueError("the bf16 path is built for latent_dim = 256")
+        if native_width and (int(latent_dim) not in (32, 64) or dtype != "f32" or impl != "auto" or int(num_decoder_tokens) > 8):
+            raise ValueError("native_width needs latent_dim 32 or 64, dtype 'f32', impl 'auto' and num_decoder_tokens <= 8 "
+                             "(got latent_dim=%d dtype=%r impl=%r num_decoder_tokens=%d)"
+                             % (int(latent_dim), dtype, impl, int(num_decoder_tokens)))
+        self.native_width = bool(native_width)
         self.dtype = dtype
         self.num_encoder_tokens = 3 * cfg.fps if num_encoder_tokens is None else int(num_encoder_tokens)
         self.num_decoder_tokens = int(num_decoder_tokens)
@@ -1638,8 +1646,8 @@ class OthersMixingSeq2Seq(KerasModelSurface):
     def _make_trainer(self, optimizer):
         from .training import OthersMixingTrainer, PaddedTrainer
         make = lambda w: OthersMixingTrainer(w, act=self.recurrent_activation, impl=self.impl, optimizer=optimizer, lr=self._lr,
-                                             device=self.device, dtype=self.dtype)
-        Hp = self._run_width()
+                                             device=self.device, dtype=self.dtype, tile_decoder=self.native_width)
+        Hp = self._run_width()           # native_width: latent_dim itself, so the trainer below is the plain one on the model's weights
         if Hp != self.latent_dim:      # the script's latent_dim = 32: the fused H = 256 kernels on zero-padded weights (exact)
             return PaddedTrainer(make, self._w, self.latent_dim, Hp, hidden_inputs=("enc2_K", "dec2_K"))
         return make(self._w)
@@ -1649,7 +1657,7 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         so the prediction takes the fused path (wide-input layer kernel + ONE decoder launch) instead of per-step
         launches on the generic kernels - 8x the arithmetic at H = 32 and still far faster."""
         H = self.latent_dim
-        if self.impl == "generic" or H >= 256 or not self.fused_decoder:
+        if self.impl == "generic" or H >= 256 or not self.fused_decoder or self.native_width:
             return H
         return 256
 
@@ -1696,8 +1704,19 @@ class OthersMixingSeq2Seq(KerasModelSurface):
             out = torch.empty((T_out, B, O), dtype=torch.float32, device=self.device)
             ops.mix_decoder(xin, h1, c1, h2, c2, oth_proj, dw, dw["mix_W_pred"], T_out, act=act, workspace=ws, out=out, dtype="bf16")
             return out.transpose(0, 1)
-        hs1, h1, c1 = ops.lstm_seq(e, dw["enc1_K"], dw["enc1_R"], dw["enc1_b"], act=act, impl=impl, workspace=ws)
-        if H == 256 and impl != "generic":   # layer 2 over the 256-wide sequence: K2 and R2 register-resident
+        tile = self.native_width
+        enc_tile = tile and ops.stacked_seq2seq_train_supported(B, T_in, 0, e.shape[2], O, H, 2)
+        if enc_tile:
+            # native width: both encoder layers in one launch (the stacked forward with no decoder step), only the final states leave
+            sw = {"%s%d_%s" % (side, l, k): dw["%s%d_%s" % (side, l + 1, k)] for side in ("enc", "dec") for l in (0, 1) for k in "KRb"}
+            hT, cT = (torch.empty((2, B, H), dtype=torch.float32, device=self.device) for _ in range(2))
+            ops.stacked_seq2seq_train_fwd(e, e.new_empty((B, 0, O)), sw, 2, act=act, tape=False, out={"hT": hT, "cT": cT})
+            (h1, h2), (c1, c2) = hT, cT
+        else:
+            hs1, h1, c1 = ops.lstm_seq(e, dw["enc1_K"], dw["enc1_R"], dw["enc1_b"], act=act, impl=impl, workspace=ws)
+        if enc_tile:
+            pass
+        elif H == 256 and impl != "generic":   # layer 2 over the 256-wide sequence: K2 and R2 register-resident
             _, h2, c2 = ops.lstm_seq(hs1, dw["enc2_K"], dw["enc2_R"], dw["enc2_b"], act=act, impl=impl,
                                      return_sequences=False, workspace=ws)
         else:                                # other widths: input projection as a GEMM, then the layer on zx
@@ -1706,8 +1725,8 @@ class OthersMixingSeq2Seq(KerasModelSurface):
         # others half of the mixing layer for every step at once (bias folded in)
         oth_proj = ops.dense(oth.reshape(B * T_out, -1), dw["mix_W_oth"], dw["mix_b"], activation=None).reshape(B, T_out, O)
         out = torch.empty((T_out, B, O), dtype=torch.float32, device=self.device)   # step-major: row t = m_t
-        if self.fused_decoder and ops.mix_decoder_supported(H, O):
-            # the whole unrolled decoder + mixing head in one persistent launch
+        if self.fused_decoder and (ops.mix_decoder_supported(H, O) or (tile and ops.mix_decoder_tile_supported(B, T_out, H, O))):
+            # the whole unrolled decoder + mixing head in one launch: persistent at H = 256, one workgroup per tile at the native widths
             ops.mix_decoder(xin, h1, c1, h2, c2, oth_proj, dw, dw["mix_W_pred"], T_out, act=act, workspace=ws, out=out)
             return out.transpose(0, 1)
         p = torch.empty((B, O), dtype=torch.float32, device=self.device)

@@ -502,8 +502,9 @@ def stacked_seq2seq_train_fwd(enc_in, dec_in, w, num_layers, act="sigmoid", tape
     """The L-layer encoder and the L-layer teacher-forced decoder of Fov_seq2seq_2layers.py:232-272 / 3layers.py in one launch
     (the Dense head is the caller's).  w: enc{l}_K/R/b, dec{l}_K/R/b at the run width.  tape=True -> dict enc_hs (L,B,T_in,H),
     enc_res (L,B,T_in,5,H), dec_hs (L,B,T_out,H), dec_res (L,B,T_out,5,H), hT, cT (L,B,H); its `top` is dec_hs[L-1].  tape=False
-    -> dict with `top` (B,T_out,H) alone: the inference forward.  out: a dict of preallocated tensors under the same names.
-    No workspace."""
+    -> dict with `top` (B,T_out,H) alone: the inference forward; hT / cT (L,B,H) handed in through `out` are written there too (with
+    T_out = 0 that is the encoder stack alone, only its final states leaving).  out: a dict of preallocated tensors under the same
+    names.  No workspace."""
     enc_in, dec_in = _dev(enc_in, "enc_in"), _dev(dec_in, "dec_in")
     L_ = int(num_layers)
     B, T_in, F_enc = enc_in.shape
@@ -516,6 +517,8 @@ def stacked_seq2seq_train_fwd(enc_in, dec_in, w, num_layers, act="sigmoid", tape
                 and w["%s%d_b" % (side, l)].shape == (4 * H,), "%s%d" % (side, l)
     shapes = {"enc_hs": (L_, B, T_in, H), "enc_res": (L_, B, T_in, 5, H), "dec_hs": (L_, B, T_out, H), "dec_res": (L_, B, T_out, 5, H),
               "hT": (L_, B, H), "cT": (L_, B, H)} if tape else {"top": (B, T_out, H)}
+    if not tape and out is not None:
+        shapes.update({k: (L_, B, H) for k in ("hT", "cT") if out.get(k) is not None})
     t = {}
     for k, s_ in shapes.items():
         t[k] = torch.empty(s_, dtype=torch.float32, device=enc_in.device) if out is None or out.get(k) is None else out[k]
@@ -1314,6 +1317,12 @@ def dense_add(x, W, b, add, activation="tanh", out=None):
 
 def mix_decoder_supported(H, O):
     return H == 256 and O <= 8
+
+
+def mix_decoder_tile_supported(B, T_out, H, O, backward=False):
+    """Shapes at which mix_decoder (backward=False: H = 32 or 64) / mix_decoder_bwd (backward=True: H = 32) run the
+    one-workgroup-per-tile kernels, fp32, 1 <= O <= 8, no workspace.  Arithmetic only: answers on a machine without a GPU."""
+    return bool(_lib.lib().fov_mix_decoder_tile_supported(B, T_out, H, O, 1 if backward else 0))
 
 
 def mix_decoder(dec0, h1, c1, h2, c2, oth_proj, w, mix_Wp, T_out, act="sigmoid", workspace=None, out=None, train=None,

@@ -1207,15 +1207,27 @@ class OthersMixingTrainer(FlatParamTrainer):
     fused_decoder = True       # H = 256: forward of the unrolled decoder as ONE launch; False = step-wise calls
     fused_decoder_bwd = True   # H = 256: BPTT through the unrolled decoder as ONE launch; False = step-wise calls
 
-    def __init__(self, weights, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda", dtype="f32"):
+    tile_decoder = False       # H = 32 / 64 at the model's own width: the one-workgroup-per-tile kernels (opt-in, see __init__)
+
+    def __init__(self, weights, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda", dtype="f32", tile_decoder=False):
         """dtype 'bf16' (BASELINE configs[4], H = 256): forward and backward matrix products take bf16 operands on the
         matrix cores with fp32 accumulation; gates, cell state, tapes, gradients' accumulation, the flat parameter
-        buffer and the optimizer stay fp32 (fp32 master weights)."""
+        buffer and the optimizer stay fp32 (fp32 master weights).
+        tile_decoder (fp32, H = 32 or 64, the script's own latent_dim and twice it): the unrolled decoder's forward is ONE
+        launch at that width (fov_mix_decoder_fwd's one-workgroup-per-tile kernel, the same tapes), its BPTT one launch at H = 32
+        and the step-wise walk over the fused forward's tapes at H = 64, and the two encoder layers are one launch
+        (ops.stacked_seq2seq_train_fwd with T_out = 0) where that call takes the shape.  fused_decoder / fused_decoder_bwd = False
+        still select the step-wise calls.  Weight gradients, the encoder's BPTT, the optimizer and the data-parallel path are
+        the same calls as without it."""
         assert dtype in ("f32", "bf16")
         self.act, self.impl, self.dtype = act, impl, dtype
         self._alloc(weights, _MIX_ORDER, optimizer, lr, device)
         if dtype == "bf16":
             assert self.w["enc1_R"].shape[0] == 256, "the bf16 path is built for H = 256"
+        if tile_decoder:
+            assert dtype == "f32", "tile_decoder is fp32 only"
+            assert self.w["enc1_R"].shape[0] in (32, 64), "tile_decoder is built for H = 32 and H = 64"
+        self.tile_decoder = bool(tile_decoder)
         self.ws_bwd = ops.Workspace()   # granule mailboxes of the fused decoder backward
 
     def forward_backward(self, enc, others, dec0, target, grad_weight=1.0):
@@ -1237,8 +1249,10 @@ class OthersMixingTrainer(FlatParamTrainer):
         # What depends on the inputs and the weights alone - the others' projection, the decoder's first input row, the fp32
         # fused kernels' packed copy of dec2_K - runs on the SIDE stream while the encoder layers run here (four launches of
         # 5-7 us each that used to sit between the encoder and the decoder).  Outputs are allocated on this stream.
-        fused = self.fused_decoder and ops.mix_decoder_supported(H, O)
-        fused_bwd = self.fused_decoder_bwd and ops.mix_decoder_supported(H, O)
+        wide = ops.mix_decoder_supported(H, O)                 # H = 256: the persistent kernels, their packed dec2_K
+        tile = self.tile_decoder and dt == "f32" and impl != "generic"   # impl = generic never reaches the tile kernels
+        fused = self.fused_decoder and (wide or (tile and ops.mix_decoder_tile_supported(B, T_out, H, O)))
+        fused_bwd = self.fused_decoder_bwd and (wide or (tile and ops.mix_decoder_tile_supported(B, T_out, H, O, backward=True)))
         XM = e(T_out + 1, B, O)                               # row t = decoder input x_t, row t+1 = output m_t
         oth_proj_buf = e(B * T_out, O)
         oth_flat = others.reshape(B * T_out, n_oth)
@@ -1247,7 +1261,7 @@ class OthersMixingTrainer(FlatParamTrainer):
         def input_side_work():
             ops.dense(oth_flat, Wm_o_c, w["mix_b"], activation=None, out=oth_proj_buf)
             XM[0].copy_(dec0.reshape(B, O))
-            if dt != "bf16" and (fused or fused_bwd):
+            if dt != "bf16" and wide and (fused or fused_bwd):
                 ops.mix_decoder_prepack(w["dec2_K"], B, H, ws if fused else None, self.ws_bwd if fused_bwd else None)
         side_in = self._wgrad_side_stream() if (B, T_in, T_out, dt) in self._side_warm else None
         if side_in is not None:
@@ -1255,14 +1269,25 @@ class OthersMixingTrainer(FlatParamTrainer):
             with torch.cuda.stream(side_in):
                 input_side_work()
         stacked = dt == "bf16" and impl != "generic" and ops.lstm_stack2_bf16_supported(B, T_in, enc.shape[2], H)
-        if stacked:   # both encoder layers as ONE wavefront launch (layer 2 one step behind layer 1 on the same CUs): same tensors
+        # tile_decoder: both encoder layers in one launch of the stacked training forward with no decoder step; slice l of its
+        # tapes is layer l's lstm_seq_bwd operand.  Its final states come as (2,B,H) blocks: four (B,H) copies put them into row 0
+        # of the state stacks, where the weight-gradient products and the BPTT read them.
+        enc_tile = tile and ops.stacked_seq2seq_train_supported(B, T_in, 0, enc.shape[2], O, H, 2)
+        if enc_tile:
+            sw = {"%s%d_%s" % (side, l, k): w["%s%d_%s" % (side, l + 1, k)] for side in ("enc", "dec") for l in (0, 1) for k in "KRb"}
+            tp = ops.stacked_seq2seq_train_fwd(enc, enc.new_empty((B, 0, O)), sw, 2, act=act)
+            (hs1, hs2), (res1, res2) = tp["enc_hs"], tp["enc_res"]
+            for l, (Hs, Cs) in enumerate(((H1, C1), (H2, C2))):
+                Hs[0].copy_(tp["hT"][l])
+                Cs[0].copy_(tp["cT"][l])
+        elif stacked:   # both encoder layers as ONE wavefront launch (layer 2 one step behind layer 1 on the same CUs): same tensors
             (hs1, h1, c1, res1), (hs2, h2, c2, res2) = ops.lstm_stack2_bf16(
                 enc, (w["enc1_K"], w["enc1_R"], w["enc1_b"]), (w["enc2_K"], w["enc2_R"], w["enc2_b"]), act=act, workspace=ws,
                 out1=(e(B, T_in, H), H1[0], C1[0], e(B, T_in, 5, H)), out2=(e(B, T_in, H), H2[0], C2[0], e(B, T_in, 5, H)))
         else:
             hs1, h1, c1, res1 = ops.lstm_seq_train(enc, w["enc1_K"], w["enc1_R"], w["enc1_b"], act=act, impl=impl, workspace=ws,
                                                    out=(e(B, T_in, H), H1[0], C1[0], e(B, T_in, 5, H)), dtype=dt)
-        if stacked:
+        if stacked or enc_tile:
             pass
         elif H == 256 and impl != "generic":   # layer 2 over the 256-wide sequence: K2 and R2 register-resident
             hs2, h2, c2, res2 = ops.lstm_seq_train(hs1, w["enc2_K"], w["enc2_R"], w["enc2_b"], act=act, impl=impl, workspace=ws,
