@@ -1910,3 +1910,279 @@ def selffed_backward(tapes, dloss, K, R, W, act, dact, mistake=None):
         DY[t], DPRE[t], DZ[t] = dy, dpre, dz
         dhR, dx = dz @ R.T, dz @ K.T
     return {"DY": DY, "DPRE": DPRE, "DZ": DZ, "dx0": dx, "dh0": dhR, "dc0": dc}
+
+
+# --------------------------------------------------------------------------------------
+# The tile kernels that train: the self-fed two-layer decoder (fov_selffed2_decoder_fwd / _bwd), the others-mixing decoder at
+# H = 32 / 64 (fov_mix_decoder_fwd / _bwd) and the stacked model's training graph (fov_stacked_seq2seq_train_fwd / _bwd) in the
+# value regimes above: restatements of the entry points' loops with every tape, the BPTT written out on GIVEN tapes, and
+# `mistake`: a named way of being wrong on purpose (finite, plausible), with which the host tests show what the GPU checks see.
+# --------------------------------------------------------------------------------------
+SELFFED2_STATES = ("h1_0", "c1_0", "h2_0", "c2_0")
+SELFFED2_TAPES = ("H1", "C1", "H2", "C2", "XY", "RES1", "RES2")
+SELFFED2_GRADS = ("DPRE", "DZ1", "DZ2", "dx0", "dh1_0", "dc1_0", "dh2_0", "dc2_0")
+SELFFED2_MISTAKES = ("ctx of step t + 1 at step t", "layer 2 reads h1 of the previous parity", "feedback gradient dropped",
+                     "c_prev one step late", "dz2 . K2^T left out of dh1")
+TILE_HEAD_BIAS = (12.0, 0.3, -0.3, -12.0, 0.5, -3.0)   # the arguments of a fed-back tanh: a third at least at +-1 (both signs from O = 4
+# on), more than a third on the slope, one near -1: at O = 3 .. 6 at least 0.30 of them lie beyond +-9 and 0.30 inside +-1
+
+
+def _cell(z, c, act, H):
+    s = _rec_act(act)
+    i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
+    c = f * c + i * g
+    return o * np.tanh(c), c, np.stack([i, f, g, o, c], 1)
+
+
+def _gates_bwd(res, c_prev, dh, dc, act):
+    """The cell's pointwise backward from the stored (i, f, g, o, c) (B,5,H) -> (dz (B,4H), dc for the step below)."""
+    i, f, g, o, c = (res[:, k] for k in range(5))
+    tc = np.tanh(c)
+    dcv = dc + dh * o * (1 - tc * tc)
+    dz = np.concatenate([dcv * g * _rec_act_grad(i, act), dcv * c_prev * _rec_act_grad(f, act), dcv * i * (1 - g * g),
+                         dh * tc * _rec_act_grad(o, act)], 1)
+    return dz, dcv * f
+
+
+def selffed2_forward(x0, st, w, T, act, dt=np.float64, mistake=None):
+    """fov_selffed2_decoder_fwd's loop in dtype dt (z = b + x . K + h . R; the head bd + h2 . W + ctx_t, in this order) -> (every
+    output in the entry point's layout plus z1, z2 (T,B,4H) and pre (T,B,O), the distance of the nearest hard_sigmoid
+    pre-activation from +-2.5).  w: dec1_K .. dec2_b, W and, optionally, bd (O,) and ctx (B,T,O); st: SELFFED2_STATES, None = zero.
+    mistake: the head of step t takes ctx of step t + 1 (zero behind the last); layer 2 reads h1 of the step before."""
+    assert mistake is None or mistake in SELFFED2_MISTAKES
+    w = {k: np.asarray(v, dt) for k, v in w.items()}
+    B, O_ = x0.shape
+    H = w["dec1_R"].shape[0]
+    z0 = np.zeros((B, H), dt)
+    h1, c1, h2, c2 = (z0 if st.get(k) is None else np.asarray(st[k], dt) for k in SELFFED2_STATES)
+    x = np.asarray(x0, dt)
+    tp = {"H1": [h1], "C1": [c1], "H2": [h2], "C2": [c2], "XY": [x], "RES1": [], "RES2": [], "z1": [], "z2": [], "pre": []}
+    for t in range(T):
+        z1 = (w["dec1_b"] + x @ w["dec1_K"]) + h1 @ w["dec1_R"]
+        h1_prev = h1
+        h1, c1, r1 = _cell(z1, c1, act, H)
+        below = h1_prev if mistake == "layer 2 reads h1 of the previous parity" else h1
+        z2 = (w["dec2_b"] + below @ w["dec2_K"]) + h2 @ w["dec2_R"]
+        h2, c2, r2 = _cell(z2, c2, act, H)
+        p = h2 @ w["W"]
+        if "bd" in w:
+            p = w["bd"] + p
+        if "ctx" in w:
+            if mistake != "ctx of step t + 1 at step t":
+                p = p + w["ctx"][:, t]
+            elif t + 1 < T:
+                p = p + w["ctx"][:, t + 1]
+        x = np.tanh(p)
+        for k, v in (("H1", h1), ("C1", c1), ("H2", h2), ("C2", c2), ("XY", x), ("RES1", r1[:, None]), ("RES2", r2[:, None]),
+                     ("z1", z1), ("z2", z2), ("pre", p)):
+            tp[k].append(v)
+    empty = {"RES1": (0, B, 1, 5, H), "RES2": (0, B, 1, 5, H), "z1": (0, B, 4 * H), "z2": (0, B, 4 * H), "pre": (0, B, O_)}
+    out = {k: np.stack(v).astype(dt) if v else np.zeros(empty[k], dt) for k, v in tp.items()}
+    out["y"] = np.ascontiguousarray(out["XY"][1:].transpose(1, 0, 2))
+    out["hT"], out["cT"] = np.stack([h1, h2]).astype(dt), np.stack([c1, c2]).astype(dt)
+    margin = np.inf
+    if act_code(act) == ACT_HARD_SIGMOID:
+        for z in tp["z1"] + tp["z2"]:
+            gates = np.concatenate([z[:, :2 * H], z[:, 3 * H:]], 1)
+            margin = min(margin, float(np.abs(np.abs(gates) - 2.5).min()))
+    return out, margin
+
+
+def selffed2_backward(tp, dloss, w, act, dt=np.float64, mistake=None):
+    """fov_selffed2_decoder_bwd's loop in dtype dt on GIVEN tapes (C1, C2, XY, RES1, RES2) -> SELFFED2_GRADS.
+    mistake: dy_t = dloss_t alone; c_{t-1} read from row t + 1 of C1 / C2; dh1 without dz2 . K2^T."""
+    assert mistake is None or mistake in SELFFED2_MISTAKES
+    w = {k: np.asarray(v, dt) for k, v in w.items()}
+    dloss = np.asarray(dloss, dt)
+    T, B, O_ = dloss.shape
+    H = w["dec1_R"].shape[0]
+    tp = {k: np.asarray(tp[k], dtype=dt) for k in ("C1", "C2", "XY", "RES1", "RES2")}
+    late = int(mistake == "c_prev one step late")
+    out = {"DPRE": np.zeros((T, B, O_), dt), "DZ1": np.zeros((T, B, 4 * H), dt), "DZ2": np.zeros((T, B, 4 * H), dt)}
+    dx, dz1, dz2 = np.zeros((B, O_), dt), np.zeros((B, 4 * H), dt), np.zeros((B, 4 * H), dt)
+    dc1, dc2 = np.zeros((B, H), dt), np.zeros((B, H), dt)
+    for t in range(T - 1, -1, -1):
+        y = tp["XY"][t + 1]
+        dy = dloss[t] if mistake == "feedback gradient dropped" else dloss[t] + dx
+        dpre = dy * (1 - y * y)
+        dh2 = dpre @ w["W"].T + dz2 @ w["dec2_R"].T
+        dz2, dc2 = _gates_bwd(tp["RES2"][t][:, 0], tp["C2"][t + late], dh2, dc2, act)
+        dh1 = dz1 @ w["dec1_R"].T
+        if mistake != "dz2 . K2^T left out of dh1":
+            dh1 = dz2 @ w["dec2_K"].T + dh1
+        dz1, dc1 = _gates_bwd(tp["RES1"][t][:, 0], tp["C1"][t + late], dh1, dc1, act)
+        dx = dz1 @ w["dec1_K"].T
+        out["DPRE"][t], out["DZ1"][t], out["DZ2"][t] = dpre, dz1, dz2
+    out.update(dx0=dx, dh1_0=dz1 @ w["dec1_R"].T, dc1_0=dc1, dh2_0=dz2 @ w["dec2_R"].T, dc2_0=dc2)
+    return out
+
+
+def _two_layer_regime(rng, regime, H, O, B, dtype):
+    """Both layers of a self-fed two-layer decoder in `regime`: each reads a computed input (xk = 0.25).  -> (w, states)."""
+    w = {}
+    w["dec1_K"], w["dec1_R"], w["dec1_b"] = regime_layer(rng, O, H, regime, 0.8, 1.0, None, dtype, xk=0.25)
+    w["dec2_K"], w["dec2_R"], w["dec2_b"] = regime_layer(rng, H, H, regime, 0.5, 1.0, None, dtype, xk=0.25)
+    if regime == "R4":          # the accumulating regime starts from the zero state
+        st = [np.zeros((B, H), dtype) for _ in range(4)]
+    else:
+        st = list(regime_state(rng, B, w["dec1_b"], regime, dtype) + regime_state(rng, B, w["dec2_b"], regime, dtype))
+    return w, st
+
+
+def regime_selffed2(seed, regime, H, O, B, T, bd=True, dtype=np.float32):
+    """The self-fed two-layer decoder's inputs with both layers in `regime` and a saturating head (_regime_head's W; the arguments
+    of the fed-back tanh sit at TILE_HEAD_BIAS, on bd + ctx together when bd is given, on ctx alone else)
+    -> dict(w (with W, ctx and perhaps bd), x0 (B,O), st {name: (B,H) or None: R4 starts from the zero state}, dloss (T,B,O), act,
+    regime).  R3 reaches LAYER 1 AND THE HEAD (regime_mix_decoder's): row 9's first input is +-500, row 3's context is scaled by
+    100; extreme = (3, 9), and x0_calm / ctx_calm hold the two rows ordinary."""
+    rng = np.random.default_rng(seed)
+    w, st = _two_layer_regime(rng, regime, H, O, B, dtype)
+    w["W"], bias = _regime_head(rng, H, O, dtype)
+    want = np.resize(np.array(TILE_HEAD_BIAS), O)
+    ctx = 0.1 * rng.standard_normal((B, T, O))
+    if bd:
+        w["bd"] = bias
+        ctx = ctx + (want - bias.astype(np.float64))
+    else:
+        ctx = ctx + want
+    w["ctx"] = ctx.astype(dtype)
+    p = {"w": w, "x0": rng.uniform(-1, 1, (B, O)).astype(dtype), "dloss": rng.standard_normal((T, B, O)).astype(dtype),
+         "st": dict(zip(SELFFED2_STATES, [None] * 4 if regime == "R4" else st)), "act": REGIME_ACT[regime], "regime": regime}
+    if regime == "R3":
+        assert B > 16
+        p["extreme"], p["x0_calm"], p["ctx_calm"] = np.array([3, 9]), p["x0"].copy(), w["ctx"].copy()
+        w["ctx"][3] *= 100.0
+        p["x0"][9] = np.where(p["x0"][9] < 0, -500.0, 500.0)
+    return p
+
+
+MIX_TILE_TAPES = ("M", "P", "H1", "C1", "H2", "C2", "res1", "res2")
+MIX_TILE_GRADS = ("DZ1", "DZ2", "dpre_m", "dpre_p", "dh1_0", "dc1_0", "dh2_0", "dc2_0")
+MIX_TILE_MISTAKES = ("mix_Wp transposed", "oth_proj of step t + 1 at step t", "dp without 1 - p^2", "feedback gradient dropped",
+                     "c_prev one step late")
+
+
+def mix_tile_forward(dec0, st, oth_proj, w, mix_Wp, T, act, dt=np.float64, mistake=None):
+    """mix_decoder_train_forward in dtype dt -> its tapes.  mistake: m_t = tanh(p_t . mix_Wp^T + ..); the mixing tanh of step t
+    takes the others' projection of step t + 1 (zero behind the last)."""
+    assert mistake is None or mistake in MIX_TILE_MISTAKES
+    c_ = lambda a: np.asarray(a, dt)
+    Wp, oth = c_(mix_Wp), c_(oth_proj)
+    if mistake == "mix_Wp transposed":
+        Wp = Wp.T
+    if mistake == "oth_proj of step t + 1 at step t":
+        oth = np.concatenate([oth[:, 1:], np.zeros_like(oth[:, :1])], axis=1)
+    return mix_decoder_train_forward(c_(dec0), *[c_(s) for s in st], oth, {k: c_(v) for k, v in w.items()}, Wp, T, act=act)
+
+
+def mix_tile_backward(tape, dloss, w, mix_Wp, act, dt=np.float64, mistake=None):
+    """mix_decoder_backward in dtype dt on GIVEN tapes (M, P, res1, res2 and C1s, C2s: row t = the cell state BEFORE step t).
+    mistake: dpp_t = dm_t . mix_Wp^T without (1 - p_t^2) (P read as zero); dm_t = dloss_t alone (M read as +-1: the feedback term
+    vanishes); c_{t-1} read from row t + 1."""
+    assert mistake is None or mistake in MIX_TILE_MISTAKES
+    c_ = lambda a: np.asarray(a, dt)
+    M, P, C1, C2 = c_(tape["M"]), c_(tape["P"]), c_(tape["C1s"]), c_(tape["C2s"])
+    if mistake == "dp without 1 - p^2":
+        P = np.zeros_like(P)
+    if mistake == "feedback gradient dropped":
+        M = np.ones_like(M)
+    if mistake == "c_prev one step late":
+        C1, C2 = (np.concatenate([C[1:T_], c_(tape[r])[T_ - 1:, :, 4]]) for C, r, T_ in ((C1, "res1", M.shape[0]), (C2, "res2", M.shape[0])))
+    return mix_decoder_backward(M, P, c_(dloss), c_(tape["res1"]), c_(tape["res2"]), C1, C2, {k: c_(v) for k, v in w.items()}, c_(mix_Wp),
+                                act=act)
+
+
+def regime_mix_tile(seed, regime, H, O, B, T, dtype=np.float32):
+    """The others-mixing decoder's inputs at a tile width with both layers in `regime`, _regime_head's Dense head and a mixing
+    stage whose arguments sit at TILE_HEAD_BIAS (on the others' projection; mix_Wp at gain 0.15, so the slope outputs stay on the
+    slope) -> dict(w, mix_Wp, st [h1, c1, h2, c2] (zeros in R4), dec0 (B,O), oth (B,T,O), G (T,B,O), act, regime).  R3 as
+    regime_mix_decoder: row 9's first input is +-500, row 3's projection is scaled by 100; extreme, dec0_calm, oth_calm."""
+    rng = np.random.default_rng(seed)
+    w, st = _two_layer_regime(rng, regime, H, O, B, dtype)
+    w["dense_W"], w["dense_b"] = _regime_head(rng, H, O, dtype)
+    p = {"w": w, "mix_Wp": (0.15 * rng.standard_normal((O, O))).astype(dtype), "st": st, "dec0": rng.uniform(-1, 1, (B, O)).astype(dtype),
+         "oth": (np.resize(np.array(TILE_HEAD_BIAS), O) + 0.1 * rng.standard_normal((B, T, O))).astype(dtype),
+         "G": rng.standard_normal((T, B, O)).astype(dtype), "act": REGIME_ACT[regime], "regime": regime}
+    if regime == "R3":
+        assert B > 16
+        p["extreme"], p["dec0_calm"], p["oth_calm"] = np.array([3, 9]), p["dec0"].copy(), p["oth"].copy()
+        p["oth"][3] *= 100.0
+        p["dec0"][9] = np.where(p["dec0"][9] < 0, -500.0, 500.0)
+    return p
+
+
+STACKED_TRAIN_TAPES = ("enc_hs", "enc_res", "dec_hs", "dec_res", "hT", "cT")
+STACKED_TRAIN_MISTAKES = ("decoder layer l seeded from encoder layer l - 1", "partial k-block dropped", "decoder input rows 0..3",
+                          "dx of the layer above dropped", "c_prev one step late", "decoder dc_0 not handed to the encoder")
+
+
+def stacked_train_forward(w, enc, dec_in, L, act, dt=np.float64, mistake=None):
+    """fov_stacked_seq2seq_train_fwd in dtype dt -> dict(enc_hs (L,B,T_in,H), enc_res (L,B,T_in,5,H), dec_hs, dec_res, hT, cT
+    (L,B,H), z_enc / z_dec [l] (B,T,4H)).  mistake: decoder layer l starts from encoder layer l - 1's state (layer 0 from the top
+    one's); the encoder drops the partial last 16-row block of x . enc0_K; the decoder's layer 0 contracts input rows 0..3 only."""
+    assert mistake is None or mistake in STACKED_TRAIN_MISTAKES
+    c_ = lambda a: np.asarray(a, dt)
+    w = {k: c_(v) for k, v in w.items()}
+    enc, dec_in = c_(enc), c_(dec_in)
+    F, O = enc.shape[2], dec_in.shape[2]
+    f_rows = F // 16 * 16 if mistake == "partial k-block dropped" else F
+    o_rows = min(O, 4) if mistake == "decoder input rows 0..3" else O
+    out = {k: [] for k in STACKED_TRAIN_TAPES + ("z_enc", "z_dec")}
+    x, state = enc[:, :, :f_rows], []
+    for l in range(L):
+        K, R, b = (w["enc%d_%s" % (l, k)] for k in "KRb")
+        K = K[:f_rows] if l == 0 else K
+        hs, h, c, res = lstm_layer_train(x, K, R, b, act=act)
+        out["enc_hs"].append(hs); out["enc_res"].append(res); out["hT"].append(h); out["cT"].append(c)
+        out["z_enc"].append(regime_preactivations(x, K, R, b, hs))
+        state.append((h, c))
+        x = hs
+    x = dec_in[:, :, :o_rows]
+    for l in range(L):
+        K, R, b = (w["dec%d_%s" % (l, k)] for k in "KRb")
+        K = K[:o_rows] if l == 0 else K
+        h0, c0 = state[l - 1] if mistake == "decoder layer l seeded from encoder layer l - 1" else state[l]
+        hs, _, _, res = lstm_layer_train(x, K, R, b, h0, c0, act=act)
+        out["dec_hs"].append(hs); out["dec_res"].append(res)
+        out["z_dec"].append(regime_preactivations(x, K, R, b, hs, h0))
+        x = hs
+    return {k: (np.stack(v) if k in STACKED_TRAIN_TAPES else v) for k, v in out.items()}
+
+
+def _bptt_from_reserve(res, c0, R, K, din, dh, dc, act, late):
+    """One layer's BPTT from its reserve (B,T,5,H): dh_t = din_t + dz_{t+1} . R^T, c_{t-1} = the reserve's c of step t - 1 (c0 at
+    t = 0; late: of step t) -> (dz (B,T,4H), dx (B,T,H) or None without K, dh_0, dc_0)."""
+    B, T, _, H = res.shape
+    dz_all = np.zeros((B, T, 4 * H), res.dtype)
+    for t in range(T - 1, -1, -1):
+        c_prev = res[:, t, 4] if late else (res[:, t - 1, 4] if t > 0 else c0)
+        dz, dc = _gates_bwd(res[:, t], c_prev, dh if din is None else dh + din[:, t], dc, act)
+        dz_all[:, t] = dz
+        dh = dz @ R.T
+    return dz_all, (None if K is None else dz_all @ K.T), dh, dc
+
+
+def stacked_train_backward(tp, dhs_top, w, L, act, dt=np.float64, mistake=None):
+    """fov_stacked_seq2seq_train_bwd in dtype dt on GIVEN tapes (enc_res, dec_res, cT) -> dict(enc_dz (L,B,T_in,4H), dec_dz
+    (L,B,T_out,4H)).  mistake: a layer below another gets no dx from it; c_{t-1} read from step t; the decoder's dc_0 does not
+    reach the encoder (dh_0 does)."""
+    assert mistake is None or mistake in STACKED_TRAIN_MISTAKES
+    c_ = lambda a: np.asarray(a, dt)
+    w = {k: c_(v) for k, v in w.items()}
+    enc_res, dec_res, cT, dhs_top = c_(tp["enc_res"]), c_(tp["dec_res"]), c_(tp["cT"]), c_(dhs_top)
+    B, H = cT.shape[1], cT.shape[2]
+    late, no_dx = mistake == "c_prev one step late", mistake == "dx of the layer above dropped"
+    zero = np.zeros((B, H), dt)
+    dec_dz, enc_dz, seed = [None] * L, [None] * L, [None] * L
+    din = dhs_top
+    for l in range(L - 1, -1, -1):
+        dec_dz[l], dx, dh0, dc0 = _bptt_from_reserve(dec_res[l], cT[l], w["dec%d_R" % l], w["dec%d_K" % l] if l else None, din, zero, zero,
+                                                     act, late)
+        seed[l] = (dh0, zero if mistake == "decoder dc_0 not handed to the encoder" else dc0)
+        din = None if no_dx else dx
+    din = None
+    for l in range(L - 1, -1, -1):
+        enc_dz[l], dx, _, _ = _bptt_from_reserve(enc_res[l], zero, w["enc%d_R" % l], w["enc%d_K" % l] if l else None, din, seed[l][0],
+                                                 seed[l][1], act, late)
+        din = None if no_dx else dx
+    return {"enc_dz": np.stack(enc_dz), "dec_dz": np.stack(dec_dz)}

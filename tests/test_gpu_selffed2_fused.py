@@ -1,7 +1,8 @@
 """The self-fed two-layer decoder's unroll as ONE launch per direction (fov_selffed2_decoder_fwd / _bwd, lstm_selffed2.hip)
-against fp64 references written here: a NumPy restatement of the entry points' two loops (forward with every tape; backward on
-GIVEN tapes) and torch.autograd in fp64 for every gradient.  The whole-model cases also run oracle.others_context_forward
-(given_others_gt_mean_var_seq2seq.py:203-299, heads target_user_only / others_mlp / others_lstm).
+against fp64 references (tests/test_tile_train_host.py: forward64 / backward64, a NumPy restatement of the entry points' two loops -
+forward with every tape, backward on GIVEN tapes - and autograd64, torch.autograd in fp64 for every gradient).  The whole-model
+cases also run oracle.others_context_forward (given_others_gt_mean_var_seq2seq.py:203-299, heads target_user_only / others_mlp /
+others_lstm).
 
 Bounds - the project's written ones and nothing looser:
     outputs and tapes:  |gpu - ref| <= 2e-5  AND  |gpu - ref| <= 1e-3 |ref| + 1e-5, per element;
@@ -22,11 +23,12 @@ import pytest
 import torch
 
 from oracle import fov_oracle as O
+from test_tile_train_host import STATES, _step_t, autograd64, backward64, forward64      # the fp64 references, shared with the guarded-view tests
+
+TAPES = O.SELFFED2_TAPES
 
 pytestmark = pytest.mark.gpu
 
-STATES = ("h1_0", "c1_0", "h2_0", "c2_0")
-TAPES = ("H1", "C1", "H2", "C2", "XY", "RES1", "RES2")
 BWD_OUT = ("DPRE", "DZ1", "DZ2", "dx0", "dh1_0", "dc1_0", "dh2_0", "dc2_0")
 LAYER_W = ("dec1_K", "dec1_R", "dec1_b", "dec2_K", "dec2_R", "dec2_b")
 
@@ -37,134 +39,6 @@ def dev(a):
 
 def f64(w):
     return {k: v.astype(np.float64) for k, v in w.items()}
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-# fp64 references
-# ------------------------------------------------------------------------------------------------------------------------------
-def _rec_np(act):
-    if act == "sigmoid":
-        return lambda z: 1.0 / (1.0 + np.exp(-z))
-    return lambda z: np.clip(0.2 * z + 0.5, 0.0, 1.0)
-
-
-def _rec_grad_np(act, a):
-    """s'(z) from the stored gate a, as Keras autodiff evaluates it."""
-    return a * (1.0 - a) if act == "sigmoid" else np.where((a > 0.0) & (a < 1.0), 0.2, 0.0)
-
-
-def _cell_np(z, c, act, H):
-    s = _rec_np(act)
-    i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), np.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
-    c = f * c + i * g
-    return o * np.tanh(c), c, np.stack([i, f, g, o, c], 1)
-
-
-def forward64(x0, st, w, T, act):
-    """fov_selffed2_decoder_fwd's loop in fp64 -> every output in the entry point's layout, and the pre-activations."""
-    w = f64(w)
-    B, O_ = x0.shape
-    H = w["dec1_R"].shape[0]
-    z0 = np.zeros((B, H))
-    h1, c1, h2, c2 = (z0 if st.get(k) is None else st[k].astype(np.float64) for k in STATES)
-    x = x0.astype(np.float64)
-    tp = {"H1": [h1], "C1": [c1], "H2": [h2], "C2": [c2], "XY": [x], "RES1": [], "RES2": [], "z": []}
-    for t in range(T):
-        z1 = w["dec1_b"] + x @ w["dec1_K"] + h1 @ w["dec1_R"]
-        h1, c1, r1 = _cell_np(z1, c1, act, H)
-        z2 = w["dec2_b"] + h1 @ w["dec2_K"] + h2 @ w["dec2_R"]
-        h2, c2, r2 = _cell_np(z2, c2, act, H)
-        p = h2 @ w["W"]
-        if "bd" in w:
-            p = w["bd"] + p
-        if "ctx" in w:
-            p = p + w["ctx"][:, t]
-        x = np.tanh(p)
-        for k, v in (("H1", h1), ("C1", c1), ("H2", h2), ("C2", c2), ("XY", x), ("RES1", r1[:, None]), ("RES2", r2[:, None])):
-            tp[k].append(v)
-        tp["z"] += [z1, z2]
-    out = {k: np.stack(tp[k]) if tp[k] else np.zeros((0, B, 1, 5, H)) for k in TAPES}
-    out["y"] = np.ascontiguousarray(out["XY"][1:].transpose(1, 0, 2))
-    out["hT"], out["cT"] = np.stack([h1, h2]), np.stack([c1, c2])
-    margin = np.inf
-    if act == "hard_sigmoid":
-        for z in tp["z"]:
-            gates = np.concatenate([z[:, :2 * H], z[:, 3 * H:]], 1)
-            margin = min(margin, float(np.abs(np.abs(gates) - 2.5).min()))
-    return out, margin
-
-
-def backward64(tp, dloss, w, act):
-    """fov_selffed2_decoder_bwd's loop in fp64 on GIVEN tapes (C1, C2, XY, RES1, RES2)."""
-    w = f64(w)
-    T, B, O_ = dloss.shape
-    H = w["dec1_R"].shape[0]
-    tp = {k: np.asarray(tp[k], dtype=np.float64) for k in ("C1", "C2", "XY", "RES1", "RES2")}
-
-    def gates_bwd(res, c_prev, dh, dc):
-        i, f, g, o, c = (res[:, 0, k] for k in range(5))
-        tc = np.tanh(c)
-        dcv = dc + dh * o * (1.0 - tc * tc)
-        dz = np.concatenate([dcv * g * _rec_grad_np(act, i), dcv * c_prev * _rec_grad_np(act, f), dcv * i * (1.0 - g * g),
-                             dh * tc * _rec_grad_np(act, o)], 1)
-        return dz, dcv * f
-    out = {"DPRE": np.zeros((T, B, O_)), "DZ1": np.zeros((T, B, 4 * H)), "DZ2": np.zeros((T, B, 4 * H))}
-    dx, dz1, dz2 = np.zeros((B, O_)), np.zeros((B, 4 * H)), np.zeros((B, 4 * H))
-    dc1, dc2 = np.zeros((B, H)), np.zeros((B, H))
-    for t in range(T - 1, -1, -1):
-        y = tp["XY"][t + 1]
-        dpre = (dloss[t] + dx) * (1.0 - y * y)
-        dh2 = dpre @ w["W"].T + dz2 @ w["dec2_R"].T
-        dz2, dc2 = gates_bwd(tp["RES2"][t], tp["C2"][t], dh2, dc2)
-        dh1 = dz2 @ w["dec2_K"].T + dz1 @ w["dec1_R"].T
-        dz1, dc1 = gates_bwd(tp["RES1"][t], tp["C1"][t], dh1, dc1)
-        dx = dz1 @ w["dec1_K"].T
-        out["DPRE"][t], out["DZ1"][t], out["DZ2"][t] = dpre, dz1, dz2
-    out.update(dx0=dx, dh1_0=dz1 @ w["dec1_R"].T, dc1_0=dc1, dh2_0=dz2 @ w["dec2_R"].T, dc2_0=dc2)
-    return out
-
-
-def _rec_t(act):
-    return torch.sigmoid if act == "sigmoid" else (lambda z: torch.clamp(0.2 * z + 0.5, 0, 1))
-
-
-def _step_t(x, h, c, K, R, b, act, zs):
-    H = R.shape[0]
-    z = b + x @ K + h @ R
-    z.retain_grad()
-    zs.append(z)
-    s = _rec_t(act)
-    i, f, g, o = s(z[:, :H]), s(z[:, H:2 * H]), torch.tanh(z[:, 2 * H:3 * H]), s(z[:, 3 * H:])
-    c = f * c + i * g
-    return o * torch.tanh(c), c
-
-
-def autograd64(x0, st, w, dloss, T, act):
-    """The same unroll on fp64 torch tensors -> (y, every gradient of sum_t <y_t, dloss_t> the backward entry returns)."""
-    leaf = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), requires_grad=True)
-    B, H = x0.shape[0], w["dec1_R"].shape[0]
-    t = {k: leaf(v) for k, v in w.items()}
-    x = x0_ = leaf(x0)
-    s0 = {k: leaf(np.zeros((B, H)) if st.get(k) is None else st[k]) for k in STATES}
-    h1, c1, h2, c2 = (s0[k] for k in STATES)
-    z1s, z2s, ps, ys = [], [], [], []
-    for tt in range(T):
-        h1, c1 = _step_t(x, h1, c1, t["dec1_K"], t["dec1_R"], t["dec1_b"], act, z1s)
-        h2, c2 = _step_t(h1, h2, c2, t["dec2_K"], t["dec2_R"], t["dec2_b"], act, z2s)
-        p = h2 @ t["W"]
-        if "bd" in t:
-            p = t["bd"] + p
-        if "ctx" in t:
-            p = p + t["ctx"][:, tt]
-        p.retain_grad()
-        x = torch.tanh(p)
-        ps.append(p); ys.append(x)
-    y = torch.stack(ys, 1)
-    (y * torch.tensor(dloss.astype(np.float64)).transpose(0, 1)).sum().backward()
-    gr = lambda seq: np.stack([a.grad.numpy() for a in seq])
-    g = {"DPRE": gr(ps), "DZ1": gr(z1s), "DZ2": gr(z2s), "dx0": x0_.grad.numpy()}
-    g.update({"d" + k: s0[k].grad.numpy() for k in STATES})
-    return y.detach().numpy(), g
 
 
 def _weights(rng, H, n_out, ctx_shape, bd):
