@@ -239,19 +239,26 @@ int fov_dense_bwd_bf16(const float* x, const float* W, const float* dpre, float*
                        int N, int In, int Out, int accumulate,
                        void* workspace, size_t workspace_bytes, fov_stream_t stream);
 
-/* BPTT of fov_lstm_stack2_fwd's two layers (mycode/lstm.py:218-240 under the train_op of :556-567) in ONE persistent launch: the
- * upper layer's recurrence, the data-gradient product dx = dz2 . K2^T and the lower layer's recurrence run as three roles on
- * disjoint CUs, the lower layer about a step behind the upper one (as two fov_lstm_seq_bwd calls: recurrence, split product,
- * reduce, recurrence, one after the other).  Arguments are those of the two calls: layer 1 = lower (input x (B,T,F), tape hs1,
- * reserve1), layer 2 = upper (input hs1, tape hs2, reserve2); dhs2 (B,T,H) / dhT2 / dcT2 / dhT1 / dcT1 optional upstream
- * gradients; dz1, dz2 (B,T,4H) out; dK / dR / db of either layer optional (NULL: data path only); dh0 / dc0 optional.  The
- * gradient with respect to x is NOT produced (lstm.py's first layer needs none).  Results equal the two-call path's up to the
- * summation order of dx (sixteen partial sums added in slice order instead of a split GEMM's reduce).
- * Shapes: fov_lstm_stack2_bwd_supported (H = 512, at most 32 sequences on 256 CUs).  The width is decided first: H != 512 is
- * FOV_ERR_UNSUPPORTED whatever B and T are.  At H = 512 an empty call (B = 0 or T = 0) is taken - it zeroes the weight gradients
- * (accumulate = 0) and, at T = 0, passes dhT / dcT through to dh0 / dc0 - although the predicate answers 0 for it (there is
- * nothing to fuse).  workspace: stateful like every exchange
- * workspace (zero-filled once), fov_lstm_stack2_bwd_workspace_bytes. */
+/* BPTT of two stacked LSTM layers in ONE launch, then the two layers' weight gradients.  Arguments are those of two
+ * fov_lstm_seq_bwd calls (upper layer first, its dx as the lower layer's dhs): layer 1 = lower (input x (B,T,F), tape hs1,
+ * reserve1), layer 2 = upper (input hs1, tape hs2, reserve2); h0_* / c0_* (B,H) or NULL (zero initial states);
+ * dhs2 (B,T,H) / dhT2 / dcT2 / dhT1 / dcT1 optional upstream gradients;
+ * dz1, dz2 (B,T,4H) out; dK / dR / db of either layer optional (NULL: data path only); dh0 / dc0 optional.  The gradient with
+ * respect to x is NOT produced.  Two forms, chosen by the width, which is decided first and as arithmetic: H = 32, 64 or 512,
+ * anything else is FOV_ERR_UNSUPPORTED whatever B and T are.
+ *   H = 512 (fov_lstm_stack2_fwd's layers, mycode/lstm.py:218-240 under the train_op of :556-567): one persistent launch in which
+ *     the upper layer's recurrence, the data-gradient product dx = dz2 . K2^T and the lower layer's recurrence run as three roles
+ *     on disjoint CUs, the lower layer about a step behind the upper one; at most 32 sequences on 256 CUs.  Results equal the
+ *     two-call path's up to the summation order of dx (sixteen partial sums added in slice order instead of a split GEMM's
+ *     reduce).  The workspace is stateful like every exchange workspace (zero-filled once).
+ *   H = 32 / 64 (the encoder of given_others_gt_mean_var_seq2seq.py at its own latent_dim): one workgroup per tile of 16 sequences
+ *     walks the upper layer, then the lower one; any batch (up to 2^30 sequences) and any T.  dx reaches the lower layer through dz1
+ *     itself (the first H floats of every step, overwritten by dz1 afterwards): no exchange, nothing to wait for.  The workspace
+ *     is plain scratch for the weight-gradient products; its header is neither read nor written.  dK / dR / db are what
+ *     fov_lstm_seq_wgrad_layers gives on dz1 and dz2, bit for bit.
+ * Shapes: fov_lstm_stack2_bwd_supported (1 at H = 32 / 64 for B, T, F >= 1).  An empty call (B = 0 or T = 0) of a width that is
+ * taken zeroes the weight gradients (accumulate = 0) and, at T = 0, passes dhT / dcT through to dh0 / dc0 - although the
+ * predicate answers 0 for it (there is nothing to fuse).  workspace: fov_lstm_stack2_bwd_workspace_bytes. */
 int fov_lstm_stack2_bwd_supported(int B, int T, int F, int H);
 size_t fov_lstm_stack2_bwd_workspace_bytes(int B, int T, int F, int H);
 int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const float* R2,

@@ -315,7 +315,11 @@ int fov_lstm_seq_bwd_bf16(const float* x, const float* K, const float* R, const 
     return lstm_seq_bwd_entry(l, workspace, workspace_bytes, stream);
 }
 
-int fov_lstm_stack2_bwd_supported(int B, int T, int F, int H) { return (F > 0 && bwd16_pair_shape(B, T, H)) ? 1 : 0; }
+// H = 32 / 64 (one workgroup per tile): arithmetic alone, any batch; H = 512: the three-role kernel's residency
+int fov_lstm_stack2_bwd_supported(int B, int T, int F, int H) {
+    if (stack2_tile_bwd_width(H)) return (B >= 1 && B <= kMaxTileBatch && T >= 1 && F >= 1) ? 1 : 0;
+    return (F > 0 && bwd16_pair_shape(B, T, H)) ? 1 : 0;
+}
 
 size_t fov_lstm_stack2_bwd_workspace_bytes(int B, int T, int F, int H) {
     if (B <= 0 || T < 0 || F <= 0 || H <= 0) return 256;
@@ -334,7 +338,8 @@ int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const 
         return FOV_ERR_INVALID;
     }
     // the width rule first, as arithmetic: an empty batch of a width the kernel does not have is refused like a full one
-    if (H != 512) { set_error("fov_lstm_stack2_bwd: H = 512 only (got H=%d)", H); return FOV_ERR_UNSUPPORTED; }
+    const bool tile = stack2_tile_bwd_width(H);
+    if (!tile && H != 512) { set_error("fov_lstm_stack2_bwd: H = 32, 64 or 512 only (got H=%d)", H); return FOV_ERR_UNSUPPORTED; }
     if (B == 0 || T == 0) {
         hipStream_t s = (hipStream_t)stream;
         int rc = accumulate ? FOV_OK : zero_lstm_wgrads(dK1, dR1, db1, F, H, s);
@@ -350,8 +355,9 @@ int fov_lstm_stack2_bwd(const float* x, const float* R1, const float* K2, const 
         }
         return rc;
     }
-    if (!bwd16_pair_shape(B, T, H)) {
-        set_error("fov_lstm_stack2_bwd: H = 512, at most 32 sequences, three role-groups of sixteen workgroups per tile resident only");
+    if (tile ? B > kMaxTileBatch : !bwd16_pair_shape(B, T, H)) {
+        set_error("fov_lstm_stack2_bwd: H = 512 with at most 32 sequences and three role-groups of sixteen workgroups per tile resident, "
+                  "or H = 32 / 64 with at most 2^30 sequences only");
         return FOV_ERR_UNSUPPORTED;
     }
     if (int rc = check_ws(workspace, workspace_bytes, fov_lstm_stack2_bwd_workspace_bytes(B, T, F, H))) return rc;

@@ -327,6 +327,10 @@ int launch_bwd16(const BwdRec& r, int B, int T, int H, int act, void* xch_ws, hi
 // ... two stacked width-512 layers as one launch: `low` takes its dhs from `up` through K2 inside the kernel (low.dhs is not read)
 bool bwd16_pair_shape(int B, int T, int H);
 int launch_bwd16_pair(const BwdRec& up, const BwdRec& low, const float* K2, int B, int T, int act, void* xch_ws, hipStream_t stream);
+// lstm_stacked_train.hip: the same two-layer contract at H = 32 / 64, one workgroup per 16-sequence tile, any batch, no workspace;
+// up's dx reaches low through low.dz itself
+bool stack2_tile_bwd_width(int H);
+int launch_stack2_tile_bwd(const BwdRec& up, const BwdRec& low, const float* K2, int B, int T, int H, int act, hipStream_t stream);
 // lstm_bwd8.hip: groups of eight workgroups (H = 256), fp32 or bf16 operands; K_dx and dx: dx = dz K^T inside the kernel
 // (fp32: dx = eight partial tapes [slice][B][T][256])
 bool bwd8_preferred(int B, int H);

@@ -25,6 +25,9 @@
 // step.  The step-interleaved order would need every layer's transposes at once (320 KB at HP = 64, L = 3).  dx goes from layer l
 // to layer l-1 through a plain (B, max T, HP) scratch: the lane that writes an element is the lane that reads it, one
 // __syncthreads() (workgroup-scope release / acquire) between the layers orders the two.  No atomics, no spin.
+//
+// stack2_tile_bwd_kernel is the same layer walk for two stacked layers whose gradients come from outside (fov_lstm_stack2_bwd at
+// H = 32 / 64: the encoder of the others-mixing and others-context models under a decoder with kernels of its own).
 #include "stacked_tile.h"
 
 namespace fov {
@@ -283,11 +286,14 @@ __device__ __forceinline__ void stage_transposed(f32x4* sT, const float* W, int 
 }
 
 // BPTT of one layer over its T steps.  res / dz: the layer's slices (B, T, 5 HP) / (B, T, 4 HP); c0 (B, HP) or NULL (zero);
-// din (B, din_T, HP) or NULL: the gradient that reaches h_t from above; dh / dc: in (dh_T, dc_T), out (dh_0, dc_0).  HASK: also
-// dx_t = dz_t . K^T into p_dx (B, dx_T, HP).
+// din (B, din_T, din_ld >= HP) or NULL: the gradient that reaches h_t from above; dh / dc: in (dh_T, dc_T), out (dh_0, dc_0).
+// HASK: also dx_t = dz_t . K^T into p_dx (B, dx_T, dx_ld >= HP).  din may lie inside dzo (din_ld = 4 HP, the gate-i slot of every
+// step: stack2_tile_bwd_kernel): the lane that reads din of (row, t, unit) is the one that overwrites it with dz_t afterwards, and
+// load_step(t - 1) touches only step t - 1.
 template <int HP, int ACT, bool HASK>
-__device__ __forceinline__ void bwd_layer(float* smem, const float* res, const float* c0, const float* din, int din_T, const float* R,
-                                          const float* K, float* dzo, float* p_dx, int dx_T, int B, int T, f32x4& dh_io, float (&dc)[4]) {
+__device__ __forceinline__ void bwd_layer(float* smem, const float* res, const float* c0, const float* din, int din_T, int din_ld,
+                                          const float* R, const float* K, float* dzo, float* p_dx, int dx_T, int dx_ld, int B, int T,
+                                          f32x4& dh_io, float (&dc)[4]) {
     constexpr int NW = HP / 16, H4 = 4 * HP, NJ4 = H4 / 16, LDZ = st_ldz(HP);
     f32x4* sRT = (f32x4*)smem;                        // [NW][NJ4][64]
     f32x4* sKT = sRT + HP * HP;                       // the same for K
@@ -318,7 +324,7 @@ __device__ __forceinline__ void bwd_layer(float* smem, const float* res, const f
             go[r] = on ? q[3 * HP] : 0.f;
             cc[r] = on ? q[4 * HP] : 0.f;
             cp[r] = !on ? 0.f : t > 0 ? q[4 * HP - 5 * HP] : c0 ? c0[row * HP + unit] : 0.f;
-            dn[r] = (on && din) ? din[(row * din_T + t) * HP + unit] : 0.f;
+            dn[r] = (on && din) ? din[(row * din_T + t) * din_ld + unit] : 0.f;
         }
     };
     load_step(T - 1);
@@ -378,7 +384,7 @@ __device__ __forceinline__ void bwd_layer(float* smem, const float* res, const f
                 const f32x4 dxv = (k4[0] + k4[1]) + (k4[2] + k4[3]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (r < live) p_dx[((size_t)(row0 + r) * dx_T + t) * HP + unit] = dxv[r];
+                    if (r < live) p_dx[((size_t)(row0 + r) * dx_T + t) * dx_ld + unit] = dxv[r];
             }
         }
         __syncthreads();
@@ -406,8 +412,8 @@ __global__ __launch_bounds__(4 * HP, 1) void stacked_train_bwd_kernel(StackedTra
         float* dzo = p.dec_dz + (size_t)l * B * T_out * 4 * HP;
         const float* din = l == L - 1 ? p.dhs_top : p.dx;
         const int din_T = l == L - 1 ? T_out : Tmax;
-        if (l > 0) bwd_layer<HP, ACT, true>(st_smem, res, c0, din, din_T, p.dR[l], p.dK[l], dzo, p.dx, Tmax, B, T_out, dh[l], dc[l]);
-        else bwd_layer<HP, ACT, false>(st_smem, res, c0, din, din_T, p.dR[l], nullptr, dzo, nullptr, 0, B, T_out, dh[l], dc[l]);
+        if (l > 0) bwd_layer<HP, ACT, true>(st_smem, res, c0, din, din_T, HP, p.dR[l], p.dK[l], dzo, p.dx, Tmax, HP, B, T_out, dh[l], dc[l]);
+        else bwd_layer<HP, ACT, false>(st_smem, res, c0, din, din_T, HP, p.dR[l], nullptr, dzo, nullptr, 0, 0, B, T_out, dh[l], dc[l]);
     }
     // ---- encoder stack: layer l takes decoder layer l's (dh_0, dc_0) as its (dh_T, dc_T) ----
 #pragma unroll
@@ -415,9 +421,71 @@ __global__ __launch_bounds__(4 * HP, 1) void stacked_train_bwd_kernel(StackedTra
         const float* res = p.enc_res + (size_t)l * B * T_in * 5 * HP;
         float* dzo = p.enc_dz + (size_t)l * B * T_in * 4 * HP;
         const float* din = l == L - 1 ? nullptr : p.dx;
-        if (l > 0) bwd_layer<HP, ACT, true>(st_smem, res, nullptr, din, Tmax, p.eR[l], p.eK[l], dzo, p.dx, Tmax, B, T_in, dh[l], dc[l]);
-        else bwd_layer<HP, ACT, false>(st_smem, res, nullptr, din, Tmax, p.eR[l], nullptr, dzo, nullptr, 0, B, T_in, dh[l], dc[l]);
+        if (l > 0) bwd_layer<HP, ACT, true>(st_smem, res, nullptr, din, Tmax, HP, p.eR[l], p.eK[l], dzo, p.dx, Tmax, HP, B, T_in, dh[l], dc[l]);
+        else bwd_layer<HP, ACT, false>(st_smem, res, nullptr, din, Tmax, HP, p.eR[l], nullptr, dzo, nullptr, 0, 0, B, T_in, dh[l], dc[l]);
     }
+}
+
+// BPTT of two stacked layers that takes its gradients from outside (fov_lstm_stack2_bwd at H = 32 / 64): the upper layer, then the
+// lower one, each from its own (dh_T, dc_T) and to its own (dh_0, dc_0).  The upper layer's dx_t = dz2_t . K2^T is staged in the
+// lower layer's dz tape itself - the first HP floats of dz1[row][t], row stride 4 HP - which the lower layer reads as its din and
+// then overwrites with its own dz_t (bwd_layer's comment: same lane, one step at a time).  No scratch, no header, no wait.
+struct Stack2TileBwdParams {
+    BwdRec up, low;                     // db_part of neither is written, low.dhs is not read
+    const float* K2;
+    int B, T;
+};
+
+// (dh, dc) of the lane's rows 4 g4 + r and unit: zeros for a NULL pointer and for rows beyond B
+template <int HP>
+__device__ __forceinline__ void load_state_grad(f32x4& dh, float (&dc)[4], const float* dhT, const float* dcT, int row0, int unit, int live) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const size_t at = (size_t)(row0 + r) * HP + unit;
+        dh[r] = (dhT && r < live) ? dhT[at] : 0.f;
+        dc[r] = (dcT && r < live) ? dcT[at] : 0.f;
+    }
+}
+
+template <int HP>
+__device__ __forceinline__ void store_state_grad(const f32x4& dh, const float (&dc)[4], float* dh0, float* dc0, int row0, int unit, int live) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r < live) {
+            const size_t at = (size_t)(row0 + r) * HP + unit;
+            if (dh0) dh0[at] = dh[r];
+            if (dc0) dc0[at] = dc[r];
+        }
+}
+
+template <int HP, int ACT>
+__global__ __launch_bounds__(4 * HP, 1) void stack2_tile_bwd_kernel(Stack2TileBwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) float st_smem[];
+    const int B = p.B, T = p.T;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int unit = 16 * wave + (lane & 15);
+    const int row0 = blockIdx.x * SS_BT + 4 * (lane >> 4);
+    const int live = min(max(B - row0, 0), 4);
+    f32x4 dh;
+    float dc[4];
+    // ---- upper layer: dz2, and dx_t into the gate-i slot of dz1's step t ----
+    load_state_grad<HP>(dh, dc, p.up.dhT, p.up.dcT, row0, unit, live);
+    bwd_layer<HP, ACT, true>(st_smem, p.up.reserve, p.up.c0, p.up.dhs, T, HP, p.up.R, p.K2, p.up.dz, p.low.dz, T, 4 * HP, B, T, dh, dc);
+    store_state_grad<HP>(dh, dc, p.up.dh0, p.up.dc0, row0, unit, live);
+    // ---- lower layer: din from its own dz tape ----
+    load_state_grad<HP>(dh, dc, p.low.dhT, p.low.dcT, row0, unit, live);
+    bwd_layer<HP, ACT, false>(st_smem, p.low.reserve, p.low.c0, p.low.dz, T, 4 * HP, p.low.R, nullptr, p.low.dz, nullptr, 0, 0, B, T, dh, dc);
+    store_state_grad<HP>(dh, dc, p.low.dh0, p.low.dc0, row0, unit, live);
+}
+
+template <int HP>
+int launch_stack2_tile(const Stack2TileBwdParams& p, int act, hipStream_t stream) {
+    void (*kern)(Stack2TileBwdParams) = act == FOV_ACT_HARD_SIGMOID ? stack2_tile_bwd_kernel<HP, FOV_ACT_HARD_SIGMOID>
+                                                                    : stack2_tile_bwd_kernel<HP, FOV_ACT_SIGMOID>;
+    const size_t lds = (size_t)st_bwd_lds_floats(HP) * sizeof(float);
+    if (int rc = ensure_dynamic_lds((const void*)kern, lds, 4 * HP)) return rc;
+    hipLaunchKernelGGL(kern, dim3((p.B + SS_BT - 1) / SS_BT), dim3(4 * HP), lds, stream, p);
+    return launch_check("two-layer tile BPTT");
 }
 
 template <int HP, int L>
@@ -455,6 +523,15 @@ bool all_there(const float* const* a, int L, int first = 0) {
 }
 
 }  // namespace
+
+bool stack2_tile_bwd_width(int H) { return H == 32 || H == 64; }
+
+int launch_stack2_tile_bwd(const BwdRec& up, const BwdRec& low, const float* K2, int B, int T, int H, int act, hipStream_t stream) {
+    if (B <= 0 || T <= 0) return FOV_OK;
+    if (!stack2_tile_bwd_width(H) || B > kMaxTileBatch) { set_error("two-layer tile BPTT: H = 32 or 64 only (got H=%d B=%d)", H, B); return FOV_ERR_UNSUPPORTED; }
+    Stack2TileBwdParams p = {up, low, K2, B, T};
+    return H == 32 ? launch_stack2_tile<32>(p, act, stream) : launch_stack2_tile<64>(p, act, stream);
+}
 
 }  // namespace fov
 

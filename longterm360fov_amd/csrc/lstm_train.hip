@@ -443,7 +443,7 @@ int lstm_seq_bwd(const LstmBwdLayer& l, float* ws, size_t ws_floats, hipStream_t
     return FOV_OK;
 }
 
-// BPTT of two stacked width-512 layers in ONE launch (lstm_bwd16.hip: both recurrences and dx = dz2 . K2^T between them as three
+// BPTT of two stacked layers in ONE launch.  Width 512 (lstm_bwd16.hip: both recurrences and dx = dz2 . K2^T between them as three
 // roles of one persistent kernel), then the two layers' weight-gradient products.  Same outputs as two lstm_seq_bwd calls
 // (upper layer first, its dx as the lower layer's dhs) except that the intermediate dx is not materialised.
 // The workspace: behind the header and the granule area the two layers' bias partials and four (B,H) of state gradients the
@@ -465,8 +465,21 @@ static Stack2Carve stack2_carve(int B, int T, int F, int H) {
 
 size_t lstm_stack2_bwd_workspace_floats(int B, int T, int F, int H) { return stack2_carve(B, T, F, H).total; }
 
+// At H = 32 / 64 (stack2_tile_bwd_kernel, lstm_stacked_train.hip): one workgroup per 16-sequence tile walks both layers, any batch;
+// the workspace's header and granule area are neither read nor written, what lies behind them is the scratch of the products.
+// The kernel writes no bias partials: db is the column sum of dz, with dK and dR through lstm_seq_wgrad_layers.
+static int lstm_stack2_tile_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up, float* ws, size_t ws_floats, hipStream_t stream) {
+    const int B = low.B, T = low.T, H = low.H;
+    const Stack2Carve carve = stack2_carve(B, T, low.F, H);
+    if (ws_floats < carve.total) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    if (int rc = launch_stack2_tile_bwd(up.rec, low.rec, up.K, B, T, H, low.act, stream)) return rc;
+    const LayerWgrad wg[2] = {low.wg, up.wg};
+    return lstm_seq_wgrad_layers(2, wg, B, H, low.accumulate, ws + carve.scratch, ws_floats - carve.scratch, stream);
+}
+
 int lstm_stack2_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up, float* ws, size_t ws_floats, hipStream_t stream) {
     const int B = low.B, T = low.T, H = low.H, accumulate = low.accumulate;
+    if (stack2_tile_bwd_width(H)) return lstm_stack2_tile_bwd(low, up, ws, ws_floats, stream);
     if (!bwd16_pair_shape(B, T, H)) { set_error("lstm_stack2_bwd: unsupported shape (H = 512, <= 32 sequences on 256 CUs)"); return FOV_ERR_UNSUPPORTED; }
     const Stack2Carve carve = stack2_carve(B, T, low.F, H);
     if (ws_floats < carve.total) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }

@@ -766,7 +766,9 @@ def lstm_stack2_bwd_supported(B, T, F, H):
 
 def lstm_stack2_bwd(x, layer1, layer2, tape1, tape2, dhs2=None, dhT2=None, dcT2=None, dhT1=None, dcT1=None, grads1=None, grads2=None,
                     need_state_grads=False, act="sigmoid", accumulate=False, scratch=None):
-    """BPTT of two stacked width-512 layers in one launch (fov_lstm_stack2_bwd).  layer1 = (K1, R1), layer2 = (K2, R2);
+    """BPTT of two stacked layers in one launch, then their weight gradients (fov_lstm_stack2_bwd): width 512 at up to 32 sequences
+    (three roles of one persistent kernel), width 32 / 64 at any batch (one workgroup per 16-sequence tile, `scratch` is plain
+    scratch there).  lstm_stack2_bwd_supported says which shapes.  layer1 = (K1, R1), layer2 = (K2, R2);
     tape = (hs, reserve, h0, c0) of the training forward; grads = (dK, dR, db) tensors or None (data path only).
     -> dict(dz1, dz2, dh0_1, dc0_1, dh0_2, dc0_2)."""
     x = _dev(x, "x")

@@ -946,6 +946,13 @@ def others_context_order(mode):
     return base
 
 
+def _fused_encoder_widths(flag):
+    """The widths at which a trainer's `fused_encoder_bwd` asks for the one-launch encoder BPTT (fp32, H = 32 / 64)."""
+    if flag is True:
+        return (32, 64)
+    return tuple(flag) if flag else ()
+
+
 class OthersContextTrainer(FlatParamTrainer):
     """Training step of the other decoder heads of mycode/given_others_gt_mean_var_seq2seq.py (2+2-layer model, no teacher
     forcing, Adam + MSE): `target_user_only` (:219-220), `others_mlp` (:153-156,223-233), `others_lstm` (two Bidirectional
@@ -954,7 +961,13 @@ class OthersContextTrainer(FlatParamTrainer):
     loop (y_t = tanh(h2_t W_h + [ctx_t W_c + b])) and so is its gradient.  The unrolled decoder is ONE launch per direction
     (lstm_selffed2.hip: the forward at width 32 or 64, the BPTT at width 32; the two choices are independent and both write /
     read the walk's tapes) or, for every other width, under FOV_NO_SELFFED2_FUSED=1 and for impl != 'auto', walked step by
-    step on the layer kernels; weight gradients are one product over all steps."""
+    step on the layer kernels; weight gradients are one product over all steps.  The two encoder layers' BPTT is one launch at
+    width 32 (`fused_encoder_bwd`)."""
+
+    # the two encoder layers' BPTT as ONE launch (ops.lstm_stack2_bwd's one-workgroup-per-tile form) instead of two ops.lstm_seq_bwd
+    # calls: True = at both widths it is built for (32, 64), False = exactly the two calls, a tuple = at those widths.  Width 32 (the
+    # host-stepped walk otherwise) wins at every measured shape of the three modes; width 64 is not measured for this trainer.
+    fused_encoder_bwd = (32,)
 
     def __init__(self, weights, mode, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda"):
         assert mode in ("target_user_only", "others_mlp", "others_lstm")
@@ -1091,10 +1104,17 @@ class OthersContextTrainer(FlatParamTrainer):
                 t1, t2 = ctape
                 ds1, dinit = self._bi_bwd(dctx.reshape(B, T_out, 2 * H), t2, 2, None, need_dx=True)
                 self._bi_bwd(ds1, t1, 1, dinit, need_dx=False)
-        e2 = ops.lstm_seq_bwd(hs1, w["enc2_K"], w["enc2_R"], hs2, res2, dhT=dh2, dcT=dc2, dK=g["enc2_K"], dR=g["enc2_R"],
-                              db=g["enc2_b"], need_dx=True, act=act, accumulate=True, scratch=bsc)
-        ops.lstm_seq_bwd(enc, w["enc1_K"], w["enc1_R"], hs1, res1, dhs=e2["dx"], dhT=dh1, dcT=dc1, dK=g["enc1_K"], dR=g["enc1_R"],
-                         db=g["enc1_b"], act=act, accumulate=True, scratch=bsc)
+        if H in _fused_encoder_widths(self.fused_encoder_bwd) and impl != "generic" and ops.lstm_stack2_bwd_supported(B, T_in, enc.shape[2], H):
+            # both encoder layers' BPTT as ONE launch from the decoder's (dh_0, dc_0), then one weight-gradient launch
+            ops.lstm_stack2_bwd(enc, (w["enc1_K"], w["enc1_R"]), (w["enc2_K"], w["enc2_R"]), (hs1, res1, None, None),
+                                (hs2, res2, None, None), dhT2=dh2, dcT2=dc2, dhT1=dh1, dcT1=dc1,
+                                grads1=(g["enc1_K"], g["enc1_R"], g["enc1_b"]), grads2=(g["enc2_K"], g["enc2_R"], g["enc2_b"]),
+                                act=act, accumulate=True, scratch=bsc)
+        else:
+            e2 = ops.lstm_seq_bwd(hs1, w["enc2_K"], w["enc2_R"], hs2, res2, dhT=dh2, dcT=dc2, dK=g["enc2_K"], dR=g["enc2_R"],
+                                  db=g["enc2_b"], need_dx=True, act=act, accumulate=True, scratch=bsc)
+            ops.lstm_seq_bwd(enc, w["enc1_K"], w["enc1_R"], hs1, res1, dhs=e2["dx"], dhT=dh1, dcT=dc1, dK=g["enc1_K"], dR=g["enc1_R"],
+                             db=g["enc1_b"], act=act, accumulate=True, scratch=bsc)
         loss = self._weigh(loss, grad_weight)
         return loss, out
 
@@ -1208,6 +1228,11 @@ class OthersMixingTrainer(FlatParamTrainer):
     fused_decoder_bwd = True   # H = 256: BPTT through the unrolled decoder as ONE launch; False = step-wise calls
 
     tile_decoder = False       # H = 32 / 64 at the model's own width: the one-workgroup-per-tile kernels (opt-in, see __init__)
+    # tile_decoder only: the two encoder layers' BPTT as ONE launch (ops.lstm_stack2_bwd's one-workgroup-per-tile form) instead of
+    # two ops.lstm_seq_bwd calls: True = at both widths it is built for (32, 64), False = exactly the two calls, a tuple = at those
+    # widths.  Width 32 (the host-stepped walk otherwise) wins at every measured shape; at width 64 the two calls are one persistent
+    # launch each already and the rule does not hold.  The FOV_WGRAD_ENC_SIDE form keeps the two calls.
+    fused_encoder_bwd = (32,)
 
     def __init__(self, weights, act="sigmoid", impl="auto", optimizer="adam", lr=1e-3, device="cuda", dtype="f32", tile_decoder=False):
         """dtype 'bf16' (BASELINE configs[4], H = 256): forward and backward matrix products take bf16 operands on the
@@ -1217,8 +1242,9 @@ class OthersMixingTrainer(FlatParamTrainer):
         launch at that width (fov_mix_decoder_fwd's one-workgroup-per-tile kernel, the same tapes), its BPTT one launch at H = 32
         and the step-wise walk over the fused forward's tapes at H = 64, and the two encoder layers are one launch
         (ops.stacked_seq2seq_train_fwd with T_out = 0) where that call takes the shape.  fused_decoder / fused_decoder_bwd = False
-        still select the step-wise calls.  Weight gradients, the encoder's BPTT, the optimizer and the data-parallel path are
-        the same calls as without it."""
+        still select the step-wise calls.  The two encoder layers' BPTT is one ops.lstm_stack2_bwd call at the widths
+        `fused_encoder_bwd` names (default: 32) and the two ops.lstm_seq_bwd calls otherwise.  Weight gradients of the decoder, the
+        optimizer and the data-parallel path are the same calls as without it."""
         assert dtype in ("f32", "bf16")
         self.act, self.impl, self.dtype = act, impl, dtype
         self._alloc(weights, _MIX_ORDER, optimizer, lr, device)
@@ -1400,6 +1426,21 @@ class OthersMixingTrainer(FlatParamTrainer):
         # bf16: layer 2's own products go under layer 1's recurrence too (they sat between the two BPTT launches, 35 us of the
         # critical path); fp32: in line (its products are 3x as long, the recurrences slow down more than is gained)
         enc_side = side is not None and os.environ.get("FOV_WGRAD_ENC_SIDE", "1" if dt == "bf16" else "0") == "1"
+        fused_enc = (H in _fused_encoder_widths(self.fused_encoder_bwd) and tile and not enc_side
+                     and ops.lstm_stack2_bwd_supported(B, T_in, enc.shape[2], H))
+        if fused_enc:   # both recurrences as ONE launch from the decoder's (dh_0, dc_0), then one weight-gradient launch
+            if split_side:
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    decoder_wgrads(2)
+                    ops.reduce_defer_flush(self.grad)
+            ops.lstm_stack2_bwd(enc, (w["enc1_K"], w["enc1_R"]), (w["enc2_K"], w["enc2_R"]), (hs1, res1, None, None),
+                                (hs2, res2, None, None), dhT2=dh2_rec, dcT2=dc2, dhT1=dh1_rec, dcT1=dc1,
+                                grads1=(g["enc1_K"], g["enc1_R"], g["enc1_b"]), grads2=(g["enc2_K"], g["enc2_R"], g["enc2_b"]),
+                                act=act, accumulate=acc, scratch=bsc)
+            if side is not None:
+                main.wait_stream(side)
+            return loss, out
         if enc_side:
             e2 = ops.lstm_seq_bwd(hs1, w["enc2_K"], w["enc2_R"], hs2, res2, dhT=dh2_rec, dcT=dc2, need_dx=True, act=act,
                                   scratch=bsc, dtype=dt, need_weight_grads=False)
@@ -2219,7 +2260,8 @@ class TFLSTMTrainer(FlatParamTrainer):
         """Asked at every step (a cheap C call): the answer depends on FOV_NO_STACK2 and the CU count the library sees, which
         ops._sync_env reloads live - a cached answer would send a later step into a launch that now refuses."""
         B, T, F = tape[0][0].shape
-        return ops.lstm_stack2_bwd_supported(B, T, F, self.w["R0"].shape[0])
+        H = self.w["R0"].shape[0]      # width 512 only: a small model padded to 64 keeps its per-layer calls
+        return H == 512 and ops.lstm_stack2_bwd_supported(B, T, F, H)
 
     def _stack_backward(self, tape, dhT, masks, accumulate, need_dx0=False):
         w, g = self.w, self.g
