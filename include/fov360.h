@@ -404,7 +404,10 @@ size_t fov_mix_decoder_bwd_workspace_bytes(int B, int H);
  * workspaces; the NEXT fov_mix_decoder_fwd / _bwd on a marked workspace with the same dec2_K skips its own pack.  The caller
  * orders the streams (the launch must come behind the pack).  The mark is valid for that one launch and only while dec2_K's
  * CONTENTS are unchanged (it is keyed by pointer: a caller that updates the weights in place packs again); fov_workspace_init and
- * the reset inside fov_check_status erase it, since they zero the packed copy.  H = 256 (another H: FOV_ERR_INVALID); both
+ * the reset inside fov_check_status erase it, since they zero the packed copy; so does every other call that keeps something
+ * of its own behind the workspace's granule area, where the packed copy lies (fov_lstm_seq_bwd, fov_lstm_stack2_bwd, the
+ * two-launch cluster decode, the width-512 layer that projects its input first, fov_seq2seq_tf_fwd, the step-wise layer):
+ * the launch behind such a call packs again.  H = 256 (another H: FOV_ERR_INVALID); both
  * workspaces are checked against their size functions before the first pack is launched. */
 int fov_mix_decoder_prepack(const float* dec2_K, void* workspace_fwd, size_t fwd_bytes, void* workspace_bwd, size_t bwd_bytes,
                             int H, fov_stream_t stream);

@@ -91,6 +91,7 @@ static int launch_lstm_fwd(const FwdPlan& plan, LstmParams& p, void* workspace, 
         case FwdKernel::Wide512:
             if (plan.project_x) {
                 float* zx = (float*)((char*)workspace + cluster_workspace_bytes(p.B, p.H));
+                prepack_forget(workspace);   // the projection lies where mix_decoder_prepack leaves its packed dec2_K
                 if (p.B > 0 && p.T > 0)
                     if (int rc = matmul_f32(p.x, p.K, zx, p.B * p.T, p.F, 4 * p.H, zx + (size_t)p.B * p.T * 4 * p.H, kWide512ScratchFloats, s))
                         return rc;
@@ -100,6 +101,7 @@ static int launch_lstm_fwd(const FwdPlan& plan, LstmParams& p, void* workspace, 
         case FwdKernel::Wide: return launch_wide(p, s);
         case FwdKernel::Cluster: return launch_cluster(p, false, s);
         case FwdKernel::Stepwise:
+            prepack_forget(workspace);   // (its buffers start at the header's end and may reach behind the granule area)
             return launch_stepwise(p, (float*)((char*)workspace + kStatusBytes), (workspace_bytes - kStatusBytes) / sizeof(float), s);
         case FwdKernel::Generic: break;
     }
@@ -640,6 +642,7 @@ int fov_seq2seq_tf_fwd(const float* enc_in, const float* dec_in, const float* en
     float* hT = (float*)((char*)workspace + at.state);
     float* cT = hT + (size_t)B * H;
     float* hs = (float*)((char*)workspace + at.hs);
+    prepack_forget(workspace);   // state and hidden sequence lie where mix_decoder_prepack leaves its packed dec2_K
     rc = fov_lstm_seq_fwd(enc_in, enc_K, enc_R, enc_b, nullptr, nullptr, nullptr, hT, cT, B, T_in, F_enc, H, act,
                           impl, workspace, at.state, stream);
     if (rc) return rc;

@@ -1560,6 +1560,7 @@ int launch_cluster(const LstmParams& p_in, bool decode, hipStream_t stream) {
     }
     LstmParams enc = p;
     float* state = (float*)((char*)p.status + kStatusBytes + kXchBytes);
+    prepack_forget(p.status);   // the carried state overwrites the head of a packed dec2_K (mix_decoder_prepack) on this workspace
     enc.hT = state;
     enc.cT = state + (size_t)p.B * p.H;
     enc.hs = nullptr;

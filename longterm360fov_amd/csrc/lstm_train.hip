@@ -387,6 +387,7 @@ int lstm_seq_bwd(const LstmBwdLayer& l, float* ws, size_t ws_floats, hipStream_t
     }
     float *dh_rec = ws + plan.carve.dh_rec, *dc = ws + plan.carve.dc, *scratch = ws + plan.carve.scratch;
     const size_t scratch_floats = ws_floats - plan.carve.scratch;
+    prepack_forget(ws);   // carries and scratch lie where mix_decoder_prepack leaves its packed dec2_K
     int rc;
     if (plan.rec != BwdRecurrence::Stepped) {
         // one launch for the whole recurrence: dz (B,T,4H), dh0, dc0
@@ -472,6 +473,7 @@ static int lstm_stack2_tile_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up,
     const int B = low.B, T = low.T, H = low.H;
     const Stack2Carve carve = stack2_carve(B, T, low.F, H);
     if (ws_floats < carve.total) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    prepack_forget(ws);   // (as lstm_seq_bwd)
     if (int rc = launch_stack2_tile_bwd(up.rec, low.rec, up.K, B, T, H, low.act, stream)) return rc;
     const LayerWgrad wg[2] = {low.wg, up.wg};
     return lstm_seq_wgrad_layers(2, wg, B, H, low.accumulate, ws + carve.scratch, ws_floats - carve.scratch, stream);
@@ -483,6 +485,7 @@ int lstm_stack2_bwd(const LstmBwdLayer& low, const LstmBwdLayer& up, float* ws, 
     if (!bwd16_pair_shape(B, T, H)) { set_error("lstm_stack2_bwd: unsupported shape (H = 512, <= 32 sequences on 256 CUs)"); return FOV_ERR_UNSUPPORTED; }
     const Stack2Carve carve = stack2_carve(B, T, low.F, H);
     if (ws_floats < carve.total) { set_error("lstm_stack2_bwd: workspace too small"); return FOV_ERR_WORKSPACE; }
+    prepack_forget(ws);   // (as lstm_seq_bwd)
     const size_t bh = (size_t)B * H;
     float *spare = ws + carve.spare, *scratch = ws + carve.scratch;
     const size_t scratch_floats = ws_floats - carve.scratch;
